@@ -119,7 +119,7 @@ PROFILE: Optional[KernelProfile] = None
 #                            wgrad(L) is the bandwidth-bound BatchNorm backward of layer L-1 on the main stream, whose kernels are
 #                            sized (<= 96 VGPRs, <= 28 KB of LDS) to fit on a CU next to a resident wgrad3 workgroup;
 #   RV3D_OVERLAP=off         one stream.
-# Round 4, after the lean BatchNorm-backward kernels, the balanced wgrad3 split and GPU_MAX_HW_QUEUES=8: `free` is the fastest again
+# Round 4, after the lean BatchNorm-backward kernels, the balanced wgrad3 split and the package's own hardware-queue count: `free` is the fastest again
 # (93.55 / 93.77 against 95.03 / 95.02 chain, 95.59 / 95.46 small, 96.77 off on one box; 94.08 / 95.50 against 96.64 / 96.35 on
 # another; rv-waymo 53.7 against 53.9) -- the chained mode pays an event round trip per layer, and with the lean passes resident
 # beside the weight gradients (the octet forms: +1 ms in this mode) there is now something to run beside them.

@@ -46,10 +46,11 @@ def build_plugins(kwargs):
     return hydra_instantiate(kw["_backbone"]), hydra_instantiate(kw["_head"]), hydra_instantiate(kw["_decoder"])
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="composes /root/reference/conf (build container only)")
 @pytest.mark.parametrize("experiment", EXPERIMENTS)
 def test_composed_conf_tree_equals_the_committed_kwargs(experiment):
-    fresh = cc.plugin_kwargs(experiment)
+    # where the reference's conf/ tree is at hand it is composed afresh and must equal the committed fixture; everywhere else the
+    # fixture stands in for it, and everything below is asserted on the fixture
+    fresh = cc.plugin_kwargs(experiment) if HAVE_REF else cc.load_fixture()[experiment]
     assert cc.from_wire(cc.to_wire(fresh)) == fresh  # (the wire form loses nothing: integer keys, .inf)
     assert fresh == cc.load_fixture()[experiment], "tests/golden/conf_kwargs.json is stale: python tests/tools/compose_conf.py"
     # the interpolations the constructors depend on, spelled out (range_view.yaml:71, :81-83, :94, :131)
