@@ -333,6 +333,170 @@ def gen_tiny_model() -> None:
     save("tiny_model", **out)
 
 
+def _open_gates(module: torch.nn.Module, shift: float = 2.0) -> None:
+    """BatchNorm biases moved up so that nearly every ReLU gate is open: with biases around zero the four-column tensors of the
+    1/16-resolution stage hold pre-activations within fp32 accumulation noise of zero, and two CORRECT fp32 formulations of
+    the model then differ by per cent in a parameter gradient (a flipped gate), which would force a tolerance that hides real errors."""
+    for m in module.modules():
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.bias.data += shift
+
+
+def _coarse(module: torch.nn.Module, step: float = 1.0 / 64) -> None:
+    """Every floating-point parameter and buffer rounded to a multiple of ``step``: any weights are valid weights, and these compress
+    to under a byte each (random fp32 weights do not compress at all and would be most of the fixture)."""
+    for t in list(module.parameters()) + list(module.buffers()):
+        if t.dtype.is_floating_point:
+            t.data = torch.round(t.data / step) * step
+
+
+def pack(out: dict, prefix: str, tensors: dict) -> None:
+    """A {name: tensor} dict as THREE arrays instead of one per entry (a zip member costs ~250 bytes, a state dict of this model has
+    450 entries): ``<prefix>/index`` = one line ``name dtype d0,d1,...`` per entry, ``<prefix>/f32`` / ``<prefix>/i64`` = the values,
+    flattened and concatenated in index order.  Read back by ``unpack`` in tests/test_oracle_golden.py."""
+    lines, f32, i64 = [], [], []
+    for name, t in tensors.items():
+        t = t.detach()
+        kind = "f32" if t.dtype.is_floating_point else "i64"
+        (f32 if kind == "f32" else i64).append(t.reshape(-1).to(torch.float32 if kind == "f32" else torch.int64))
+        lines.append(f"{name} {kind} {','.join(str(d) for d in t.shape)}")
+    out[f"{prefix}/index"] = np.asarray("\n".join(lines))
+    out[f"{prefix}/f32"] = torch.cat(f32) if f32 else torch.zeros(0)
+    out[f"{prefix}/i64"] = torch.cat(i64) if i64 else torch.zeros(0, dtype=torch.int64)
+
+
+GRAD_PROBES = 4
+
+
+def grad_summary(name: str, grad: torch.Tensor) -> torch.Tensor:
+    """[norm, <grad, r_1>, ..., <grad, r_4>] with r_k standard-normal vectors seeded by the parameter's NAME (crc32): every element
+    of the gradient enters every projection with its own random weight, so an error of relative size e anywhere moves a
+    projection by about e * norm -- the whole gradient in five numbers (the gradients are fp32 noise to a compressor: stored
+    element-wise they would be as large as the weights were before ``_coarse``).  The stem's gradients are ALSO stored element-wise."""
+    import zlib
+
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    g = grad.detach().double().reshape(-1)
+    r = torch.randn(GRAD_PROBES, g.numel(), generator=gen, dtype=torch.float64)
+    return torch.cat([g.norm().reshape(1), r @ g])
+
+
+def gen_basic_model() -> None:
+    """RangeNet(BASIC stem, layers=[8, 8, 16, 16, 16]) + DetectionHead(fpn {1: 16}, towers 16): the shape of the default config
+    tree (conf/model/range_view.yaml, conf/model/baseline.yaml: base-av2 / base-waymo) with every width divided by eight.
+    layers[0] == layers[1] != layers[2], as shipped, so an aggregation block built from the wrong entry of ``layers`` shows.
+    Recipe of gen_tiny_model on 2 x 4 x 64 sweeps; plus a backbone-only case with six input channels (the waymo feature set) on the
+    same trunk.  Kept small (weights on a coarse grid, dicts packed, gradients as norm + random projections): under 400 KiB."""
+    g = torch.Generator().manual_seed(21)
+    torch.manual_seed(21)
+    B, H, W, NCLS = 2, 4, 64, 5
+    widths = [8, 8, 16, 16, 16]
+    L = ListConfig(widths)
+    backbone = RangeNet(
+        in_channels=5, layers=L, out_channels=widths[0], projection_kernel_size=1, dataset_name="av2", num_neighbors=3,
+        num_layers=2, stem_type="BASIC",
+        _net=DictConfig(_target_="torchbox3d.nn.backbones.dla.RangeBackbone", in_channels=5, layers=L, out_channels=widths[0]),
+    )
+    C = 2 * widths[0]  # level 1 = cat(stem, agg3)
+    tasks = DictConfig({0: ListConfig([f"C{i}" for i in range(NCLS)])})
+    tcfg = DictConfig(
+        dataset_name="av2", tasks=tasks, enable_azimuth_invariant_targets=True,
+        range_partitions=DictConfig({1: [0.0, math.inf]}), fpn_assignment_method=None, k=math.inf,
+        affinity_fn="GAUSSIAN", normalize_affinities=False, sigma=0.75,
+    )
+    head = DetectionHead(
+        fpn=DictConfig({1: C}), fpn_kernel_sizes=DictConfig({1: ListConfig([3, 3])}), targets_config=tcfg,
+        num_classification_blocks=4, num_regression_blocks=4, final_kernel_size=1, tasks_cfg=tasks,
+        task_in_channels=C, classification_weight=1.0, regression_weight=1.0,
+        coding_weights=ListConfig([1.0] * 8), classification_head_channels=C, regression_head_channels=C,
+        classification_normalization_method="FOREGROUND",
+        _cls_loss=DictConfig(_target_="torchbox3d.nn.losses.classification.VarifocalLoss", alpha=0.75, gamma=2.0, reduction="none"),
+        _regression_loss=DictConfig(_target_="torch.nn.L1Loss", reduction="none"),
+    )
+    randomize_bn(backbone, g)
+    randomize_bn(head, g)
+    _open_gates(backbone)
+    _open_gates(head)
+    for name, p in head.named_parameters():
+        if name.endswith("0.weight"):
+            p.data = 0.08 * torch.randn(p.shape, generator=g)
+    head.classification_head["1"]["0"].blocks[-1][0].bias.data.fill_(-1.0)
+    _coarse(backbone)
+    _coarse(head)
+    features, cart, mask = synthetic_sweep(g, B, H, W, smooth=True)
+    ann = make_annotations(g, cart, mask, n_per=6, n_cls=NCLS)
+    frame = Frame({c: ann[:, i] for i, c in enumerate(COLS)})
+
+    out: dict = {"features": features, "cart": cart, "mask": mask, "annotations": ann}
+    sd0 = {**{f"backbone.{k}": v.clone() for k, v in backbone.state_dict().items()}, **{f"head.{k}": v.clone() for k, v in head.state_dict().items()}}
+    pack(out, "sd", sd0)
+
+    backbone.train()
+    head.train()
+    data = {"features": features, "cart": cart, "mask": mask, "annotations": frame}
+    feats = backbone(data)
+    outputs, losses = head(feats, data, return_loss=True)
+    losses["loss"].backward()
+    for s, t in feats.items():
+        out[f"feat/{s}"] = t
+    out["logits"] = outputs[1][0]["logits"]
+    out["regressands"] = outputs[1][0]["regressands"]
+    for k in ("classification_labels", "panoptics", "regression_targets", "points_per_obj"):
+        out[f"targets/{k}"] = data[1][0][k]
+    out["targets/soft"] = data[1][0]["targets"]
+    pack(out, "loss", {k: v.reshape(1) for k, v in losses.items() if isinstance(v, torch.Tensor) and "/" not in k})
+    grads = {**{f"backbone.{k}": p.grad for k, p in backbone.named_parameters()}, **{f"head.{k}": p.grad for k, p in head.named_parameters()}}
+    pack(out, "grad_summary", {k: grad_summary(k, v) for k, v in grads.items()})
+    pack(out, "grad", {k: v for k, v in grads.items() if k.startswith("backbone.stem.")})
+    after = {**{f"backbone.{k}": v.clone() for k, v in backbone.state_dict().items()}, **{f"head.{k}": v.clone() for k, v in head.state_dict().items()}}
+    pack(out, "sd_after", {k: v for k, v in after.items() if "running_" in k})
+
+    backbone.load_state_dict({k[len("backbone."):]: v for k, v in sd0.items() if k.startswith("backbone.")})
+    head.load_state_dict({k[len("head."):]: v for k, v in sd0.items() if k.startswith("head.")})
+    backbone.eval()
+    head.eval()
+    with torch.no_grad():
+        data = {"features": features, "cart": cart, "mask": mask}
+        feats = backbone(data)
+        outputs, _ = head(feats, data, return_loss=False)
+        out["eval/logits"] = outputs[1][0]["logits"]
+        out["eval/regressands"] = outputs[1][0]["regressands"]
+        dec = RangeDecoder(True, True, ListConfig([0, 15, 30]), ListConfig([15, 30, math.inf]), ListConfig([8, 2, 1]))
+        params, scores, cats, bidx = dec.decode(
+            outputs, DictConfig(num_pre_nms=50000, num_post_nms=1000, nms_threshold=0.3, min_confidence=0.1, nms_mode="WEIGHTED"),
+            tasks, use_nms=False,
+        )
+        out["eval/dec_params"], out["eval/dec_scores"], out["eval/dec_categories"], out["eval/dec_batch_index"] = params, scores, cats, bidx
+
+    # six input channels (the waymo feature set): the same trunk (its weights are the backbone.net.* entries above) behind a stem of its
+    # own -- train forward, stem gradients of sum(feature^2) / 2, running statistics of the stem, eval output of the stem (the first half of level 1 = [stem, agg3])
+    net6 = RangeNet(
+        in_channels=6, layers=L, out_channels=widths[0], projection_kernel_size=1, dataset_name="waymo", num_neighbors=3,
+        num_layers=2, stem_type="BASIC",
+        _net=DictConfig(_target_="torchbox3d.nn.backbones.dla.RangeBackbone", in_channels=6, layers=L, out_channels=widths[0]),
+    )
+    randomize_bn(net6.stem, g)
+    _open_gates(net6.stem)
+    _coarse(net6.stem)
+    net6.net.load_state_dict({k[len("backbone.net."):]: v for k, v in sd0.items() if k.startswith("backbone.net.")})
+    f6, cart6, mask6 = synthetic_sweep(g, B, H, W, n_feat=6, smooth=True)
+    out["c6/features"], out["c6/cart"], out["c6/mask"] = f6, cart6, mask6
+    sd6 = {k: v.clone() for k, v in net6.state_dict().items()}
+    pack(out, "c6/sd", {k: v for k, v in sd6.items() if k.startswith("stem.")})
+    net6.train()
+    feats = net6({"features": f6, "cart": cart6, "mask": mask6})
+    for s, t in feats.items():
+        out[f"c6/feat/{s}"] = t
+    sum(0.5 * (t**2).sum() for t in feats.values()).backward()
+    pack(out, "c6/grad", {f"stem.{k}": p.grad for k, p in net6.stem.named_parameters()})
+    pack(out, "c6/sd_after", {f"stem.{k}": v.clone() for k, v in net6.stem.state_dict().items() if "running_" in k})
+    net6.load_state_dict(sd6)
+    net6.eval()
+    with torch.no_grad():
+        out["c6/eval_stem"] = net6({"features": f6, "cart": cart6, "mask": mask6})[1][:, : widths[0]]
+    save("basic_model", **out)
+
+
 def gen_decode() -> None:
     g = torch.Generator().manual_seed(4)
     B, H, W, NCLS = 2, 8, 64, 7
@@ -873,7 +1037,7 @@ def gen_detections_frame() -> None:
 
 
 ALL = ("conv_blocks", "meta_kernel", "range_partition", "decode", "projection", "tiny_model", "augment", "loader_item", "raw_sweep", "nms_wrapper",
-       "loader_train_item", "detections_frame")  # in dependency order: nms_wrapper reads tiny_model / decode, detections_frame reads nms_wrapper
+       "loader_train_item", "detections_frame", "basic_model")  # in dependency order: nms_wrapper reads tiny_model / decode, detections_frame reads nms_wrapper
 
 
 if __name__ == "__main__":

@@ -27,11 +27,18 @@ EMULATION = {
     "rv-waymo": {"emu~fp32": 0.004899260393146024, "reg emu~fp32": 0.01794988154751432, "cos_logits": 0.9999993211445424,
                  "cos_reg": 0.999920294573489, "loss32": 0.7749601747592445, "loss16": 0.774672120470353,
                  "grad_cos_median": 0.9966902366019017, "grad_cos_q05": 0.9841837880888346, "grad_cos_min": 0.9597309407237882},
+    # the base models (BASIC stem, layers [64, 64, 128, 128, 128], towers 128), same tool, 8 threads
+    "base-av2": {"emu~fp32": 0.004759569415091149, "reg emu~fp32": 0.01995814708871327, "cos_logits": 0.9999994244495308,
+                 "cos_reg": 0.9998998213024213, "loss32": 0.9637800748402937, "loss16": 0.963851266960579,
+                 "grad_cos_median": 0.996778199366995, "grad_cos_q05": 0.9913501579539131, "grad_cos_min": 0.9668336298437605},
+    "base-waymo": {"emu~fp32": 0.005080894217616061, "reg emu~fp32": 0.018263220683924223, "cos_logits": 0.9999995368116108,
+                   "cos_reg": 0.9999502125618025, "loss32": 0.9251870548159752, "loss16": 0.9252379662266835,
+                   "grad_cos_median": 0.998170634478962, "grad_cos_q05": 0.9847190772977913, "grad_cos_min": 0.9567327898137814},
     "first-step": {"loss32": 0.8670136843224887, "loss16": 0.8670791479993034},
 }
 
 
-@pytest.mark.parametrize("widths,n_feat,n_cls,W", [("rv-av2", 5, 26, 2048), ("rv-waymo", 6, 3, 2656)])
+@pytest.mark.parametrize("widths,n_feat,n_cls,W", [("rv-av2", 5, 26, 2048), ("rv-waymo", 6, 3, 2656), ("base-av2", 5, 26, 2048), ("base-waymo", 6, 3, 2656)])
 def test_full_size_train_step_vs_oracle(widths, n_feat, n_cls, W):
     from test_gpu_realwidth import _train_step_vs_oracle
 

@@ -1,4 +1,5 @@
-"""Teacher-forced per-layer parity at the REAL channel widths: every conv (+ BatchNorm) unit of the rv-av2 and rv-waymo models.
+"""Teacher-forced per-layer parity at the REAL channel widths: every conv (+ BatchNorm) unit of the rv-av2, rv-waymo, base-av2 and
+base-waymo models (the base models print the census of which kernel each of their layers lands on).
 
 The composed-model tests (test_gpu_realwidth.py) bound the END of ~60 bf16 layers; a wrong epilogue in one of the ~160 layer
 launches could hide inside those margins.  Here the oracle's bf16 run (``oracle.model.Numerics.bf16`` with ``trace``) records,
@@ -25,7 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from test_gpu_forward import DEV, rel_err
-from test_gpu_realwidth import _small_grids, _prepare
+from test_gpu_realwidth import _small_grids, _prepare, stem_type_of
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +49,7 @@ def _ref_unit(rec, w):
     return y.detach(), dx, dw
 
 
-@pytest.mark.parametrize("widths,n_feat,n_cls,W", [("rv-av2", 5, 26, 256), ("rv-waymo", 6, 3, 336)])
+@pytest.mark.parametrize("widths,n_feat,n_cls,W", [("rv-av2", 5, 26, 256), ("rv-waymo", 6, 3, 336), ("base-av2", 5, 26, 256), ("base-waymo", 6, 3, 336)])
 def test_every_layer_teacher_forced(widths, n_feat, n_cls, W):
     from bench import Detector
     from oracle import model as om
@@ -61,7 +62,7 @@ def test_every_layer_teacher_forced(widths, n_feat, n_cls, W):
     nm = om.Numerics.bf16(train=True)
     nm.trace = []
     params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.dtype.is_floating_point and "running_" not in k}
-    _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, nm=nm)
+    _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, stem_type=stem_type_of(widths), nm=nm)
     tg = otgt.compute_targets(batch["cart"], batch["annotations"], n_cls)
     otgt.detection_loss(logits, reg, batch["cart"], batch["mask"], tg, n_cls)["loss"].backward()
     trace = nm.trace
@@ -69,7 +70,8 @@ def test_every_layer_teacher_forced(widths, n_feat, n_cls, W):
 
     model = Detector(backbone, head).to(DEV).train()
     modules = dict(model.named_modules())
-    C0 = modules["backbone.stem"].out_channels
+    C0 = backbone.layers[0]
+    census = {}  # (forward, backward-data, weight-gradient) kernel names -> layers
     ran, worst = set(), {"fwd": (0.0, ""), "dgrad": (0.0, ""), "wgrad": (0.0, ""), "mean": (0.0, ""), "invstd": (0.0, "")}
 
     def note(kind, err, name):
@@ -91,8 +93,11 @@ def test_every_layer_teacher_forced(widths, n_feat, n_cls, W):
                 y_ref, dx_ref, dw_ref = _ref_unit(rec, sd[name])
                 t = E.Tape(True, DEV)
                 x_act = E.Act.from_nchw(om.round_bf16(x).to(DEV).to(torch.bfloat16).contiguous(memory_format=torch.channels_last))
-                first = name.startswith("backbone.stem.projection") and x.shape[1] == n_feat or "positional_kernel.0" in name
+                # the layers whose input is the sweep itself need no input gradient: the stem convs that read the n_feat feature channels (META:
+                # stem.projection.net.0 / .projection_block.0; BASIC: stem.net.0 / stem.projection_block.0) and the first positional conv
+                first = name.startswith("backbone.stem.") and x.shape[1] == n_feat or "positional_kernel.0" in name
                 final = rec["bn"] is None
+                n_rec = len(E.PROFILE.records)
                 conv = E.ConvOp(t, layer, x_act, stats=not final, out_f32=final, need_input_grad=not first)
                 if final:
                     y = conv.out_t[..., : layer.c_out].permute(0, 3, 1, 2).float().cpu()
@@ -136,13 +141,22 @@ def test_every_layer_teacher_forced(widths, n_feat, n_cls, W):
                     e = rel_err(dx, om.round_bf16(ref))
                     note("dgrad", e, name)
                     assert e < 8e-3, (name, "backward-data", e)
+                census.setdefault(tuple(r[0] for r in E.PROFILE.records[n_rec:]), []).append(name[: -len(".weight")])
             torch.cuda.synchronize()
             ran = set(n for n, *_ in E.PROFILE.records)
         finally:
             E.PROFILE = None
     print(f"[{widths}] {len(trace)} units; worst " + "  ".join(f"{k} {v[0]:.2e} ({v[1].split('.weight')[0][-40:]})" for k, v in worst.items()))
-    need = {"tapconv4_kernel<128>", "wgrad3_kernel(+reduce)"}
-    assert need <= ran and any(n.startswith(("tapconv5_kernel<", "tapconv6_kernel<")) for n in ran), (need - ran, sorted(ran))
+    if widths.startswith("base-"):
+        # census: which kernels (forward, backward-data, weight gradient) each layer of the model lands on
+        for kernels, layers in sorted(census.items(), key=lambda kv: -len(kv[1])):
+            print(f"    census[{widths}] {len(layers):3d} x {' | '.join(kernels)}: {', '.join(n[len('backbone.'):] if n.startswith('backbone.') else n for n in layers[:4])}" + (" ..." if len(layers) > 4 else ""))
+        assert "tapconv2_kernel<2>" in ran and any(n.startswith("tapconv_kernel<") for n in ran), sorted(ran)
+        assert {"wgrad_kernel(+reduce)", "wgrad2_kernel(+reduce)"} <= ran, sorted(ran)
+        assert any(n.startswith(("tapconv5_kernel<", "tapconv6_kernel<")) for n in ran), sorted(ran)
+    else:
+        need = {"tapconv4_kernel<128>", "wgrad3_kernel(+reduce)"}
+        assert need <= ran and any(n.startswith(("tapconv5_kernel<", "tapconv6_kernel<")) for n in ran), (need - ran, sorted(ran))
 
 
 def test_rv_waymo_full_size_eval_forward_vs_oracle():

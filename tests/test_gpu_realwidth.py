@@ -2,6 +2,9 @@
 
 * rv-av2 widths  (layers [256,128,128,128,128], towers 512, 26 classes, 5 features) on a 1 x 64 x 256 crop;
 * rv-waymo widths ([128]*5, towers 256, 3 classes, 6 features) on a 1 x 64 x 336 crop (width not a multiple of 64);
+* base-av2 / base-waymo widths (BASIC stem, layers [64,64,128,128,128], towers 128: the config tree's defaults) on the same crops --
+  their 64-channel layers run on ``tapconv2_kernel<2>`` and the generic kernel, their weight gradients on ``wgrad_kernel`` /
+  ``wgrad2_kernel``, and the 128-wide towers take the UNFUSED tower-final backward;
 * one full-size (1 x 64 x 2048) eval forward of the rv-av2 model.
 
 On crops this small the library's speed heuristic would pick the register-staged kernels (too few tiles to fill 256 CUs), so
@@ -41,13 +44,13 @@ def _check_forward(m):
         assert m[f"{got}~fp32"] < 1.5 * m[emu] + 1e-2, m
 
 
-def _check_direction(logits, lg16, lg32, reg, rg16, rg32):
+def _check_direction(logits, lg16, lg32, reg, rg16, rg32, floor=0.99):
     """Cosine against the fp32 oracle: > 0.99, and no worse than the CPU bf16 emulation's by more than 2e-3.  ``lg16`` / ``rg16``:
     the emulation's tensors, or its RECORDED cosines (floats: the full-size tests' yardstick, tests/tools/emulation_yardstick.py)."""
     for name, got, emu, ref in (("logits", logits, lg16, lg32), ("regressands", reg, rg16, rg32)):
         c, c_emu = _cos(got, ref), (emu if isinstance(emu, float) else _cos(emu, ref))
         print(f"    {name}: cosine vs fp32 oracle {c:.5f} (CPU bf16 emulation {c_emu:.5f})")
-        assert c > 0.99 and c > c_emu - 2e-3, (name, c, c_emu)
+        assert c > floor and c > c_emu - 2e-3, (name, c, c_emu)
 
 
 def _envelope(key):
@@ -60,8 +63,43 @@ def _envelope(key):
         return json.load(f)["cases"].get(key)
 
 
+def stem_type_of(widths):
+    """The stem of a width set: the base-* models (the config tree's defaults) have the BASIC stem."""
+    return "BASIC" if widths.startswith("base-") else "META"
+
+
+def build_model(widths, n_cls, n_feat=5):
+    """``bench.build_model`` for the width sets bench.py measures; the base-av2 / base-waymo models (the defaults of the reference's
+    conf/model/range_view.yaml + baseline.yaml: BASIC stem, layers [64, 64, 128, 128, 128], towers 128) are built here, with the same
+    constructor arguments -- the benchmark has no section for them."""
+    import math
+
+    import bench
+
+    if not widths.startswith("base-"):
+        return bench.build_model(widths, n_cls, n_feat)
+    from range_view_3d_detection_amd.nn.backbones.dla import RangeNet
+    from range_view_3d_detection_amd.nn.heads.detection_head import DetectionHead
+
+    layers, head_c = [64, 64, 128, 128, 128], 128
+    backbone = RangeNet(in_channels=n_feat, layers=layers, out_channels=layers[0], projection_kernel_size=1, dataset_name="av2",
+                        num_neighbors=3, num_layers=2, stem_type="BASIC",
+                        _net={"_target_": "torchbox3d.nn.backbones.dla.RangeBackbone", "in_channels": n_feat, "layers": layers, "out_channels": layers[0]})
+    tasks = {0: [f"C{i}" for i in range(n_cls)]}
+    tcfg = {"dataset_name": "av2", "tasks": tasks, "enable_azimuth_invariant_targets": True, "range_partitions": {1: [0.0, math.inf]},
+            "fpn_assignment_method": None, "k": math.inf, "affinity_fn": "GAUSSIAN", "normalize_affinities": False, "sigma": 0.75}
+    head = DetectionHead(fpn={1: 2 * layers[0]}, fpn_kernel_sizes={1: [3, 3]}, targets_config=tcfg, num_classification_blocks=4,
+                         num_regression_blocks=4, final_kernel_size=1, tasks_cfg=tasks, task_in_channels=layers[0],
+                         classification_weight=1.0, regression_weight=1.0, coding_weights=[1.0] * 8,
+                         classification_head_channels=head_c, regression_head_channels=head_c,
+                         classification_normalization_method="FOREGROUND",
+                         _cls_loss={"_target_": "torchbox3d.nn.losses.classification.VarifocalLoss", "alpha": 0.75, "gamma": 2.0, "reduction": "none"},
+                         _regression_loss={"_target_": "torch.nn.L1Loss", "reduction": "none"})
+    return backbone, head
+
+
 def _prepare(widths, n_feat, n_cls, W, bn_bias_shift, B=1, H=64, boxes=12):
-    from bench import build_model, synthetic_batch
+    from bench import synthetic_batch
 
     torch.manual_seed(0)
     backbone, head = build_model(widths, n_cls, n_feat)
@@ -78,7 +116,9 @@ def _prepare(widths, n_feat, n_cls, W, bn_bias_shift, B=1, H=64, boxes=12):
 
 
 @pytest.mark.parametrize("widths,n_feat,n_cls,W,bn_bias_shift", [("rv-av2", 5, 26, 256, 3.0), ("rv-av2", 5, 26, 256, 0.0),
-                                                                 ("rv-waymo", 6, 3, 336, 3.0)])
+                                                                 ("rv-waymo", 6, 3, 336, 3.0),
+                                                                 ("base-av2", 5, 26, 256, 3.0), ("base-av2", 5, 26, 256, 0.0),
+                                                                 ("base-waymo", 6, 3, 336, 3.0)])
 def test_real_width_train_step_vs_oracle(widths, n_feat, n_cls, W, bn_bias_shift):
     _train_step_vs_oracle(widths, n_feat, n_cls, W, bn_bias_shift, small_grids=True)
 
@@ -94,13 +134,14 @@ def _train_step_vs_oracle(widths, n_feat, n_cls, W, bn_bias_shift, small_grids, 
     from oracle import model as om
     from oracle import targets as otgt
     from range_view_3d_detection_amd import engine as E
+    from range_view_3d_detection_amd import engine_bwd
 
     backbone, head, sd, batch = _prepare(widths, n_feat, n_cls, W, bn_bias_shift)
     torch.set_num_threads(min(32, torch.get_num_threads()))
 
     def oracle_run(nm):
         params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.dtype.is_floating_point and "running_" not in k}
-        _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, nm=nm)
+        _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, stem_type=stem_type_of(widths), nm=nm)
         tg = otgt.compute_targets(batch["cart"], batch["annotations"], n_cls)
         loss = otgt.detection_loss(logits, reg, batch["cart"], batch["mask"], tg, n_cls)["loss"]
         loss.backward()
@@ -116,6 +157,9 @@ def _train_step_vs_oracle(widths, n_feat, n_cls, W, bn_bias_shift, small_grids, 
 
     model = Detector(backbone, head).to(DEV).train()
     data = {k: (v.to(DEV) if k != "annotations" else v) for k, v in batch.items()}
+    # the fused tower-final backward (engine_bwd._head_final_sums) is not a profiled launch: its calls are counted through a wrapper
+    fused_final, real_sums = [], engine_bwd._head_final_sums
+    engine_bwd._head_final_sums = lambda *a: (fused_final.append(1), real_sums(*a))[1]
     with _small_grids(small_grids):
         E.PROFILE = E.KernelProfile()
         try:
@@ -126,10 +170,20 @@ def _train_step_vs_oracle(widths, n_feat, n_cls, W, bn_bias_shift, small_grids, 
             ran = set(name for name, *_ in E.PROFILE.records)
         finally:
             E.PROFILE = None
+            engine_bwd._head_final_sums = real_sums
     # ---- the production kernels are what ran ----
-    # (rv-waymo has no 256-channel pointwise conv: its only 256-channel layers are the 3x3 towers, i.e. tapconv5)
-    need = {"tapconv4_kernel<128>", "wgrad3_kernel(+reduce)"} | ({"tapconv4_kernel<256>"} if widths == "rv-av2" else set())
-    assert need <= ran and any(n.startswith(("tapconv5_kernel<", "tapconv6_kernel<")) for n in ran), (need - ran, sorted(ran))
+    if widths.startswith("base-"):
+        # 64-channel layers: tapconv2 (half of its channel tile empty) and the generic kernel, weight gradients on generations 1 / 2;
+        # the 128-channel stages on the LDS-DMA kernels; towers of 128 channels fail the fused tower-final's width rule (a multiple of 256)
+        assert "tapconv2_kernel<2>" in ran and any(n.startswith("tapconv_kernel<") for n in ran), sorted(ran)
+        assert {"wgrad_kernel(+reduce)", "wgrad2_kernel(+reduce)"} & ran, sorted(ran)
+        assert any(n.startswith(("tapconv5_kernel<", "tapconv6_kernel<")) for n in ran), sorted(ran)
+        assert len(fused_final) == 0, len(fused_final)
+    else:
+        # (rv-waymo has no 256-channel pointwise conv: its only 256-channel layers are the 3x3 towers, i.e. tapconv5)
+        need = {"tapconv4_kernel<128>", "wgrad3_kernel(+reduce)"} | ({"tapconv4_kernel<256>"} if widths == "rv-av2" else set())
+        assert need <= ran and any(n.startswith(("tapconv5_kernel<", "tapconv6_kernel<")) for n in ran), (need - ran, sorted(ran))
+        assert len(fused_final) == 2, len(fused_final)  # (both towers: the counter the base-* cases rely on does count)
     if not small_grids:
         assert "tapconv6_kernel<128>" in ran, sorted(ran)
 
@@ -151,7 +205,9 @@ def _train_step_vs_oracle(widths, n_feat, n_cls, W, bn_bias_shift, small_grids, 
     # accumulators, ReLU gates within one bf16 ulp of zero) differ from each other by about as much as each differs from
     # fp32.  Bounds: vs the bf16 emulation max(3e-2, 1.5 x yardstick + 1e-2); vs fp32 1.5 x yardstick + 1e-2.
     _check_forward(m)
-    _check_direction(logits, lg16, lg32, reg, rg16, rg32)
+    # (base-av2 with BatchNorm shifts around zero: the 128-wide regression tower is chaotic enough that the CPU bf16 emulation ITSELF reaches
+    #  a cosine of only 0.9884 on the regressands (HIP 0.9895) -- the absolute floor there is 0.98; the bound relative to the emulation stays)
+    _check_direction(logits, lg16, lg32, reg, rg16, rg32, floor=0.98 if (widths.startswith("base-") and bn_bias_shift == 0.0) else 0.99)
     # loss: 1e-2 relative to the fp32 oracle (and no further from it than 2x the bf16 emulation + 2e-3)
     assert abs(loss - loss32) / abs(loss32) < 1e-2, (loss, loss32, loss16)
     assert abs(loss - loss32) <= 2.0 * abs(loss16 - loss32) + 2e-3 * abs(loss32), (loss, loss32, loss16)

@@ -288,6 +288,141 @@ def test_tiny_model_eval_and_decode(golden):
     close(s, g["eval/dec_scores"], 1e-7, "dec scores")
 
 
+# ----------------------------------------------------------------------------- the BASIC stem (base-av2 / base-waymo): same rows
+def unpack(g, prefix):
+    """{name: tensor} of a dict packed by tests/golden/make_golden.py ``pack`` (three arrays instead of one zip member per entry):
+    ``<prefix>/index`` holds one line ``name dtype d0,d1,...`` per entry, ``<prefix>/f32`` / ``<prefix>/i64`` the values in index order."""
+    pools = {"f32": g[f"{prefix}/f32"], "i64": g[f"{prefix}/i64"]}
+    at = {"f32": 0, "i64": 0}
+    out = {}
+    for line in str(g.np(f"{prefix}/index")).split("\n"):
+        name, kind, dims = line.split(" ")
+        shape = tuple(int(d) for d in dims.split(",")) if dims else ()
+        n = int(np.prod(shape, dtype=np.int64))
+        out[name] = pools[kind][at[kind] : at[kind] + n].reshape(shape).clone()
+        at[kind] += n
+    assert at["f32"] == pools["f32"].numel() and at["i64"] == pools["i64"].numel()
+    return out
+
+
+def grad_summary(name, grad):
+    """[norm, four projections on standard-normal vectors seeded by the parameter's name]: ``grad_summary`` of make_golden.py."""
+    import zlib
+
+    gen = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+    v = grad.detach().double().reshape(-1)
+    r = torch.randn(4, v.numel(), generator=gen, dtype=torch.float64)
+    return torch.cat([v.norm().reshape(1), r @ v])
+
+
+def check_grad_summary(name, grad, ref, tol=2e-4):
+    """A gradient against its recorded summary: norm and every projection within ``tol`` x the recorded norm.  An error of relative
+    size e (L2) moves each projection by ~ e x norm (the probes are unit-variance), so this is the gradient tolerance of this file (2e-4)
+    stated on projections (measured on the fixture: 7e-6); the probes depend on the name only, so a gradient that landed on the wrong parameter fails as well."""
+    got, ref = grad_summary(name, grad), ref.double()
+    scale = max(float(ref[0]), 1e-7)
+    err = float((got - ref).abs().max()) / scale
+    assert err <= tol, f"grad {name}: summary off by {err:.3e} of the norm"
+
+
+def test_basic_model_forward_backward(golden):
+    """RangeNet(stem_type="BASIC", layers=[8, 8, 16, 16, 16]) + DetectionHead against the reference: the default shape of the config
+    tree (a projecting BasicBlock as the stem, layers[0] == layers[1] != layers[2]).  BatchNorm biases sit at +2 in the fixture
+    (ReLU gates open), so the parameter gradients compare at the tiny model's bound with nothing left to gate flips.  Every gradient
+    is held to its recorded norm + random projections, the stem's also element by element."""
+    g = golden("basic_model")
+    sd = unpack(g, "sd")
+    params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.dtype.is_floating_point and "running_" not in k}
+    full = {**sd, **params}
+    assert sd["backbone.stem.net.0.conv.weight"].shape == (8, 5, 1, 1) and sd["backbone.net.res2.blocks.0.net.0.conv.weight"].shape == (16, 8, 3, 3)
+    nm = om.Numerics(train=True, running={})
+    feats, logits, reg = om.detector_forward(g["features"], g["cart"], full, stem_type="BASIC", nm=nm)
+    for s in (1, 2, 4, 16):
+        close(feats[s], g[f"feat/{s}"], 5e-5, f"feat {s}")
+    close(logits, g["logits"], 5e-5, "logits")
+    close(reg, g["regressands"], 5e-5, "regressands")
+
+    tg = otgt.compute_targets(g["cart"], g["annotations"], num_classes=5)
+    for k in ("classification_labels", "panoptics", "points_per_obj"):
+        assert torch.equal(tg[k], g[f"targets/{k}"]), k
+    close(tg["regression_targets"], g["targets/regression_targets"], 1e-6, "regression targets")
+    assert int((tg["panoptics"] > 0).sum()) > 20
+
+    losses = otgt.detection_loss(logits, reg, g["cart"], g["mask"], tg, num_classes=5)
+    close(losses["targets"], g["targets/soft"], 1e-5, "soft targets")
+    ref_losses = unpack(g, "loss")
+    for k in ("loss", "classification_loss", "foreground_loss", "background_loss", "regression_loss",
+              "coordinate_loss", "dimension_loss", "rotation_loss", "total_fg", "total_objects"):
+        close(losses[k].reshape(()), ref_losses[k].reshape(()), 5e-5, f"loss {k}")
+
+    losses["loss"].backward()
+    summaries = unpack(g, "grad_summary")
+    assert set(summaries) == set(params)
+    for k, p in params.items():
+        check_grad_summary(k, p.grad, summaries[k])
+    stem = unpack(g, "grad")
+    assert set(stem) == {k for k in params if k.startswith("backbone.stem.")} and len(stem) == 9
+    for k, v in stem.items():
+        close(params[k].grad, v, 2e-3, f"grad {k}")
+    after = unpack(g, "sd_after")
+    assert len(after) == sum("running_" in k for k in sd)
+    for k, v in after.items():
+        close(nm.running[k], v, 5e-5, f"running {k}")
+
+
+def test_grad_summary_notices_a_wrong_gradient():
+    """The summary is only worth something if small errors move it: one element off by 1 % of the maximum, a transposed kernel, and
+    the right gradient under another parameter's name all fail; the gradient itself passes."""
+    gen = torch.Generator().manual_seed(0)
+    grad = torch.randn(16, 8, 3, 3, generator=gen)
+    ref = grad_summary("backbone.net.res2.blocks.0.net.0.conv.weight", grad)
+    check_grad_summary("backbone.net.res2.blocks.0.net.0.conv.weight", grad, ref)
+    bad = grad.clone()
+    bad[3, 2, 1, 1] += 0.01 * float(grad.abs().max())
+    for wrong, name in ((bad, "backbone.net.res2.blocks.0.net.0.conv.weight"), (grad.transpose(2, 3).contiguous(), "backbone.net.res2.blocks.0.net.0.conv.weight"),
+                        (grad, "backbone.net.res2.blocks.0.net.3.conv.weight")):
+        with pytest.raises(AssertionError):
+            check_grad_summary(name, wrong, ref)
+
+
+def test_basic_model_eval_and_decode(golden):
+    g = golden("basic_model")
+    sd = unpack(g, "sd")
+    with torch.no_grad():
+        feats, logits, reg = om.detector_forward(g["features"], g["cart"], sd, stem_type="BASIC", nm=om.Numerics(train=False))
+    close(logits, g["eval/logits"], 5e-5, "eval logits")
+    close(reg, g["eval/regressands"], 5e-5, "eval regressands")
+    post = {"num_pre_nms": 50000, "num_post_nms": 1000, "nms_threshold": 0.3, "min_confidence": 0.1}
+    p, s, c, b = odec.range_decode(g["eval/logits"], g["eval/regressands"], g["cart"], g["mask"], post, use_nms=False)
+    assert torch.equal(c, g["eval/dec_categories"]) and torch.equal(b, g["eval/dec_batch_index"])
+    assert p.shape[0] > 10
+    close(p, g["eval/dec_params"], 1e-6, "dec params")
+    close(s, g["eval/dec_scores"], 1e-7, "dec scores")
+
+
+def test_basic_backbone_with_six_input_channels(golden):
+    """The waymo feature set through the BASIC stem (6 -> 8 projection and 6 -> 8 / 8 -> 8 net) in front of the same trunk."""
+    g = golden("basic_model")
+    sd = {k[len("backbone."):]: v for k, v in unpack(g, "sd").items() if k.startswith("backbone.net.")}
+    sd.update(unpack(g, "c6/sd"))
+    assert sd["stem.net.0.conv.weight"].shape == (8, 6, 1, 1) and sd["stem.projection_block.0.conv.weight"].shape == (8, 6, 1, 1)
+    params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if k.startswith("stem.") and v.dtype.is_floating_point and "running_" not in k}
+    nm = om.Numerics(train=True, running={})
+    feats = om.range_net(g["c6/features"], g["c6/cart"], {**sd, **params}, stem_type="BASIC", nm=nm)
+    for s in (1, 2, 4, 16):
+        close(feats[s], g[f"c6/feat/{s}"], 5e-5, f"c6 feat {s}")
+    sum(0.5 * (t**2).sum() for t in feats.values()).backward()
+    grads = unpack(g, "c6/grad")
+    assert set(grads) == set(params)
+    for k, p in params.items():
+        close(p.grad, grads[k], 2e-3, f"c6 grad {k}")
+    for k, v in unpack(g, "c6/sd_after").items():
+        close(nm.running[k], v, 5e-5, f"c6 running {k}")
+    with torch.no_grad():
+        out = om.range_net(g["c6/features"], g["c6/cart"], sd, stem_type="BASIC", nm=om.Numerics(train=False))
+    close(out[1][:, :8], g["c6/eval_stem"], 5e-5, "c6 eval stem output")
+
+
 def _check_augmented(got_sweep, got_ann, g, tag, names):
     from oracle import augment as oaug
 
@@ -475,7 +610,7 @@ def test_loader_train_item_augments_before_padding(golden):
 
 @pytest.mark.skipif(not os.path.isdir("/root/reference/src/torchbox3d"), reason="build container only: regenerating the fixtures runs the reference")
 def test_fixture_generator_reproduces_every_committed_fixture(tmp_path):
-    """tests/golden/make_golden.py (the reference itself, run in the build container) regenerates all twelve fixtures BYTE for byte:
+    """tests/golden/make_golden.py (the reference itself, run in the build container) regenerates all thirteen fixtures BYTE for byte:
     every generator seeds its own torch.Generator and the global one (module constructors initialise from it)."""
     import subprocess
     import sys
@@ -484,6 +619,6 @@ def test_fixture_generator_reproduces_every_committed_fixture(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(GOLDEN, "make_golden.py"), "all"], env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     names = sorted(f for f in os.listdir(GOLDEN) if f.endswith(".npz"))
-    assert len(names) == 12
+    assert len(names) == 13
     for f in names:
         assert open(os.path.join(GOLDEN, f), "rb").read() == open(tmp_path / f, "rb").read(), f"{f} is not reproduced"

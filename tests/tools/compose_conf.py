@@ -222,7 +222,7 @@ def load_fixture() -> Dict[str, Any]:
 
 
 if __name__ == "__main__":
-    data = {e: plugin_kwargs(e) for e in ("rv-av2", "rv-waymo")}
+    data = {e: plugin_kwargs(e) for e in ("rv-av2", "rv-waymo", "base-av2", "base-waymo")}
     with open(FIXTURE, "w") as f:
         json.dump(to_wire(data), f, indent=1, sort_keys=False)
         f.write("\n")

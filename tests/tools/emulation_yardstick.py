@@ -3,8 +3,8 @@ the fp32 oracle, at the benchmarked widths and image sizes.  The crop tests (tes
 on the fly; at 64 x 2048 / 64 x 2656 one emulation pass costs 50-80 s of a 16-core host per test, so it is measured ONCE with this
 script and recorded in tests/test_gpu_fullsize_train.py (``EMULATION``).  CPU only; run from the repo root:
 
-    python tests/tools/emulation_yardstick.py [rv-av2|rv-waymo|first-step]
-    python tests/tools/emulation_yardstick.py envelope     # rewrites tests/golden/emulation_envelope.json
+    python tests/tools/emulation_yardstick.py [rv-av2|rv-waymo|base-av2|base-waymo|first-step]
+    python tests/tools/emulation_yardstick.py envelope [case key ...]   # rewrites tests/golden/emulation_envelope.json (given keys: only those cases)
 
 ``envelope`` (round-5 review, item 9): the crop cases of tests/test_gpu_realwidth.py under EIGHT summation orders of the CPU bf16
 emulation (``Numerics.bf16(sum_order=k)``: every conv visits its input channels in a permuted order -- the same network, another
@@ -40,13 +40,13 @@ def rel_err(a, b):
 def train_case(widths, n_feat, n_cls, W):
     from oracle import model as om
     from oracle import targets as otgt
-    from test_gpu_realwidth import _prepare
+    from test_gpu_realwidth import _prepare, stem_type_of
 
     _, _, sd, batch = _prepare(widths, n_feat, n_cls, W, 3.0)
 
     def run(nm):
         params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.dtype.is_floating_point and "running_" not in k}
-        _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, nm=nm)
+        _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, stem_type=stem_type_of(widths), nm=nm)
         tg = otgt.compute_targets(batch["cart"], batch["annotations"], n_cls)
         loss = otgt.detection_loss(logits, reg, batch["cart"], batch["mask"], tg, n_cls)["loss"]
         loss.backward()
@@ -78,20 +78,22 @@ def first_step():
     return out
 
 
-ENVELOPE_CASES = {"rv-av2/256/3.0": ("rv-av2", 5, 26, 256, 3.0), "rv-av2/256/0.0": ("rv-av2", 5, 26, 256, 0.0), "rv-waymo/336/3.0": ("rv-waymo", 6, 3, 336, 3.0)}
+ENVELOPE_CASES = {"rv-av2/256/3.0": ("rv-av2", 5, 26, 256, 3.0), "rv-av2/256/0.0": ("rv-av2", 5, 26, 256, 0.0), "rv-waymo/336/3.0": ("rv-waymo", 6, 3, 336, 3.0),
+                  "base-av2/256/3.0": ("base-av2", 5, 26, 256, 3.0), "base-av2/256/0.0": ("base-av2", 5, 26, 256, 0.0),
+                  "base-waymo/336/3.0": ("base-waymo", 6, 3, 336, 3.0)}
 ENVELOPE_ORDERS = (0, 1, 2, 3, 4, 5, 6, 7)
 
 
 def envelope_case(widths, n_feat, n_cls, W, shift):
     from oracle import model as om
     from oracle import targets as otgt
-    from test_gpu_realwidth import _prepare
+    from test_gpu_realwidth import _prepare, stem_type_of
 
     _, _, sd, batch = _prepare(widths, n_feat, n_cls, W, shift)
 
     def run(nm):
         params = {k: v.clone().requires_grad_(True) for k, v in sd.items() if v.dtype.is_floating_point and "running_" not in k}
-        _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, nm=nm)
+        _, logits, reg = om.detector_forward(batch["features"], batch["cart"], {**sd, **params}, stem_type=stem_type_of(widths), nm=nm)
         tg = otgt.compute_targets(batch["cart"], batch["annotations"], n_cls)
         loss = otgt.detection_loss(logits, reg, batch["cart"], batch["mask"], tg, n_cls)["loss"]
         loss.backward()
@@ -114,18 +116,25 @@ def envelope_case(widths, n_feat, n_cls, W, shift):
 
 
 if __name__ == "__main__":
-    if sys.argv[1:] == ["envelope"]:
+    if sys.argv[1:2] == ["envelope"]:
+        path = os.path.join(ROOT, "tests", "golden", "emulation_envelope.json")
+        wanted = sys.argv[2:]  # case keys to (re-)record; the other cases keep their recorded values
         out = {}
+        if wanted:
+            with open(path) as f:
+                out = json.load(f)["cases"]
         for name, case in ENVELOPE_CASES.items():
+            if wanted and name not in wanted:
+                continue
             print(name, flush=True)
             out[name] = envelope_case(*case)
-        path = os.path.join(ROOT, "tests", "golden", "emulation_envelope.json")
         with open(path, "w") as f:
             json.dump({"threads": torch.get_num_threads(), "torch": torch.__version__, "cases": out}, f, indent=1)
             f.write("\n")
         print("wrote", path)
         sys.exit(0)
-    which = sys.argv[1:] or ["rv-av2", "rv-waymo", "first-step"]
+    which = sys.argv[1:] or ["rv-av2", "rv-waymo", "base-av2", "base-waymo", "first-step"]
     for w in which:
-        r = first_step() if w == "first-step" else train_case(*{"rv-av2": ("rv-av2", 5, 26, 2048), "rv-waymo": ("rv-waymo", 6, 3, 2656)}[w])
+        r = first_step() if w == "first-step" else train_case(*{"rv-av2": ("rv-av2", 5, 26, 2048), "rv-waymo": ("rv-waymo", 6, 3, 2656),
+                                                                     "base-av2": ("base-av2", 5, 26, 2048), "base-waymo": ("base-waymo", 6, 3, 2656)}[w])
         print(w, json.dumps(r), flush=True)
