@@ -323,7 +323,10 @@ def test_engine_reaches_the_generic_kernel_without_folding(monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------------------------- weight gradients
-def _wgrad(geom, N, H, Wu, u, v, expect, flags=0, scale=None, shift=None, v_affine=0, torch_layout=True):
+def _wgrad(geom, N, H, Wu, u, v, expect, flags=0, scale=None, shift=None, v_affine=0, torch_layout=True, ld_v=None, nan_workspace=False):
+    """One ``rv_tap_wgrad`` launch through the C ABI.  ``u`` / ``v``: ``engine.Act`` (possibly channel slices of wider buffers); ``ld_v``: pixel
+    stride of V when it is not ``v.ld`` (the folded view of a strided layer); ``nan_workspace``: the split-K slabs start as NaN instead of
+    whatever the allocator hands out, so a slab region that no workgroup writes shows in the result."""
     from range_view_3d_detection_amd import _lib as L
     from range_view_3d_detection_amd import engine as E
 
@@ -331,11 +334,15 @@ def _wgrad(geom, N, H, Wu, u, v, expect, flags=0, scale=None, shift=None, v_affi
     info = (ctypes.c_int32 * 4)()
     L.call("rv_tap_wgrad_info", ctypes.byref(geom), ctypes.byref(shape), info)
     assert info[0] == expect, list(info)
-    ws = torch.empty(L.load().rv_tap_wgrad_workspace_bytes(ctypes.byref(geom), ctypes.byref(shape)), dtype=torch.uint8, device=DEV)
+    ws_bytes = L.load().rv_tap_wgrad_workspace_bytes(ctypes.byref(geom), ctypes.byref(shape))
+    if nan_workspace:
+        ws = torch.full((ws_bytes // 4,), float("nan"), dtype=torch.float32, device=DEV)
+    else:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
     cu, cv, taps = geom.cu, geom.cv, geom.kh * geom.kw
     out = torch.full((cu, cv, geom.kh, geom.kw) if torch_layout else (taps, E.pad32(cu), E.pad32(cv)), float("nan"), dtype=torch.float32, device=DEV)
-    L.call("rv_tap_wgrad", ctypes.byref(geom), ctypes.byref(shape), u.ptr(), L.i32(u.ld), v.ptr(), L.i32(v.ld), L.ptr(scale), L.ptr(shift),
-           L.i32(v_affine), L.ptr(out), L.ptr(ws), L.stream_ptr())
+    L.call("rv_tap_wgrad", ctypes.byref(geom), ctypes.byref(shape), u.ptr(), L.i32(u.ld), v.ptr(), L.i32(v.ld if ld_v is None else ld_v), L.ptr(scale),
+           L.ptr(shift), L.i32(v_affine), L.ptr(out), L.ptr(ws), L.stream_ptr())
     torch.cuda.synchronize()
     out = out.cpu()
     if not torch_layout:  # packed [tap][cu_pad][cv_pad]: padding entries are zero, the rest is the torch layout transposed

@@ -419,6 +419,38 @@ def _gfx950_code_objects(path):
     return out
 
 
+def _kernel_metadata(co_path, name):
+    """The scalar fields (``.vgpr_count``, ``.vgpr_spill_count``, ``.private_segment_fixed_size`` ...) of the one kernel whose mangled name
+    contains ``name``, from the AMDGPU metadata note of a code object file."""
+    import re
+
+    readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
+    if not os.path.exists(readelf):
+        pytest.skip("no llvm-readelf")
+    text = subprocess.run([readelf, "--notes", str(co_path)], check=True, capture_output=True, text=True).stdout
+    kernels = []
+    for ln in text.splitlines():
+        if ln.startswith("  - ."):  # a new entry of amdhsa.kernels (the entries of .args sit deeper)
+            kernels.append({})
+        m = re.match(r"(?:  - |    )\.(\w+):\s+(\S.*)$", ln)
+        if m and kernels:
+            kernels[-1][m.group(1)] = m.group(2).strip()
+    found = [k for k in kernels if name in k.get("name", "")]
+    assert len(found) == 1, [k.get("name") for k in kernels]
+    return found[0]
+
+
+def _assert_no_spills(co_path, name):
+    """Register spills are ``scratch_load`` / ``scratch_store``: they count in ``vmcnt`` like every other vector-memory instruction, so a
+    kernel that waits with a COUNTED ``vmcnt`` is only right while it has none."""
+    md = _kernel_metadata(co_path, name)
+    assert int(md["vgpr_spill_count"]) == 0 and int(md["private_segment_fixed_size"]) == 0, md
+
+
+# every vector-memory instruction that counts in vmcnt (scratch_: spills; flat_: what a global access becomes when the address space is lost)
+VMEM = ("global_", "buffer_", "scratch_", "flat_")
+
+
 @pytest.mark.parametrize("tag", ["bf16", "f16"])
 def test_wgrad3_epilogue_waits_before_it_touches_a_register(tmp_path, lib, tag):
     """Round 6's rv-waymo fault: wgrad3's transposing LDS reads are inline asm, the last one of the K loop is a prefetch nobody consumes, and the
@@ -444,8 +476,11 @@ def test_wgrad3_epilogue_waits_before_it_touches_a_register(tmp_path, lib, tag):
     for i in waits:
         assert body[i - 1].startswith(("s_cbranch", "s_branch")), body[i - 6:i + 1]
         # ... and the first vector instruction behind the wait is arithmetic on registers nobody is still loading into
-        nxt = next(ln for ln in body[i + 1:] if ln.startswith(("v_", "global_", "ds_")))
+        nxt = next(ln for ln in body[i + 1:] if ln.startswith(("v_", "ds_") + VMEM))
         assert nxt.startswith("v_"), nxt
+    # the K loop's waits are counted (vmcnt(8) / vmcnt(10) = the DMA instructions of two chunks): nothing else may be in that count
+    assert not [ln for ln in body if ln.startswith(("scratch_", "flat_"))]
+    _assert_no_spills(co, "wgrad3_kernel")
 
 
 def _kernel_body(text, name):
@@ -473,5 +508,6 @@ def test_pointwise_kernel_counts_its_wait_over_the_order_it_was_written_in(tmp_p
     body = _kernel_body(text, "pointwise_kernel")
     waits = [i for i, ln in enumerate(body) if ln.startswith("s_waitcnt vmcnt(8)")]
     assert len(waits) == 1, waits
-    mem = [ln.split()[0] for ln in body[:waits[0]] if ln.startswith(("global_load_lds", "global_store", "global_load", "buffer_"))]
+    mem = [ln.split()[0] for ln in body[:waits[0]] if ln.startswith(VMEM)]
     assert mem[-16:] == ["global_load_lds_dwordx4"] * 8 + ["global_store_dwordx4"] * 8, mem[-20:]
+    _assert_no_spills(co, "pointwise_kernelILi256E")
