@@ -614,6 +614,83 @@ int rv_detection_loss_backward(const float* logits, int32_t ld_logits, const flo
                                int32_t azimuth_invariant, const double* sums, float grad_scale, float* d_logits,
                                float* d_regressands, rvStream stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Several FPN levels x several tasks (nn/heads/detection_head.py:138-196 forward, :496-665 compute_targets, :202-449 loss +
+ * reduce_multiscale_loss).  An ENTRY is one (level, task) pair; entries are ordered level-major (stride-major), tasks in the order of
+ * tasks_cfg -- the order of the reference's `losses_list`.  At most RV_ML_MAX_LEVELS levels and RV_ML_MAX_ENTRIES entries.
+ * The one-level entry points above keep their signatures and results.
+ * ------------------------------------------------------------------------------------- */
+#define RV_ML_MAX_LEVELS 8
+#define RV_ML_MAX_ENTRIES 16
+/* length of one row of loss sums (the layout rv_detection_loss_forward documents) */
+#define RV_LOSS_SUMS_LEN 24
+int32_t rv_detection_loss_sums_len(void);
+
+typedef struct {
+    int32_t stride;    /* the level sees the columns ::stride of the sweep (rows are never strided); W % stride == 0 */
+    int32_t use_range; /* fpn_assignment_method == "RANGE" (:568-582): an annotation belongs to the level iff lower < ||centre xyz|| <= upper (fp64) */
+    double lower, upper;
+} rvTargetLevel;
+
+typedef struct { /* outputs of one entry at the level's resolution Ws = W / stride, every element written */
+    int64_t* labels;         /* (B,H,Ws), background = the task's class count */
+    int64_t* panoptics;      /* (B,H,Ws), 0 = background, else 1 + rank within (sweep, level, task) */
+    float* reg_targets;      /* (B,8,H,Ws), encoded against the strided cart */
+    int64_t* points_per_obj; /* (B,H,Ws), the owner's interior-point count AT THE LEVEL'S RESOLUTION */
+} rvTargetOut;
+
+/* compute_targets (:496-665) for every level and task in one sequence of launches, no host round trip.  cuboids / box_offsets / cart
+ * as rv_assign_targets (full resolution).  The slab tests run ONCE per (full-resolution pixel, box): a hit is added to the counter
+ * of every level whose stride divides the pixel's column.  Boxes are ranked per (sweep, level, task) by that STRIDED count (stable,
+ * ascending) over the boxes that pass the level's range filter and carry the task's id in the task column (the reference splits by
+ * unique(return_counts), i.e. assumes rows sorted by task within a sweep; for such rows the two agree); boxes without a pixel at
+ * the level still consume a rank.  task_ids[t] is the value of the task column of task t, task_classes[t] its class count (the
+ * background label).  scratch: (3 * n_levels * max(m,1)) i32.  num_objects: (n_levels * n_tasks) i32, entry order, = boxes owning
+ * >= 1 pixel of that entry (== the distinct panoptic ids per sweep summed over sweeps, :379-390).  host_* tables are read at call time. */
+int rv_assign_targets_multilevel(const double* cuboids, int32_t m, const int32_t* box_offsets, const float* cart, int32_t B,
+                                 int32_t H, int32_t W, int32_t n_levels, const rvTargetLevel* host_levels, int32_t n_tasks,
+                                 const int32_t* host_task_ids, const int32_t* host_task_classes, int32_t azimuth_invariant,
+                                 int32_t* scratch, const rvTargetOut* host_outs, int32_t* num_objects, rvStream stream);
+
+typedef struct { /* one (level, task) of the loss: the tensors rv_detection_loss_forward / _backward take, at the level's resolution */
+    const float* logits;
+    const float* regressands;
+    const float* cart;
+    const uint8_t* mask;
+    const int64_t* labels;
+    const int64_t* panoptics;
+    const float* reg_targets;
+    const int64_t* points_per_obj;
+    const int32_t* num_objects; /* (1) i32 of this entry */
+    float* soft_targets;        /* forward, optional */
+    float* foreground;          /* forward, optional */
+    float* d_logits;            /* backward */
+    float* d_regressands;       /* backward */
+    int32_t ld_logits, ld_reg, B, n_cls, H, W;
+} rvLossEntry;
+
+typedef struct {
+    float coding_weights[8];
+    float cls_weight, reg_weight, smoothing, sigma, alpha, gamma;
+    int32_t azimuth_invariant;
+} rvLossParams;
+
+/* DetectionHead.loss + reduce_multiscale_loss (:202-449) over n_entries (level, task) pairs in two phases.
+ * sums: (n_entries + 1) rows of RV_LOSS_SUMS_LEN f64 (device).
+ * phase one, ONE launch over the entry table (passed by value as a kernel argument: nothing is copied to the device): row e [0..11] as
+ *   rv_detection_loss_forward, soft targets and foreground map of every entry;
+ * phase two, one small kernel: total_fg = sum_e row e [3] + smoothing and total_objects = max(sum_e num_objects_e, 1) (:379-401); then
+ *   per row e [12] = total_objects, [13] = total_fg, [15] = 1, [16..23] the entry's scalars normalised by the two GLOBAL numbers;
+ *   row n_entries = each of [16..23] summed over the entries ([16] is the loss), [12] / [13] = n_entries x the global numbers (the
+ *   reference sums its collated list, :438-439), [15] = 1 (the backward pass's device-side factor, as sums[15] above).
+ * backward, ONE launch: gradients of row n_entries [16] for every entry, scaled by grad_scale * sums[n_entries][15]; reads the
+ *   normalisers from the rows on the device.  With one entry every tensor and row 0 equal the one-level entry points' results
+ *   (the atomically accumulated [0..11] up to the order of the workgroups' additions). */
+int rv_detection_loss_multilevel_forward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                         double* sums, rvStream stream);
+int rv_detection_loss_multilevel_backward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                          const double* sums, float grad_scale, rvStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -68,6 +68,41 @@ class BnbEpilogue(ctypes.Structure):
                 ("mean", ctypes.c_void_p), ("invstd", ctypes.c_void_p), ("partial", ctypes.c_void_p)]
 
 
+class TargetLevel(ctypes.Structure):
+    """``rvTargetLevel`` of include/rv3d.h (rv_assign_targets_multilevel)."""
+
+    _fields_ = [("stride", ctypes.c_int32), ("use_range", ctypes.c_int32), ("lower", ctypes.c_double), ("upper", ctypes.c_double)]
+
+
+class TargetOut(ctypes.Structure):
+    """``rvTargetOut``: the four target tensors of one (level, task)."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("labels", "panoptics", "reg_targets", "points_per_obj")]
+
+
+class LossEntry(ctypes.Structure):
+    """``rvLossEntry``: the tensors of one (level, task) of the multi-level loss."""
+
+    _fields_ = [(n, ctypes.c_void_p) for n in ("logits", "regressands", "cart", "mask", "labels", "panoptics", "reg_targets", "points_per_obj",
+                                               "num_objects", "soft_targets", "foreground", "d_logits", "d_regressands")] + \
+               [(n, ctypes.c_int32) for n in ("ld_logits", "ld_reg", "B", "n_cls", "H", "W")]
+
+
+class LossParams(ctypes.Structure):
+    """``rvLossParams``."""
+
+    _fields_ = [("coding_weights", ctypes.c_float * 8)] + [(n, ctypes.c_float) for n in ("cls_weight", "reg_weight", "smoothing", "sigma", "alpha", "gamma")] + \
+               [("azimuth_invariant", ctypes.c_int32)]
+
+
+ML_MAX_LEVELS, ML_MAX_ENTRIES = 8, 16  # RV_ML_MAX_LEVELS / RV_ML_MAX_ENTRIES
+
+
+def loss_sums_len() -> int:
+    """Length of one row of loss sums (``RV_LOSS_SUMS_LEN``), asked of the library."""
+    return int(load().rv_detection_loss_sums_len())
+
+
 class RvError(RuntimeError):
     pass
 

@@ -11,6 +11,8 @@
 //   sums[3] = number of foreground pixels       sums[4..11] = sum of the un-normalised regression terms
 //   sums[12] = max(total_objects, 1)            sums[13] = sums[3] + smoothing (total_fg)
 // loss = sums[0]/sums[13] + (sums[4]+..+sums[11])/sums[12]   (assembled by the host wrapper, on device).
+// Several (level, task) entries: one row of RV_LOSS_SUMS_LEN sums per entry, filled by ONE launch over an entry table, then
+// loss_table_finish_kernel normalises every row by the foreground / object counts of ALL rows (reduce_multiscale_loss, :379-449).
 #include "common.h"
 
 namespace {
@@ -54,16 +56,15 @@ __device__ __forceinline__ void decode_centre(const float* r, float px, float py
 
 __device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
+// The work of workgroup `block` of `n_blocks` on one (level, task): shared by the one-level kernel and the entry-table kernel, which
+// differ only in where a workgroup finds its tensors.  total_fg / total_obj / gscale are read by the caller (BACKWARD only).
 template <bool BACKWARD>
-__global__ __launch_bounds__(256) void loss_kernel(const LossArgs a) {
+__device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int64_t n_blocks, double total_fg, double total_obj, float gscale) {
     const int64_t hw = (int64_t)a.H * a.W, total = (int64_t)a.B * hw;
     double acc[12];
 #pragma unroll
     for (int j = 0; j < 12; ++j) acc[j] = 0.0;
-    const double total_fg = BACKWARD ? a.sums[13] : 1.0;
-    const double total_obj = BACKWARD ? a.sums[12] : 1.0;
-    const float gscale = BACKWARD ? a.grad_scale * (float)a.sums[15] : 1.f;  // host factor x device factor (sums[15]: 1 unless the caller wrote the incoming gradient there)
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    for (int64_t i = block * (int64_t)blockDim.x + threadIdx.x; i < total; i += n_blocks * blockDim.x) {
         const int64_t b = i / hw, pix = i - b * hw;
         const float m = a.mask[i] ? 1.f : 0.f;
         const float* cart = a.cart + b * 3 * hw;
@@ -194,6 +195,113 @@ __global__ __launch_bounds__(256) void loss_kernel(const LossArgs a) {
     }
 }
 
+template <bool BACKWARD>
+__global__ __launch_bounds__(256) void loss_kernel(const LossArgs a) {
+    const double total_fg = BACKWARD ? a.sums[13] : 1.0;
+    const double total_obj = BACKWARD ? a.sums[12] : 1.0;
+    const float gscale = BACKWARD ? a.grad_scale * (float)a.sums[15] : 1.f;  // host factor x device factor (sums[15]: 1 unless the caller wrote the incoming gradient there)
+    loss_tile<BACKWARD>(a, blockIdx.x, gridDim.x, total_fg, total_obj, gscale);
+}
+
+// ---- several (level, task) entries in ONE launch: the table travels by value as the kernel argument (<= 16 entries, ~2.3 KB: nothing
+// to copy to the device and nothing to keep alive); a workgroup finds its entry by the prefix sums of the entries' workgroup counts ----
+struct LossTable {
+    int n;
+    int block_begin[RV_ML_MAX_ENTRIES + 1];
+    rvLossEntry e[RV_ML_MAX_ENTRIES];
+    rvLossParams p;
+    double* sums;  // (n + 1) rows of RV_LOSS_SUMS_LEN
+    float grad_scale;
+};
+
+template <bool BACKWARD>
+__global__ __launch_bounds__(256) void loss_table_kernel(const LossTable t) {
+    int k = 0;
+    while (k + 1 < t.n && (int)blockIdx.x >= t.block_begin[k + 1]) ++k;  // (wave-uniform: scalar loads)
+    const rvLossEntry& e = t.e[k];
+    LossArgs a;
+    a.logits = e.logits;
+    a.reg = e.regressands;
+    a.cart = e.cart;
+    a.mask = e.mask;
+    a.labels = e.labels;
+    a.panoptics = e.panoptics;
+    a.reg_targets = e.reg_targets;
+    a.ppo = e.points_per_obj;
+    a.num_objects = e.num_objects;
+    a.B = e.B;
+    a.n_cls = e.n_cls;
+    a.H = e.H;
+    a.W = e.W;
+    a.ld_logits = e.ld_logits;
+    a.ld_reg = e.ld_reg;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a.coding[j] = t.p.coding_weights[j];
+    a.cls_w = t.p.cls_weight;
+    a.reg_w = t.p.reg_weight;
+    a.smoothing = t.p.smoothing;
+    a.sigma = t.p.sigma;
+    a.alpha = t.p.alpha;
+    a.gamma = t.p.gamma;
+    a.az_inv = t.p.azimuth_invariant;
+    a.sums = t.sums + (int64_t)k * RV_LOSS_SUMS_LEN;
+    a.soft = e.soft_targets;
+    a.fg = e.foreground;
+    a.d_logits = e.d_logits;
+    a.d_reg = e.d_regressands;
+    a.grad_scale = t.grad_scale;
+    // every level is normalised by the two GLOBAL numbers phase two left in its row; the incoming gradient sits in the totals row
+    const double total_fg = BACKWARD ? a.sums[13] : 1.0;
+    const double total_obj = BACKWARD ? a.sums[12] : 1.0;
+    const float gscale = BACKWARD ? t.grad_scale * (float)t.sums[(int64_t)t.n * RV_LOSS_SUMS_LEN + 15] : 1.f;
+    loss_tile<BACKWARD>(a, (int)blockIdx.x - t.block_begin[k], t.block_begin[k + 1] - t.block_begin[k], total_fg, total_obj, gscale);
+}
+
+// phase two (reduce_multiscale_loss, detection_head.py:379-449): the global normalisers, every entry's scalars, and their sums over
+// the entry list.  One wave; lane e owns entry e (n <= 16), the totals go through wave shuffles.
+__global__ __launch_bounds__(64) void loss_table_finish_kernel(const LossTable t) {
+    const int e = threadIdx.x;
+    const bool on = e < t.n;
+    double* s = t.sums + (int64_t)(on ? e : 0) * RV_LOSS_SUMS_LEN;
+    const double n_fg = wave_sum_d(on ? s[3] : 0.0);
+    const double n_obj = wave_sum_d(on ? (double)*t.e[on ? e : 0].num_objects : 0.0);
+    const double obj = n_obj < 1.0 ? 1.0 : n_obj, fg = n_fg + (double)t.p.smoothing;
+    double v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = 0.0;
+    if (on) {
+        const double coord = (s[4] + s[5] + s[6]) / obj, dim = (s[7] + s[8] + s[9]) / obj, rot = (s[10] + s[11]) / obj;
+        const double cls = s[0] / fg, reg = (((((((s[4] + s[5]) + s[6]) + s[7]) + s[8]) + s[9]) + s[10]) + s[11]) / obj;
+        v[0] = cls + reg;
+        v[1] = cls;
+        v[2] = s[1] / fg;
+        v[3] = s[2] / fg;
+        v[4] = coord;
+        v[5] = dim;
+        v[6] = rot;
+        v[7] = coord + dim + rot;
+        s[12] = obj;
+        s[13] = fg;
+        s[14] = 0.0;
+        s[15] = 1.0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[16 + j] = v[j];
+    }
+    double* tot = t.sums + (int64_t)t.n * RV_LOSS_SUMS_LEN;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const double w = wave_sum_d(v[j]);
+        if (e == 0) tot[16 + j] = w;
+    }
+    if (e == 0) {
+        for (int j = 0; j < 12; ++j) tot[j] = 0.0;
+        tot[12] = (double)t.n * obj;  // (the reference sums its collated list: n_entries x the value)
+        tot[13] = (double)t.n * fg;
+        tot[14] = 0.0;
+        tot[15] = 1.0;
+    }
+}
+
 __global__ void loss_finish_kernel(double* sums, const int32_t* num_objects, float smoothing) {
     const double n = (double)*num_objects;
     const double obj = n < 1.0 ? 1.0 : n, fg = sums[3] + (double)smoothing;
@@ -272,7 +380,7 @@ extern "C" int rv_detection_loss_forward(const float* logits, int32_t ld_logits,
     a.soft = soft_targets;
     a.fg = foreground;
     hipStream_t st = (hipStream_t)stream;
-    hipError_t e = hipMemsetAsync(sums, 0, 24 * sizeof(double), st);
+    hipError_t e = hipMemsetAsync(sums, 0, RV_LOSS_SUMS_LEN * sizeof(double), st);
     if (e != hipSuccess) RV_FAIL("rv_detection_loss_forward: %s", hipGetErrorString(e));
     const int fwd_grid = grid_for((int64_t)B * H * W) < 512 ? grid_for((int64_t)B * H * W) : 512;  // (grid-stride: fewer, longer workgroups -> fewer atomics)
     hipLaunchKernelGGL(loss_kernel<false>, dim3(fwd_grid), dim3(256), 0, st, a);
@@ -300,5 +408,59 @@ extern "C" int rv_detection_loss_backward(const float* logits, int32_t ld_logits
     a.grad_scale = grad_scale;
     hipLaunchKernelGGL(loss_kernel<true>, dim3(grid_for((int64_t)B * H * W)), dim3(256), 0, (hipStream_t)stream, a);
     RV_CHECK_LAUNCH("loss backward kernel");
+    return 0;
+}
+
+extern "C" int32_t rv_detection_loss_sums_len(void) { return RV_LOSS_SUMS_LEN; }
+
+namespace {
+
+int fill_table(LossTable* t, const rvLossEntry* entries, int32_t n, const rvLossParams* p, double* sums, bool backward) {
+    RV_REQUIRE(entries && p && sums, "rv_detection_loss_multilevel: null argument");
+    RV_REQUIRE(n >= 1 && n <= RV_ML_MAX_ENTRIES, "rv_detection_loss_multilevel: %d entries (1 .. %d)", n, RV_ML_MAX_ENTRIES);
+    memset(t, 0, sizeof(*t));
+    t->n = n;
+    t->p = *p;
+    t->sums = sums;
+    t->grad_scale = 1.f;
+    for (int k = 0; k < n; ++k) {
+        const rvLossEntry& e = entries[k];
+        RV_REQUIRE(e.logits && e.regressands && e.cart && e.mask && e.labels && e.panoptics && e.reg_targets && e.points_per_obj && e.num_objects,
+                   "rv_detection_loss_multilevel: null tensor in entry %d", k);
+        RV_REQUIRE(e.B > 0 && e.H > 0 && e.W > 0 && e.n_cls > 0, "rv_detection_loss_multilevel: bad shape in entry %d", k);
+        RV_REQUIRE(e.ld_logits >= e.n_cls && e.ld_reg >= 8 && e.ld_reg % 4 == 0,
+                   "rv_detection_loss_multilevel: bad strides in entry %d (rows of regressands must be 16-byte aligned)", k);
+        RV_REQUIRE(!backward || (e.d_logits && e.d_regressands), "rv_detection_loss_multilevel_backward: null gradient buffers in entry %d", k);
+        t->e[k] = e;
+        const int64_t work = (int64_t)e.B * e.H * e.W;
+        // the one-level entry points' grids, entry by entry (forward: grid-stride with at most 512 workgroups -> fewer atomics)
+        const int blocks = backward ? grid_for(work) : (grid_for(work) < 512 ? grid_for(work) : 512);
+        t->block_begin[k + 1] = t->block_begin[k] + blocks;
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rv_detection_loss_multilevel_forward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                                    double* sums, rvStream stream) {
+    LossTable t;
+    if (fill_table(&t, host_entries, n_entries, host_params, sums, false)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(sums, 0, (size_t)(n_entries + 1) * RV_LOSS_SUMS_LEN * sizeof(double), st);
+    if (e != hipSuccess) RV_FAIL("rv_detection_loss_multilevel_forward: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(loss_table_kernel<false>, dim3(t.block_begin[n_entries]), dim3(256), 0, st, t);
+    hipLaunchKernelGGL(loss_table_finish_kernel, dim3(1), dim3(64), 0, st, t);
+    RV_CHECK_LAUNCH("multi-level loss forward kernels");
+    return 0;
+}
+
+extern "C" int rv_detection_loss_multilevel_backward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                                     const double* sums, float grad_scale, rvStream stream) {
+    LossTable t;
+    if (fill_table(&t, host_entries, n_entries, host_params, (double*)sums, true)) return 1;
+    t.grad_scale = grad_scale;
+    hipLaunchKernelGGL(loss_table_kernel<true>, dim3(t.block_begin[n_entries]), dim3(256), 0, (hipStream_t)stream, t);
+    RV_CHECK_LAUNCH("multi-level loss backward kernel");
     return 0;
 }

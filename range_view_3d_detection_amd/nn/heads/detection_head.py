@@ -9,6 +9,12 @@ What runs where: the towers are fused HIP tap-conv programs; target assignment
 (``compute_targets`` :496-665) and the soft-target / varifocal / L1 loss (:202-449,
 ``math/ops/assignment.py:76-161``) are device kernels without host synchronisation (the
 reference loops over sweeps, tasks and instances in Python with ``.unique()/.tolist()``).
+
+Any list of FPN strides and any number of tasks: one level of stride 1 with one task (the shipped rv-* / base-* recipes) runs the
+one-level entry points (``rv_assign_targets``, ``rv_detection_loss_*``); every other layout, and ``fpn_assignment_method: RANGE``,
+runs the multi-level ones (``rv_assign_targets_multilevel``, ``rv_detection_loss_multilevel_*``), which assign all levels and tasks
+in one sequence of launches and normalise every level by the foreground / object counts summed over all of them.
+``fpn_assignment_method: POINTS`` raises: the reference overwrites its configured intervals with constants (``:583``).
 """
 
 from __future__ import annotations
@@ -54,20 +60,29 @@ def annotations_to_cuboids(annotations: Any) -> np.ndarray:
     return np.concatenate([arr[:, :6], yaw[:, None], arr[:, 10:]], axis=1)
 
 
-def compute_targets(x: Dict[str, Any], tasks_config: Mapping, fpn_strides: Sequence[int], targets_config: Any) -> Dict[int, Dict[int, Dict[str, Tensor]]]:
-    """Dense targets per stride / task (``detection_head.py:496-665``), one stride-1 level and one task on device."""
-    cart = x["cart"]
-    _require_cuda(cart, "cart")
-    strides, tasks = [int(s) for s in fpn_strides], list(tasks_config.keys())
-    if strides != [1] or len(tasks) != 1:
-        raise NotImplementedError("the HIP target kernels cover the one-stride (1) / one-task layout of the rv-* configs")
-    if _cfg_get(targets_config, "fpn_assignment_method") is not None:
-        raise NotImplementedError("fpn_assignment_method must be null (conf/model/range_view.yaml:124)")
-    t_id = tasks[0]
-    n_cls = len(tasks_config[t_id])
-    az_inv = bool(_cfg_get(targets_config, "enable_azimuth_invariant_targets", True))
-    B, _, H, W = cart.shape
-    dev = cart.device
+def _partition(targets_config: Any, stride: Any) -> Tuple[float, float]:
+    parts = _cfg_get(targets_config, "range_partitions")
+    for key in (stride, int(stride), str(stride)):
+        try:
+            lower, upper = parts[key]
+            return float(lower), float(upper)
+        except (KeyError, TypeError, IndexError):
+            continue
+    raise KeyError(f"targets_config.range_partitions has no entry for stride {stride}")
+
+
+def _assignment_method(targets_config: Any) -> Optional[str]:
+    method = _cfg_get(targets_config, "fpn_assignment_method")
+    if method is None or method == "RANGE":
+        return method
+    if method == "POINTS":
+        raise NotImplementedError("fpn_assignment_method POINTS: the reference overwrites the configured point_intervals with "
+                                  "constants (detection_head.py:583), so the configuration does not say what it computes")
+    raise ValueError(f"unknown fpn_assignment_method {method!r}")
+
+
+def _stage_annotations(x: Dict[str, Any], B: int, dev: torch.device):
+    """Annotation table grouped by sweep -> (cuboids (m,10) f64, CSR offsets (B+1) i32) on the device through ONE pinned staging buffer."""
     cub = annotations_to_cuboids(x["annotations"])
     order = np.argsort(cub[:, -1], kind="stable") if cub.shape[0] else np.zeros(0, dtype=np.int64)
     cub = cub[order]
@@ -80,10 +95,33 @@ def compute_targets(x: Dict[str, Any], tasks_config: Mapping, fpn_strides: Seque
     stage[: 10 * m].view(m, 10).copy_(torch.from_numpy(np.ascontiguousarray(cub)))
     stage[10 * max(m, 1) :].view(torch.int32)[: B + 1].copy_(torch.from_numpy(offsets))
     stage_d = stage.to(dev, non_blocking=True)
-    cub_d = stage_d[: 10 * m].view(m, 10)
-    off_d = stage_d[10 * max(m, 1) :].view(torch.int32)[: B + 1]
-    scratch = torch.empty((3, max(m, 1)), dtype=torch.int32, device=dev)
+    return stage_d[: 10 * m].view(m, 10), stage_d[10 * max(m, 1) :].view(torch.int32)[: B + 1], m
+
+
+def compute_targets(x: Dict[str, Any], tasks_config: Mapping, fpn_strides: Sequence[int], targets_config: Any) -> Dict[int, Dict[int, Dict[str, Tensor]]]:
+    """Dense targets per stride / task (``detection_head.py:496-665``) on the device, for any list of strides and tasks.
+
+    Level ``s`` sees the columns ``::s`` of the sweep; with ``fpn_assignment_method == "RANGE"`` an annotation belongs to it iff
+    ``lower < ||centre|| <= upper`` of ``range_partitions[s]``.  Boxes are ranked per (sweep, level, task) by their interior-point
+    count at the level's resolution.  An annotation belongs to a task by its ``task_id`` column: the reference splits a sweep's rows by
+    ``unique(return_counts=True)`` of that column, which is the same thing only for rows sorted by task within a sweep (the loader
+    sorts them so); the fixtures feed rows sorted by (sweep, task).  One level of stride 1, one task, no RANGE filter: the one-level
+    kernels, which ignore the task column as they always did.
+    """
+    cart = x["cart"]
+    _require_cuda(cart, "cart")
+    strides, tasks = [int(s) for s in fpn_strides], list(tasks_config.keys())
+    method = _assignment_method(targets_config)
+    az_inv = bool(_cfg_get(targets_config, "enable_azimuth_invariant_targets", True))
+    B, _, H, W = cart.shape
+    dev = cart.device
+    cub_d, off_d, m = _stage_annotations(x, B, dev)
     cart32 = cart.detach().float().contiguous()
+    if strides != [1] or len(tasks) != 1 or method is not None:
+        return _compute_targets_multilevel(cart32, cub_d, off_d, m, tasks_config, strides, tasks, targets_config, method, az_inv)
+    t_id = tasks[0]
+    n_cls = len(tasks_config[t_id])
+    scratch = torch.empty((3, max(m, 1)), dtype=torch.int32, device=dev)
     labels = torch.empty((B, H, W), dtype=torch.int64, device=dev)
     pan = torch.empty((B, 1, H, W), dtype=torch.int64, device=dev)
     reg = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
@@ -94,6 +132,44 @@ def compute_targets(x: Dict[str, Any], tasks_config: Mapping, fpn_strides: Seque
            L.ptr(pan), L.ptr(reg), L.ptr(ppo), L.ptr(nobj), L.stream_ptr())
     return {1: {t_id: {"points_per_obj": ppo, "panoptics": pan, "classification_labels": labels, "regression_targets": reg,
                        "num_objects": nobj, "num_category": torch.ones((B, n_cls, 1, 1), device=dev)}}}
+
+
+def _compute_targets_multilevel(cart32: Tensor, cub_d: Tensor, off_d: Tensor, m: int, tasks_config: Mapping, strides: Sequence[int],
+                                tasks: Sequence[Any], targets_config: Any, method: Optional[str], az_inv: bool):
+    """Every level and task through ``rv_assign_targets_multilevel``: the slab tests once per (full-resolution pixel, box)."""
+    B, _, H, W = cart32.shape
+    dev = cart32.device
+    n_l, n_t = len(strides), len(tasks)
+    if n_l > L.ML_MAX_LEVELS or n_l * n_t > L.ML_MAX_ENTRIES:
+        raise NotImplementedError(f"{n_l} levels x {n_t} tasks: the kernels take at most {L.ML_MAX_LEVELS} levels and {L.ML_MAX_ENTRIES} (level, task) pairs")
+    levels = (L.TargetLevel * n_l)()
+    for i, s in enumerate(strides):
+        if W % s:
+            raise ValueError(f"stride {s} does not divide the sweep width {W}")
+        lower, upper = _partition(targets_config, s) if method == "RANGE" else (0.0, float("inf"))
+        levels[i] = L.TargetLevel(s, 1 if method == "RANGE" else 0, lower, upper)
+    task_ids = (ctypes.c_int32 * n_t)(*[int(t) for t in tasks])
+    task_cls = (ctypes.c_int32 * n_t)(*[len(tasks_config[t]) for t in tasks])
+    outs = (L.TargetOut * (n_l * n_t))()
+    nobj = torch.empty(n_l * n_t, dtype=torch.int32, device=dev)
+    scratch = torch.empty(3 * n_l * max(m, 1), dtype=torch.int32, device=dev)
+    result: Dict[int, Dict[Any, Dict[str, Tensor]]] = {}
+    for i, s in enumerate(strides):
+        ws = W // s
+        result[s] = {}
+        for k, t in enumerate(tasks):
+            e = i * n_t + k
+            tg = {"points_per_obj": torch.empty((B, 1, H, ws), dtype=torch.int64, device=dev),
+                  "panoptics": torch.empty((B, 1, H, ws), dtype=torch.int64, device=dev),
+                  "classification_labels": torch.empty((B, H, ws), dtype=torch.int64, device=dev),
+                  "regression_targets": torch.empty((B, 8, H, ws), dtype=torch.float32, device=dev),
+                  "num_objects": nobj[e : e + 1], "num_category": torch.ones((B, len(tasks_config[t]), 1, 1), device=dev)}
+            outs[e] = L.TargetOut(tg["classification_labels"].data_ptr(), tg["panoptics"].data_ptr(), tg["regression_targets"].data_ptr(),
+                                  tg["points_per_obj"].data_ptr())
+            result[s][t] = tg
+    L.call("rv_assign_targets_multilevel", L.ptr(cub_d) if m else None, L.i32(m), L.ptr(off_d), L.ptr(cart32), L.i32(B), L.i32(H), L.i32(W),
+           L.i32(n_l), levels, L.i32(n_t), task_ids, task_cls, L.i32(1 if az_inv else 0), L.ptr(scratch), outs, L.ptr(nobj), L.stream_ptr())
+    return result
 
 
 def _nhwc_f32(x: Tensor) -> Tuple[Tensor, int]:
@@ -139,6 +215,65 @@ class _DetectionLossFn(torch.autograd.Function):
         ctx.sums[15:16].copy_(g_loss.reshape(1))  # the incoming gradient as the kernel's device-side factor: one 8-byte copy instead of two passes over the gradients
         L.call("rv_detection_loss_backward", *ctx.args, L.ptr(ctx.sums), L.f32(1.0), L.ptr(d_l), L.ptr(d_r), L.stream_ptr())
         return (d_l[..., :n_cls].permute(0, 3, 1, 2).to(dt_l), d_r[..., :8].permute(0, 3, 1, 2).to(dt_r), None, None, None, None)
+
+
+# rows of loss sums: where ``loss_finish_kernel`` / ``loss_table_finish_kernel`` leave the scalars of the loss dict
+SUMS_INDEX = {"loss": 16, "classification_loss": 17, "foreground_loss": 18, "background_loss": 19, "regression_loss": 23,
+              "coordinate_loss": 20, "dimension_loss": 21, "rotation_loss": 22, "total_fg": 13, "total_objects": 12}
+
+
+class _MultiLevelLossFn(torch.autograd.Function):
+    """The loss of every (level, task) entry as ONE node: phase one (one launch over the entry table) and phase two (the global
+    normalisers and every reported scalar) in forward, one launch in backward.  ``entries`` is a list of dicts (cart, mask, targets);
+    forward adds each entry's soft targets and foreground map to its dict.  Tensor inputs: logits, regressands of entry 0, 1, ..."""
+
+    @staticmethod
+    def forward(ctx, entries, hp: Dict[str, Any], *tensors: Tensor):
+        n = len(entries)
+        dev = tensors[0].device
+        width = L.loss_sums_len()
+        sums = torch.empty((n + 1, width), dtype=torch.float64, device=dev)
+        table = (L.LossEntry * n)()
+        keep, meta = [], []
+        for e, ent in enumerate(entries):
+            logits, regressands = tensors[2 * e], tensors[2 * e + 1]
+            B, n_cls, H, W = logits.shape
+            lg, ld_l = _nhwc_f32(logits)
+            rg, ld_r = _nhwc_f32(regressands)
+            cart32 = ent["cart"].detach().float().contiguous()
+            mask8 = ent["mask"].detach().reshape(B, H, W).to(torch.uint8).contiguous()
+            tg = ent["targets"]
+            ent["soft"] = torch.empty((B, n_cls, H, W), dtype=torch.float32, device=dev)
+            ent["foreground"] = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
+            table[e] = L.LossEntry(lg.data_ptr(), rg.data_ptr(), cart32.data_ptr(), mask8.data_ptr(), tg["classification_labels"].data_ptr(),
+                                   tg["panoptics"].data_ptr(), tg["regression_targets"].data_ptr(), tg["points_per_obj"].data_ptr(),
+                                   tg["num_objects"].data_ptr(), ent["soft"].data_ptr(), ent["foreground"].data_ptr(), None, None,
+                                   ld_l, ld_r, B, n_cls, H, W)
+            keep.append((lg, rg, cart32, mask8, tg))
+            meta.append((B, n_cls, H, W, ld_l, ld_r, logits.dtype, regressands.dtype))
+        params = L.LossParams((ctypes.c_float * 8)(*[float(v) for v in hp["coding_weights"]]), hp["cls_weight"], hp["reg_weight"], hp["smoothing"],
+                              hp["sigma"], hp["alpha"], hp["gamma"], 1 if hp["az_inv"] else 0)
+        L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), L.ptr(sums), L.stream_ptr())
+        ctx.table, ctx.params, ctx.keep, ctx.meta, ctx.sums = table, params, keep, meta, sums
+        ctx.mark_non_differentiable(sums)
+        return sums[n, SUMS_INDEX["loss"]].clone(), sums
+
+    @staticmethod
+    def backward(ctx, g_loss, *_):
+        n, dev = len(ctx.meta), ctx.sums.device
+        bufs = []
+        for e, (B, n_cls, H, W, ld_l, ld_r, _, _) in enumerate(ctx.meta):
+            # (padding channels beyond n_cls / 8 are never written and never read: the returned gradients are slices)
+            d_l = torch.empty((B, H, W, ld_l), dtype=torch.float32, device=dev)
+            d_r = torch.empty((B, H, W, ld_r), dtype=torch.float32, device=dev)
+            ctx.table[e].d_logits, ctx.table[e].d_regressands = d_l.data_ptr(), d_r.data_ptr()
+            bufs.append((d_l, d_r))
+        ctx.sums[n, 15:16].copy_(g_loss.reshape(1))  # the incoming gradient as the kernel's device-side factor
+        L.call("rv_detection_loss_multilevel_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
+        grads = []
+        for (d_l, d_r), (_, n_cls, _, _, _, _, dt_l, dt_r) in zip(bufs, ctx.meta):
+            grads += [d_l[..., :n_cls].permute(0, 3, 1, 2).to(dt_l), d_r[..., :8].permute(0, 3, 1, 2).to(dt_r)]
+        return (None, None, *grads)
 
 
 def _instantiate(cfg: Any) -> Any:
@@ -190,6 +325,7 @@ class DetectionHead(nn.Module):
 
     def forward(self, input: Dict[int, Tensor], data: Dict[Any, Any], return_loss: bool = False):
         multiscale_outputs: Dict[int, Dict[Any, Any]] = {}
+        method = _assignment_method(self.targets_config)
         for stride in self.fpn.keys():
             s = int(stride)
             feats = input[s]
@@ -197,8 +333,12 @@ class DetectionHead(nn.Module):
             cart = data["cart"][:, :, ::1, ::s].clone()
             mask = data["mask"][:, :, ::1, ::s].clone()
             multiscale_outputs[s] = {"features": features, "cart": cart, "mask": mask}
-            if _cfg_get(self.targets_config, "fpn_assignment_method") == "RANGE":
-                raise NotImplementedError("RANGE fpn assignment is not selected by any shipped rv-* config")
+            if method == "RANGE":  # (:154-158) in place: the loss and the decoder see the partitioned mask
+                lower, upper = _partition(self.targets_config, stride)
+                dists = torch.linalg.vector_norm(cart, dim=1, keepdim=True)
+                mask.mul_((dists > lower) & (dists <= upper))
+            # one program (one autograd node) per task: with several tasks at a level autograd adds the tasks' input gradients
+            # in len(tasks) - 1 passes of its own over the level's feature gradient
             for task_id in self.tasks_cfg.keys():
                 logits, regressands = forward_pair(self.classification_head[str(stride)][str(task_id)],
                                                    self.regression_head[str(stride)][str(task_id)], feats)
@@ -212,11 +352,15 @@ class DetectionHead(nn.Module):
         return multiscale_outputs, losses
 
     def loss(self, multiscale_outputs: Dict[int, Dict[Any, Any]], multiscale_data: Dict[Any, Any]) -> Dict[str, Any]:
-        """``DetectionHead.loss`` + ``reduce_multiscale_loss`` (``detection_head.py:202-449``) for one stride / one task."""
-        (stride,) = [int(s) for s in self.fpn.keys()]
-        (task_id,) = list(self.tasks_cfg.keys())
-        out = multiscale_outputs[stride]
-        tg = multiscale_data[stride][task_id]
+        """``DetectionHead.loss`` + ``reduce_multiscale_loss`` (``detection_head.py:202-449``).
+
+        Every (level, task) is normalised by ``total_fg`` (foreground pixels of ALL levels and tasks + ``additive_smoothing``) and
+        ``total_objects`` (objects of all levels and tasks, at least 1).  The dict holds each scalar summed over the (level, task) list;
+        ``total_fg`` / ``total_objects`` are summed over that list too, as the reference does, so they read ``n_entries x`` the value.
+        The reference fills ``"{name}/s{stride}"`` from position ``i`` of the stride in a list that has ``levels x tasks`` entries in
+        stride-major order: with more than one task ``/s{strides[i]}`` is entry ``i`` of that list, not the level's sum.  Reproduced.
+        """
+        strides, tasks = [int(s) for s in self.fpn.keys()], list(self.tasks_cfg.keys())
         tc = self.targets_config
         if str(_cfg_get(tc, "affinity_fn", "GAUSSIAN")).upper() != "GAUSSIAN" or _cfg_get(tc, "normalize_affinities", False):
             raise NotImplementedError("the HIP loss kernel implements the configured GAUSSIAN affinity without normalisation")
@@ -229,17 +373,18 @@ class DetectionHead(nn.Module):
             "alpha": float(getattr(self.cls_loss, "alpha", 0.75)), "gamma": float(getattr(self.cls_loss, "gamma", 2.0)),
             "az_inv": bool(_cfg_get(tc, "enable_azimuth_invariant_targets", True)),
         }
+        if strides != [1] or len(tasks) != 1 or _assignment_method(tc) is not None:
+            return self._multilevel_loss(multiscale_outputs, multiscale_data, strides, tasks, hp)
+        stride, task_id = strides[0], tasks[0]
+        out = multiscale_outputs[stride]
+        tg = multiscale_data[stride][task_id]
         flat = {"classification_labels": tg["classification_labels"], "panoptics": tg["panoptics"], "regression_targets": tg["regression_targets"],
                 "points_per_obj": tg["points_per_obj"], "num_objects": tg["num_objects"]}
         loss, sums, soft, fg = _DetectionLossFn.apply(out[task_id]["logits"], out[task_id]["regressands"], out["cart"], out["mask"], flat, hp)
         tg["targets"] = soft
-        total_fg, total_obj = sums[13], sums[12]
         # (views of the scalars loss_finish_kernel formed on the device: no launches here)
-        task = {
-            "loss": loss, "classification_loss": sums[17], "foreground_loss": sums[18], "background_loss": sums[19],
-            "regression_loss": sums[23], "coordinate_loss": sums[20], "dimension_loss": sums[21], "rotation_loss": sums[22],
-            "total_fg": total_fg, "total_objects": total_obj,
-        }
+        task = {name: sums[i] for name, i in SUMS_INDEX.items()}
+        task["loss"] = loss
         losses: Dict[str, Any] = dict(task)
         for name, v in task.items():
             losses[f"{name}/s{stride}"] = v
@@ -247,4 +392,30 @@ class DetectionHead(nn.Module):
         bg = torch.logical_and(fg.logical_not(), mask)
         losses["aux"] = {stride: {task_id: {"targets": soft, "foreground": fg, "background": bg.float(), "mask": mask,
                                             "point_counts": tg["points_per_obj"]}}}
+        return losses
+
+    def _multilevel_loss(self, multiscale_outputs: Dict[int, Dict[Any, Any]], multiscale_data: Dict[Any, Any], strides: Sequence[int],
+                         tasks: Sequence[Any], hp: Dict[str, Any]) -> Dict[str, Any]:
+        entries, tensors = [], []
+        for stride in strides:
+            out = multiscale_outputs[stride]
+            for task_id in tasks:
+                entries.append({"stride": stride, "task": task_id, "cart": out["cart"], "mask": out["mask"], "targets": multiscale_data[stride][task_id]})
+                tensors += [out[task_id]["logits"], out[task_id]["regressands"]]
+        loss, sums = _MultiLevelLossFn.apply(entries, hp, *tensors)
+        n = len(entries)
+        # (views of the scalars loss_table_finish_kernel formed on the device: no launches here)
+        losses: Dict[str, Any] = {name: sums[n, i] for name, i in SUMS_INDEX.items()}
+        losses["loss"] = loss
+        for name, i in SUMS_INDEX.items():
+            for pos, stride in enumerate(strides):  # position in the stride-major (level, task) list, as the reference indexes it
+                losses[f"{name}/s{stride}"] = sums[pos, i]
+        aux: Dict[int, Dict[Any, Dict[str, Tensor]]] = {}
+        for ent in entries:
+            tg, mask, fg = ent["targets"], ent["mask"], ent["foreground"]
+            tg["targets"] = ent["soft"]
+            bg = torch.logical_and(fg.logical_not(), mask)
+            aux.setdefault(ent["stride"], {})[ent["task"]] = {"targets": ent["soft"], "foreground": fg, "background": bg.float(), "mask": mask,
+                                                             "point_counts": tg["points_per_obj"]}
+        losses["aux"] = aux
         return losses
