@@ -691,6 +691,47 @@ int rv_detection_loss_multilevel_forward(const rvLossEntry* host_entries, int32_
 int rv_detection_loss_multilevel_backward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
                                           const double* sums, float grad_scale, rvStream stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Soft target assignment with every option of targets_config (math/ops/assignment.py:76-147 compute_classification_targets, :150-161
+ * _gaussian, :64-73 iou_2d_axis_aligned): `affinity_fn` GAUSSIAN | BEV, `normalize_affinities`, finite `k`.  With GAUSSIAN, no
+ * normalisation and k = inf the affinity is a per-pixel quantity and the loss entry points above compute it themselves; every other
+ * combination makes it a per-INSTANCE quantity (a minimum, a k-th largest value).  rv_soft_assign computes it for every entry of a loss
+ * table into one fp32 map (B,H,W) per entry -- the final likelihood of every pixel, 0 outside instances and below the instance's
+ * threshold -- and the _aff loss pair reads the affinity from the maps; nothing else about the loss changes.
+ *
+ * An instance is the pixel set `panoptics[b] == p`, p >= 1, of one entry and sweep.  The valid-pixel mask plays no part in the set (a
+ * pixel with mask == 0 competes for a top-k slot, as in the reference; the mask enters in the background mask and the loss).
+ *   GAUSSIAN: d = ||centre(prediction) - centre(target)||, both decoded like decode_range_view (fp64 rounded to fp32; predictions always
+ *             azimuth-invariantly, :112); normalize: d -= min over the instance (:158-159); a = exp(-d / sigma^2).
+ *   BEV:      a = clamp(rotated IoU of [x, y, l, w, yaw] of the decoded prediction and target, 0, 1) (:64-73), the geometry of
+ *             rv_rotated_iou (bit-exact with the oracle on equal fp32 boxes).  BEV with normalize is an UnboundLocalError in the
+ *             reference (:71-72) and an error here.
+ *   top k:    k_actual = min(k, |set|) (:129).  TIE RULE (torch.topk leaves it open): a pixel stays iff its affinity is >= the instance's
+ *             k_actual-th largest affinity, and != 0 -- a per-instance threshold on the fp32 affinity values, independent of pixel order
+ *             and of scheduling; equal to the reference whenever the k-th and (k+1)-th values differ.  A pixel with affinity exactly 0
+ *             (BEV: disjoint boxes; GAUSSIAN: underflow) is never foreground, inside the top k or not (:137-140 `likelihoods.bool()`).
+ * k: 0 = infinity, else >= 1.  box_offsets (B+1) i32 (device) / m: the CSR of the annotation table that rv_assign_targets* took; a
+ * panoptic id of sweep b lies in 1 .. box_offsets[b+1] - box_offsets[b], so n_entries * (m + B) instance slots bound the tables (pixels
+ * with an id beyond that are treated as background).  workspace: rv_soft_assign_workspace_bytes (259 u32 per slot: 256 histogram bins,
+ * threshold prefix, remaining count, minimum), 16-byte aligned, need not be initialised; may be NULL when k == 0 and normalize == 0.
+ * Of each entry regressands / ld_reg, cart, panoptics, reg_targets, B, H, W are read; every element of every map is written.
+ * A fixed number of launches whatever the number of instances and sweeps (1 affinity pass, + 1 under normalize, + 9 under finite k: four
+ * rounds of an 8-bit radix select on the affinity's bit pattern, then the threshold pass); integer atomics and min only; no host read. */
+#define RV_AFFINITY_GAUSSIAN 0
+#define RV_AFFINITY_BEV 1
+int64_t rv_soft_assign_workspace_bytes(int32_t n_entries, int32_t m, int32_t B);
+int rv_soft_assign(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params, int32_t affinity_fn,
+                   int32_t normalize, int32_t k, const int32_t* box_offsets, int32_t m, void* workspace,
+                   float* const* host_affinity_maps, rvStream stream);
+/* rv_detection_loss_multilevel_forward / _backward with the affinity of entry e read from host_affinity_maps[e] (device pointers, host
+ * array read at call time) instead of computed per pixel: foreground = (map != 0), soft target = map at the label's class
+ * (assignment.py:137-146).  One entry is a legal table: the one-level recipe with a non-default option runs these too. */
+int rv_detection_loss_multilevel_forward_aff(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                             const float* const* host_affinity_maps, double* sums, rvStream stream);
+int rv_detection_loss_multilevel_backward_aff(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                              const float* const* host_affinity_maps, const double* sums, float grad_scale,
+                                              rvStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,8 +58,11 @@ __device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1
 
 // The work of workgroup `block` of `n_blocks` on one (level, task): shared by the one-level kernel and the entry-table kernel, which
 // differ only in where a workgroup finds its tensors.  total_fg / total_obj / gscale are read by the caller (BACKWARD only).
-template <bool BACKWARD>
-__device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int64_t n_blocks, double total_fg, double total_obj, float gscale) {
+// AFF_MAP: the pixel's affinity is read from `aff_map` (B,H,W), which rv_soft_assign filled (softassign.hip: BEV affinity,
+// normalize_affinities, finite k), instead of being the per-pixel exponential below.
+template <bool BACKWARD, bool AFF_MAP = false>
+__device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int64_t n_blocks, double total_fg, double total_obj, float gscale,
+                                          const float* aff_map = nullptr) {
     const int64_t hw = (int64_t)a.H * a.W, total = (int64_t)a.B * hw;
     double acc[12];
 #pragma unroll
@@ -83,7 +86,9 @@ __device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int6
         const int64_t label = a.labels[i];
         const bool inst = a.panoptics[i] > 0;
         float aff = 0.f;
-        if (inst) {
+        if (AFF_MAP) {
+            aff = aff_map[i];
+        } else if (inst) {
             float cp[3], cg[3];
             decode_centre(r, px, py, pz, 1, cp);  // predictions are always decoded azimuth-invariantly (assignment.py:112)
             decode_centre(tg, px, py, pz, a.az_inv, cg);
@@ -255,6 +260,59 @@ __global__ __launch_bounds__(256) void loss_table_kernel(const LossTable t) {
     const double total_obj = BACKWARD ? a.sums[12] : 1.0;
     const float gscale = BACKWARD ? t.grad_scale * (float)t.sums[(int64_t)t.n * RV_LOSS_SUMS_LEN + 15] : 1.f;
     loss_tile<BACKWARD>(a, (int)blockIdx.x - t.block_begin[k], t.block_begin[k + 1] - t.block_begin[k], total_fg, total_obj, gscale);
+}
+
+// the LossArgs of entry k of the table, as loss_table_kernel fills them (that kernel keeps its own text: its machine code is unchanged)
+__device__ __forceinline__ LossArgs table_args(const LossTable& t, int k) {
+    const rvLossEntry& e = t.e[k];
+    LossArgs a;
+    a.logits = e.logits;
+    a.reg = e.regressands;
+    a.cart = e.cart;
+    a.mask = e.mask;
+    a.labels = e.labels;
+    a.panoptics = e.panoptics;
+    a.reg_targets = e.reg_targets;
+    a.ppo = e.points_per_obj;
+    a.num_objects = e.num_objects;
+    a.B = e.B;
+    a.n_cls = e.n_cls;
+    a.H = e.H;
+    a.W = e.W;
+    a.ld_logits = e.ld_logits;
+    a.ld_reg = e.ld_reg;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a.coding[j] = t.p.coding_weights[j];
+    a.cls_w = t.p.cls_weight;
+    a.reg_w = t.p.reg_weight;
+    a.smoothing = t.p.smoothing;
+    a.sigma = t.p.sigma;
+    a.alpha = t.p.alpha;
+    a.gamma = t.p.gamma;
+    a.az_inv = t.p.azimuth_invariant;
+    a.sums = t.sums + (int64_t)k * RV_LOSS_SUMS_LEN;
+    a.soft = e.soft_targets;
+    a.fg = e.foreground;
+    a.d_logits = e.d_logits;
+    a.d_reg = e.d_regressands;
+    a.grad_scale = t.grad_scale;
+    return a;
+}
+
+// the same with every entry's affinity read from its map (rv_soft_assign): the maps travel as a second by-value argument
+struct AffMaps {
+    const float* map[RV_ML_MAX_ENTRIES];
+};
+
+template <bool BACKWARD>
+__global__ __launch_bounds__(256) void loss_table_aff_kernel(const LossTable t, const AffMaps maps) {
+    int k = 0;
+    while (k + 1 < t.n && (int)blockIdx.x >= t.block_begin[k + 1]) ++k;
+    const LossArgs a = table_args(t, k);
+    const double total_fg = BACKWARD ? a.sums[13] : 1.0;
+    const double total_obj = BACKWARD ? a.sums[12] : 1.0;
+    const float gscale = BACKWARD ? t.grad_scale * (float)t.sums[(int64_t)t.n * RV_LOSS_SUMS_LEN + 15] : 1.f;
+    loss_tile<BACKWARD, true>(a, (int)blockIdx.x - t.block_begin[k], t.block_begin[k + 1] - t.block_begin[k], total_fg, total_obj, gscale, maps.map[k]);
 }
 
 // phase two (reduce_multiscale_loss, detection_head.py:379-449): the global normalisers, every entry's scalars, and their sums over
@@ -462,5 +520,45 @@ extern "C" int rv_detection_loss_multilevel_backward(const rvLossEntry* host_ent
     t.grad_scale = grad_scale;
     hipLaunchKernelGGL(loss_table_kernel<true>, dim3(t.block_begin[n_entries]), dim3(256), 0, (hipStream_t)stream, t);
     RV_CHECK_LAUNCH("multi-level loss backward kernel");
+    return 0;
+}
+
+namespace {
+
+int fill_maps(AffMaps* maps, const float* const* host_maps, int32_t n) {
+    RV_REQUIRE(host_maps, "rv_detection_loss_multilevel_*_aff: null affinity maps");
+    memset(maps, 0, sizeof(*maps));
+    for (int k = 0; k < n; ++k) {
+        RV_REQUIRE(host_maps[k], "rv_detection_loss_multilevel_*_aff: null affinity map of entry %d", k);
+        maps->map[k] = host_maps[k];
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int rv_detection_loss_multilevel_forward_aff(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                                        const float* const* host_affinity_maps, double* sums, rvStream stream) {
+    LossTable t;
+    AffMaps maps;
+    if (fill_table(&t, host_entries, n_entries, host_params, sums, false) || fill_maps(&maps, host_affinity_maps, n_entries)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(sums, 0, (size_t)(n_entries + 1) * RV_LOSS_SUMS_LEN * sizeof(double), st);
+    if (e != hipSuccess) RV_FAIL("rv_detection_loss_multilevel_forward_aff: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(loss_table_aff_kernel<false>, dim3(t.block_begin[n_entries]), dim3(256), 0, st, t, maps);
+    hipLaunchKernelGGL(loss_table_finish_kernel, dim3(1), dim3(64), 0, st, t);
+    RV_CHECK_LAUNCH("multi-level loss forward kernels (affinity maps)");
+    return 0;
+}
+
+extern "C" int rv_detection_loss_multilevel_backward_aff(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                                         const float* const* host_affinity_maps, const double* sums, float grad_scale,
+                                                         rvStream stream) {
+    LossTable t;
+    AffMaps maps;
+    if (fill_table(&t, host_entries, n_entries, host_params, (double*)sums, true) || fill_maps(&maps, host_affinity_maps, n_entries)) return 1;
+    t.grad_scale = grad_scale;
+    hipLaunchKernelGGL(loss_table_aff_kernel<true>, dim3(t.block_begin[n_entries]), dim3(256), 0, (hipStream_t)stream, t, maps);
+    RV_CHECK_LAUNCH("multi-level loss backward kernel (affinity maps)");
     return 0;
 }

@@ -15,6 +15,11 @@ one-level entry points (``rv_assign_targets``, ``rv_detection_loss_*``); every o
 runs the multi-level ones (``rv_assign_targets_multilevel``, ``rv_detection_loss_multilevel_*``), which assign all levels and tasks
 in one sequence of launches and normalise every level by the foreground / object counts summed over all of them.
 ``fpn_assignment_method: POINTS`` raises: the reference overwrites its configured intervals with constants (``:583``).
+
+Soft target assignment takes every option of ``targets_config`` (``math/ops/assignment.py:76-147``): ``affinity_fn`` GAUSSIAN | BEV,
+``normalize_affinities`` and ``k`` (``.inf`` or an integer).  GAUSSIAN without normalisation and ``k = inf`` (every shipped recipe) is a
+per-pixel map inside the loss kernels, as before; any other combination runs ``rv_soft_assign`` (per-instance minimum / top-k threshold
+on the device, no host synchronisation) inside the loss node and the ``rv_detection_loss_multilevel_*_aff`` pair, see ``soft_options``.
 """
 
 from __future__ import annotations
@@ -81,6 +86,35 @@ def _assignment_method(targets_config: Any) -> Optional[str]:
     raise ValueError(f"unknown fpn_assignment_method {method!r}")
 
 
+def soft_options(targets_config: Any) -> Tuple[int, bool, int]:
+    """``(affinity_fn, normalize_affinities, k)`` of ``targets_config`` as ``rv_soft_assign`` takes them (``L.AFFINITY_*``, bool, 0 = inf).
+
+    ``affinity_fn`` is case-insensitive; an unknown name raises as the reference does (``assignment.py:96-102``).  ``k`` is ``inf`` or an
+    integer-valued number >= 1.  ``BEV`` with ``normalize_affinities`` is a ``ValueError``: the reference's ``iou_2d_axis_aligned`` divides
+    a name that does not exist there (``assignment.py:71-72``, an ``UnboundLocalError``).
+
+    Ties at the k-th value, which ``torch.topk`` leaves open: a pixel stays iff its affinity is >= the instance's ``min(k, |set|)``-th
+    largest affinity (and != 0) -- a per-instance threshold, independent of pixel order; equal to the reference whenever the k-th and
+    (k+1)-th values differ.  The instance's set is ``panoptics == p``, whatever ``mask`` says there."""
+    name = str(_cfg_get(targets_config, "affinity_fn", "GAUSSIAN")).upper()
+    if name not in ("GAUSSIAN", "BEV"):
+        raise NotImplementedError("This affinity function is not implemented.")
+    normalize = bool(_cfg_get(targets_config, "normalize_affinities", False))
+    if name == "BEV" and normalize:
+        raise ValueError("affinity_fn BEV with normalize_affinities: the reference fails there with an UnboundLocalError "
+                         "(math/ops/assignment.py:71-72 divides `object_ious`, which iou_2d_axis_aligned never binds)")
+    k = _cfg_get(targets_config, "k", float("inf"))
+    if isinstance(k, bool) or not isinstance(k, (int, float)) or k != k or k < 1 or (k != float("inf") and k != int(k)):
+        raise ValueError(f"targets_config.k must be inf or an integer >= 1, not {k!r}")
+    if k >= 2 ** 31:
+        k = float("inf")  # (no instance has that many pixels)
+    return (L.AFFINITY_BEV if name == "BEV" else L.AFFINITY_GAUSSIAN), normalize, (0 if k == float("inf") else int(k))
+
+
+def _soft_is_default(soft: Tuple[int, bool, int]) -> bool:
+    return soft == (L.AFFINITY_GAUSSIAN, False, 0)
+
+
 def _stage_annotations(x: Dict[str, Any], B: int, dev: torch.device):
     """Annotation table grouped by sweep -> (cuboids (m,10) f64, CSR offsets (B+1) i32) on the device through ONE pinned staging buffer."""
     cub = annotations_to_cuboids(x["annotations"])
@@ -117,6 +151,18 @@ def compute_targets(x: Dict[str, Any], tasks_config: Mapping, fpn_strides: Seque
     dev = cart.device
     cub_d, off_d, m = _stage_annotations(x, B, dev)
     cart32 = cart.detach().float().contiguous()
+    result = _assign_targets(cart32, cub_d, off_d, m, tasks_config, strides, tasks, targets_config, method, az_inv)
+    if not _soft_is_default(soft_options(targets_config)):
+        for level in result.values():  # rv_soft_assign indexes its instance table by the CSR of the annotation table
+            for tg in level.values():
+                tg["box_offsets"], tg["box_count"] = off_d, m
+    return result
+
+
+def _assign_targets(cart32: Tensor, cub_d: Tensor, off_d: Tensor, m: int, tasks_config: Mapping, strides: Sequence[int],
+                         tasks: Sequence[Any], targets_config: Any, method: Optional[str], az_inv: bool):
+    B, _, H, W = cart32.shape
+    dev = cart32.device
     if strides != [1] or len(tasks) != 1 or method is not None:
         return _compute_targets_multilevel(cart32, cub_d, off_d, m, tasks_config, strides, tasks, targets_config, method, az_inv)
     t_id = tasks[0]
@@ -225,7 +271,11 @@ SUMS_INDEX = {"loss": 16, "classification_loss": 17, "foreground_loss": 18, "bac
 class _MultiLevelLossFn(torch.autograd.Function):
     """The loss of every (level, task) entry as ONE node: phase one (one launch over the entry table) and phase two (the global
     normalisers and every reported scalar) in forward, one launch in backward.  ``entries`` is a list of dicts (cart, mask, targets);
-    forward adds each entry's soft targets and foreground map to its dict.  Tensor inputs: logits, regressands of entry 0, 1, ..."""
+    forward adds each entry's soft targets and foreground map to its dict.  Tensor inputs: logits, regressands of entry 0, 1, ...
+
+    ``hp["soft"]`` (``soft_options``; absent = the per-pixel GAUSSIAN affinity inside the loss kernel): forward first runs ``rv_soft_assign``
+    over the same entry table -- every entry's affinity map, selected per instance on the device -- and the ``_aff`` loss pair reads the
+    maps; backward reuses the maps forward saved (the affinity comes from detached inputs: there is no second selection)."""
 
     @staticmethod
     def forward(ctx, entries, hp: Dict[str, Any], *tensors: Tensor):
@@ -253,7 +303,22 @@ class _MultiLevelLossFn(torch.autograd.Function):
             meta.append((B, n_cls, H, W, ld_l, ld_r, logits.dtype, regressands.dtype))
         params = L.LossParams((ctypes.c_float * 8)(*[float(v) for v in hp["coding_weights"]]), hp["cls_weight"], hp["reg_weight"], hp["smoothing"],
                               hp["sigma"], hp["alpha"], hp["gamma"], 1 if hp["az_inv"] else 0)
-        L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), L.ptr(sums), L.stream_ptr())
+        ctx.maps = None
+        if hp.get("soft") is None:
+            L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), L.ptr(sums), L.stream_ptr())
+        else:
+            fn, normalize, k = hp["soft"]
+            off_d, m = hp["box_offsets"], int(hp["box_count"])
+            B = meta[0][0]
+            maps = [torch.empty((m_[0], 1, m_[2], m_[3]), dtype=torch.float32, device=dev) for m_ in meta]
+            map_ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in maps])
+            ws = torch.empty(max(int(L.load().rv_soft_assign_workspace_bytes(L.i32(n), L.i32(m), L.i32(B))), 1), dtype=torch.uint8, device=dev)
+            L.call("rv_soft_assign", table, L.i32(n), ctypes.byref(params), L.i32(fn), L.i32(1 if normalize else 0), L.i32(k), L.ptr(off_d),
+                   L.i32(m), L.ptr(ws), map_ptrs, L.stream_ptr())
+            L.call("rv_detection_loss_multilevel_forward_aff", table, L.i32(n), ctypes.byref(params), map_ptrs, L.ptr(sums), L.stream_ptr())
+            ctx.maps = (map_ptrs, maps)
+            for ent, amap in zip(entries, maps):
+                ent["affinity"] = amap
         ctx.table, ctx.params, ctx.keep, ctx.meta, ctx.sums = table, params, keep, meta, sums
         ctx.mark_non_differentiable(sums)
         return sums[n, SUMS_INDEX["loss"]].clone(), sums
@@ -269,7 +334,11 @@ class _MultiLevelLossFn(torch.autograd.Function):
             ctx.table[e].d_logits, ctx.table[e].d_regressands = d_l.data_ptr(), d_r.data_ptr()
             bufs.append((d_l, d_r))
         ctx.sums[n, 15:16].copy_(g_loss.reshape(1))  # the incoming gradient as the kernel's device-side factor
-        L.call("rv_detection_loss_multilevel_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
+        if ctx.maps is None:
+            L.call("rv_detection_loss_multilevel_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
+        else:
+            L.call("rv_detection_loss_multilevel_backward_aff", ctx.table, L.i32(n), ctypes.byref(ctx.params), ctx.maps[0], L.ptr(ctx.sums), L.f32(1.0),
+                   L.stream_ptr())
         grads = []
         for (d_l, d_r), (_, n_cls, _, _, _, _, dt_l, dt_r) in zip(bufs, ctx.meta):
             grads += [d_l[..., :n_cls].permute(0, 3, 1, 2).to(dt_l), d_r[..., :8].permute(0, 3, 1, 2).to(dt_r)]
@@ -362,17 +431,24 @@ class DetectionHead(nn.Module):
         """
         strides, tasks = [int(s) for s in self.fpn.keys()], list(self.tasks_cfg.keys())
         tc = self.targets_config
-        if str(_cfg_get(tc, "affinity_fn", "GAUSSIAN")).upper() != "GAUSSIAN" or _cfg_get(tc, "normalize_affinities", False):
-            raise NotImplementedError("the HIP loss kernel implements the configured GAUSSIAN affinity without normalisation")
-        k = _cfg_get(tc, "k", float("inf"))
-        if k != float("inf"):
-            raise NotImplementedError("top-k soft assignment with finite k is not configured by any shipped rv-* config")
+        soft = soft_options(tc)
         hp = {
             "coding_weights": self.coding_weights, "cls_weight": float(self.classification_weight), "reg_weight": float(self.regression_weight),
             "smoothing": float(self.additive_smoothing), "sigma": float(_cfg_get(tc, "sigma", 0.75)),
             "alpha": float(getattr(self.cls_loss, "alpha", 0.75)), "gamma": float(getattr(self.cls_loss, "gamma", 2.0)),
             "az_inv": bool(_cfg_get(tc, "enable_azimuth_invariant_targets", True)),
         }
+        if not _soft_is_default(soft):
+            # a per-instance affinity (BEV, normalize_affinities, finite k): one entry is a legal table, so the one-level recipe goes
+            # through the multi-level node too; the instance table is indexed by the CSR of the annotation table
+            tg0 = multiscale_data[strides[0]][tasks[0]]
+            if "box_offsets" in tg0:
+                hp["box_offsets"], hp["box_count"] = tg0["box_offsets"], tg0["box_count"]
+            else:  # (targets that did not come from compute_targets: the same CSR from the annotation table, one small upload)
+                out0 = multiscale_outputs[strides[0]]
+                _, hp["box_offsets"], hp["box_count"] = _stage_annotations(multiscale_data, out0["cart"].shape[0], out0["cart"].device)
+            hp["soft"] = soft
+            return self._multilevel_loss(multiscale_outputs, multiscale_data, strides, tasks, hp)
         if strides != [1] or len(tasks) != 1 or _assignment_method(tc) is not None:
             return self._multilevel_loss(multiscale_outputs, multiscale_data, strides, tasks, hp)
         stride, task_id = strides[0], tasks[0]
