@@ -252,6 +252,15 @@ def _call(name: str, *args) -> None:
         torch.cuda.synchronize()
 
 
+def tap_launch_info(geom: TapGeom, shape: TapShape, scatter: bool):
+    """``rv_tap_launch_info``: (kernel generation, variant, grid.x, grid.y) of the launch the library plans for this tap op, or ``None``
+    when it rejects the shape (``rv_last_error`` says why).  Launches nothing."""
+    info = (ctypes.c_int32 * 4)()
+    if load().rv_tap_launch_info(ctypes.byref(geom), ctypes.byref(shape), 1 if scatter else 0, info) != 0:
+        return None
+    return tuple(info)
+
+
 def ptr(t) -> ctypes.c_void_p:
     """Device (or host) pointer of a torch tensor / None."""
     if t is None:

@@ -72,6 +72,27 @@ static inline int rv_persistent_grid() {
     const int g = rv_cu_count() & ~7;
     return g < 8 ? 8 : g;
 }
+// Dynamic-LDS opt-in of one kernel (more than the 64 KB a launch may ask for by default), made once per (kernel, device ordinal):
+// function attributes are per device, so the flags are too (as rv_cu_count's cache; two threads racing on the first call set the
+// same value twice).  Returns the runtime's error: a launch that needs the LDS must not go ahead without it (RV_LDS_OPT_IN).
+template <auto Kernel>
+static inline hipError_t rv_lds_opt_in(int bytes) {
+    static std::atomic<bool> done[32];
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const bool cached = dev >= 0 && dev < 32;
+    if (cached && done[dev].load(std::memory_order_acquire)) return hipSuccess;
+    e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess && cached) done[dev].store(true, std::memory_order_release);
+    return e;
+}
+// (the kernel goes last: a template-id's commas split it into several macro arguments)
+#define RV_LDS_OPT_IN(bytes, ...)                                                                                     \
+    do {                                                                                                              \
+        hipError_t e__ = rv_lds_opt_in<__VA_ARGS__>(bytes);                                                           \
+        if (e__ != hipSuccess) RV_FAIL("%s: dynamic LDS opt-in (%d bytes): %s", #__VA_ARGS__, (int)(bytes), hipGetErrorString(e__)); \
+    } while (0)
 
 // ---------------------------------------------------------------------------------------
 // bf16 <-> f32

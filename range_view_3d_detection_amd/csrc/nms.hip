@@ -200,11 +200,7 @@ extern "C" int rv_wnms_classes(const float* boxes, const float* data, const int3
     hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, boxes, n, sc);
     hipLaunchKernelGGL(iou_mask_kernel, dim3(cb, cb), dim3(64), 0, st, boxes, sc, cats, n, cb, nms_thresh, merge_thresh, nms_mask,
                        merge_mask);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)scan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);  // + the static word
-        attr = true;
-    }
+    RV_LDS_OPT_IN(160 * 1024 - 256, scan_kernel);  // + the static word
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(cb < 1024 ? ((cb + 63) / 64) * 64 : 1024), (size_t)cb * 8, st, n, cb,
                        nms_mask, merge_mask, (long long*)keep, num_out);
     hipLaunchKernelGGL(merge_kernel, dim3((unsigned)n), dim3(64), 0, st, data, d, cb, merge_mask, (const long long*)keep,

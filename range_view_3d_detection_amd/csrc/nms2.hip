@@ -505,11 +505,7 @@ extern "C" int rv_nms_sweeps(const float* scores, const int64_t* cats, const flo
         hipLaunchKernelGGL(k_unkeep, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
     }
     hipLaunchKernelGGL(k_iou, dim3(kIouCols, a.cb < kIouRows ? a.cb : kIouRows, B), dim3(64), 0, st, a);
-    static bool attr = false;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_scan, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
-        attr = true;
-    }
+    RV_LDS_OPT_IN(64 * 1024, k_scan);
     const int seg_max = cap < num_pre_nms ? cap : num_pre_nms;  // longest class segment that takes part
     hipLaunchKernelGGL(k_scan, dim3(n_classes, B), dim3(256), (size_t)(seg_max / 64 + 3) * 8, st, a);
     hipLaunchKernelGGL(k_keep, dim3(B), dim3(1024), 0, st, a);

@@ -710,19 +710,17 @@ __global__ __launch_bounds__(512, 1) void pointwise_kernel(const PwArgs a) {
 
 }  // namespace
 
-// Pointwise path of the tap-conv dispatcher (tapconv.hip::tap_launch): 1x1 stride-1 layers C -> C, C = 256 or 128, plain bf16 in and out,
+// Pointwise path of the tap-conv dispatcher (tapconv.hip::tap_plan): 1x1 stride-1 layers C -> C, C = 256 or 128, plain bf16 in and out,
 // at most the batch-statistics epilogue, and enough pixels for one step per workgroup and round.
-static bool pointwise_pair(const TapConvArgs* a) {  // 128 -> 128 on dense rows, an even number of pixels: the paired 256-channel view
-    return a->C_src == 128 && a->C_dst == 128 && a->ld_src == 128 && a->ld_dst == 128 && (((int64_t)a->N * a->H * a->W_src) & 1) == 0;
-}
-
-bool rv_pointwise_plan(const TapConvArgs* a, bool scatter, int* grid, size_t* lds, int* stats_rows) {
+bool rv_pointwise_plan(TapPlan* p) {
+    const TapConvArgs* a = &p->args;
     if (a->sel & RV_SEL_NO_POINTWISE) return false;
-    if (scatter && (a->sel & RV_SEL_NO_POINTWISE_BWD)) return false;
+    if (p->scatter && (a->sel & RV_SEL_NO_POINTWISE_BWD)) return false;
     if (a->phases != 1 || a->step != 1 || a->tt.ntaps[0] != 1 || a->tt.dh[0][0] != 0 || a->tt.dw[0][0] != 0) return false;
     // 256 input channels, or 128 -> 128 on dense rows as PAIRS of pixels through the same 256-channel instance (a native 128-channel instance was
     // written too and is exact; it is not instantiated: one kernel to soak instead of two -- profiles/r06_ab_notes.md section 4)
-    const bool pair = pointwise_pair(a);
+    // (the pair: 128 -> 128 on dense rows, an even number of pixels)
+    const bool pair = a->C_src == 128 && a->C_dst == 128 && a->ld_src == 128 && a->ld_dst == 128 && (((int64_t)a->N * a->H * a->W_src) & 1) == 0;
     if (!pair && (a->C_src != 256 || a->C_dst % 256 != 0)) return false;
     const int slices = pair ? 1 : a->C_dst / 256;  // C_out = slices x 256: the backward-data of the stem's 9 C -> C fusion conv is nine 256-channel blocks of one input
     if (slices > 16) return false;
@@ -739,26 +737,28 @@ bool rv_pointwise_plan(const TapConvArgs* a, bool scatter, int* grid, size_t* ld
     // one workgroup per CU; fewer steps than groups (crops in the tests): eight workgroups per row of `slices` x 8 ... keep the grid a multiple of 8 x slices
     int g = cus;
     if (steps < groups) g = 8 * slices * (int)((steps + 7) / 8);
-    *grid = g;
-    *stats_rows = pair ? 2 * g : g;
-    *lds = (size_t)2 * Pos<256>::kBuf;
+    p->gen = 7;
+    p->pair = pair ? 1 : 0;
+    p->slices = slices;  // (1: also the paired 128 -> 128 form)
+    p->grid_x = g;
+    p->stats_rows = pair ? 2 * g : g;
+    p->lds = (size_t)2 * Pos<256>::kBuf;
+    p->info[0] = 7, p->info[1] = a->C_dst, p->info[2] = g, p->info[3] = slices;
     return true;
 }
 
-int rv_pointwise_launch(const TapConvArgs& a, int grid, size_t lds, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)pointwise_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<256>::kBuf);
-        attr_set = true;
-    }
+int rv_pointwise_launch(const TapPlan& plan, hipStream_t stream) {
+    const TapConvArgs& a = plan.args;
+    const int grid = plan.grid_x;
     PwArgs p{};
     p.x = a.src, p.w = a.w, p.y = (bf16_t*)a.dst, p.partial = (a.flags & RV_OUT_STATS) ? a.stats : nullptr;
     p.P = (int64_t)a.N * a.H * a.W_src, p.ld_x = a.ld_src, p.ld_y = a.ld_dst;
-    p.pair = pointwise_pair(&a) ? 1 : 0;
+    p.pair = plan.pair;
     if (p.pair) p.P /= 2, p.ld_x = 256, p.ld_y = 256;
-    p.slices = p.pair ? 1 : a.C_dst / 256;
+    p.slices = plan.slices;
     RV_REQUIRE((p.pair || a.C_src == 256) && grid % 8 == 0 && (grid / 8) / p.slices >= 1, "pointwise kernel: 256 input channels (or paired 128), grid a multiple of 8 with room for a group per XCD");
-    hipLaunchKernelGGL(pointwise_kernel<256>, dim3(grid), dim3(512), lds, stream, p);
+    RV_LDS_OPT_IN(2 * Pos<256>::kBuf, pointwise_kernel<256>);
+    hipLaunchKernelGGL(pointwise_kernel<256>, dim3(grid), dim3(512), plan.lds, stream, p);
     RV_CHECK_LAUNCH("pointwise_kernel");
     return 0;
 }
@@ -769,12 +769,8 @@ int rv_pos_bwd_launch(int64_t pixels, const void* dy2, const void* w2_scatter, c
                       const float* invstd1, float* partial, int32_t planes, int32_t max_rows, int32_t* rows, int32_t c, hipStream_t stream) {
     RV_REQUIRE(c == 256 || c == 128, "rv_pos_backward_sums: built for 256 or 128 channels (got %d)", c);
     const int lds = c == 256 ? 2 * Pos<256>::kBuf + 2 * Pos<256>::kTM * 8 : 2 * Pos<128>::kBuf + 2 * Pos<128>::kTM * 8;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)pos_bwd_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<256>::kBuf + 2 * Pos<256>::kTM * 8);
-        (void)hipFuncSetAttribute((const void*)pos_bwd_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<128>::kBuf + 2 * Pos<128>::kTM * 8);
-        attr_set = true;
-    }
+    if (c == 256) RV_LDS_OPT_IN(2 * Pos<256>::kBuf + 2 * Pos<256>::kTM * 8, pos_bwd_kernel<256>);
+    else RV_LDS_OPT_IN(2 * Pos<128>::kBuf + 2 * Pos<128>::kTM * 8, pos_bwd_kernel<128>);
     PosBwdArgs a{};
     a.dy2 = (const bf16_t*)dy2, a.w2s = (const bf16_t*)w2_scatter, a.rel = (const bf16_t*)rel, a.w1 = (const bf16_t*)w1_packed;
     a.scale1 = scale1, a.shift1 = shift1, a.mean1 = mean1, a.invstd1 = invstd1;
@@ -800,12 +796,8 @@ extern "C" int rv_pos_forward(const void* rel, int32_t ld_rel, int32_t cin, int6
     RV_REQUIRE(rel && w1_packed && scale1 && shift1 && w2_packed && h1 && y2, "rv_pos_forward: null argument");
     RV_REQUIRE(c == 256 || c == 128, "rv_pos_forward: built for 256 or 128 channels (got %d)", c);
     RV_REQUIRE(cin >= 1 && cin <= 3 && ld_rel >= 4 && ld_rel % 4 == 0 && pixels > 0, "rv_pos_forward: bad shape");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)pos_fwd_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<256>::kBuf);
-        (void)hipFuncSetAttribute((const void*)pos_fwd_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<128>::kBuf);
-        attr_set = true;
-    }
+    if (c == 256) RV_LDS_OPT_IN(2 * Pos<256>::kBuf, pos_fwd_kernel<256, false>);
+    else RV_LDS_OPT_IN(2 * Pos<128>::kBuf, pos_fwd_kernel<128, false>);
     PosFwdArgs a{};
     a.rel = (const bf16_t*)rel, a.w1 = (const bf16_t*)w1_packed, a.w2 = (const bf16_t*)w2_packed;
     a.scale1 = scale1, a.shift1 = shift1;
@@ -826,12 +818,8 @@ extern "C" int rv_pos_modulate_forward(const void* rel, int32_t ld_rel, int32_t 
     RV_REQUIRE(N > 0 && H > 0 && W >= 32 && ld_feat >= c && ld_feat % 8 == 0, "rv_pos_modulate_forward: W >= 32, feature rows of at least c channels");
     const int64_t pixels = (int64_t)N * H * W * 9;
     RV_REQUIRE(pixels < ((int64_t)1 << 31) - 512, "rv_pos_modulate_forward: 9 N H W must stay below 2^31");
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)pos_fwd_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<256>::kBuf);
-        (void)hipFuncSetAttribute((const void*)pos_fwd_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * Pos<128>::kBuf);
-        attr_set = true;
-    }
+    if (c == 256) RV_LDS_OPT_IN(2 * Pos<256>::kBuf, pos_fwd_kernel<256, true>);
+    else RV_LDS_OPT_IN(2 * Pos<128>::kBuf, pos_fwd_kernel<128, true>);
     PosFwdArgs a{};
     a.rel = (const bf16_t*)rel, a.w1 = (const bf16_t*)w1_packed, a.w2 = (const bf16_t*)w2_packed;
     a.scale1 = scale1, a.shift1 = shift1, a.scale2 = scale2, a.shift2 = shift2;

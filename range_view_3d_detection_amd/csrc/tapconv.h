@@ -52,27 +52,44 @@ struct TapConvArgs {
 // fills tt (except w_tile), *phases and *step; scatter == false: GATHER form, true: SCATTER form
 int rv_build_tap_table(const rvTapGeom* g, bool scatter, TapTable* tt, int* phases, int* step);
 
-// second-generation kernel (tapconv2.hip): plan returns false when the layer is not eligible
-bool rv_tapconv2_plan(TapConvArgs* a, int* grid_x, int* grid_y, size_t* lds, int* ks);
-int rv_tapconv2_launch(const TapConvArgs& a, int grid_x, int grid_y, size_t lds, int ks, hipStream_t stream);
+// Everything that is decided about a tap-conv launch before it runs and that no kernel reads: filled ONCE by tap_plan
+// (tapconv.hip), read by the planning entry points (rv_tap_stats_rows, rv_tap_launch_info, rv_tap_bnb_rows) and by the launch.
+struct TapPlan {
+    int gen;             // 1 = generic, 2, 4, 5, 6, 7 = pointwise; 0 = RV_OUT_BNB asked of a layer no kernel forms the sums for
+    int bn, ks;          // generations 4 / 5: channels per workgroup (256 / 128); generation 2: 32-channel K steps per chunk
+    int mt, nt;          // generation 1: block tile 32*mt pixels x 32*nt channels
+    int epi;             // generations 4 / 5 / 6: epilogue instance -- 0 plain, 1 BatchNorm-backward sums, 2 accumulate
+    int pair, slices;    // generation 7: 128 -> 128 as pixel pairs; 256-channel output slices per step group
+    int grid_x, grid_y;
+    size_t lds;          // dynamic LDS bytes
+    int stats_rows;      // rows of the RV_OUT_STATS partial buffer
+    int bnb_rows;        // rows of the RV_OUT_BNB partial sums (generations 5 / 6; 0: the caller takes the separate reduce pass)
+    int32_t info[4];     // rv_tap_launch_info
+    bool scatter;
+    TapConvArgs args;    // what the kernel receives: shape-derived fields set, pointers null until the launch fills them
+};
 
-// fourth-generation kernel (tapconv4.hip): 256 x 256 tiles, LDS-DMA staging, counted waits; *stats_rows = rows of the partial-statistics
-// buffer (2 per group of workgroups that share a pixel tile when the launch is persistent, else 2 per tile)
-bool rv_tapconv4_plan(TapConvArgs* a, int* tiles, size_t* lds, int* bn, int* stats_rows);
-int rv_tapconv4_launch(const TapConvArgs& a, size_t lds, int bn, hipStream_t stream);
-
-// fifth-generation kernel (tapconv5.hip): 256 x 256 tiles with the input halo of a channel chunk resident in LDS for all
-// taps (multi-tap layers); stats rows = 2 * tiles
-bool rv_tapconv5_plan(TapConvArgs* a, int* tiles, size_t* lds, int* bn);
-int rv_tapconv5_launch(const TapConvArgs& a, size_t lds, int bn, hipStream_t stream);
-
-// sixth-generation kernel (tapconv6.hip): 512-pixel x 128-channel tiles, 32-channel chunks, input halo resident in LDS across
-// the taps; *stats_rows = rows of the partial-statistics buffer (4 per group of workgroups that share a pixel tile when the
-// launch is persistent, else 4 per tile), *bnb_rows = rows of the BatchNorm-backward partial sums (one per such group, else per tile)
-bool rv_tapconv6_plan(TapConvArgs* a, int* tiles, size_t* lds, int* stats_rows, int* bnb_rows);
-int rv_tapconv6_launch(const TapConvArgs& a, size_t lds, hipStream_t stream);
-
+// One pair per kernel generation, tried by tap_plan in its order.  plan: p->args holds the shape (tap table, strides, flags, sel) and no
+// tile field yet; false = the layer is not eligible (the caller hands the next candidate a fresh copy), true = every field above
+// is set.  launch: grid, LDS size and variant come from the plan, pointers from p.args.  (A launcher names its kernel instances in a
+// fixed order: the order of first mention is the order of the kernels in the code object.)
+// second generation (tapconv2.hip): 2-row x 64-column tiles, 64-channel chunks; stats rows = 2 * grid.x
+bool rv_tapconv2_plan(TapPlan* p);
+int rv_tapconv2_launch(const TapPlan& p, hipStream_t stream);
+// fourth generation (tapconv4.hip): 256 x 256 tiles, LDS-DMA staging, counted waits; stats rows = 2 per group of workgroups that
+// share a pixel tile when the launch is persistent, else 2 per tile
+bool rv_tapconv4_plan(TapPlan* p);
+int rv_tapconv4_launch(const TapPlan& p, hipStream_t stream);
+// fifth generation (tapconv5.hip): 256 x 256 tiles with the input halo of a channel chunk resident in LDS for all taps (multi-tap
+// layers); stats rows = 2 * tiles, BatchNorm-backward rows = tiles
+bool rv_tapconv5_plan(TapPlan* p);
+int rv_tapconv5_launch(const TapPlan& p, hipStream_t stream);
+// sixth generation (tapconv6.hip): 512-pixel x 128-channel tiles, 32-channel chunks, input halo resident in LDS across the taps;
+// stats rows = 4 per group of workgroups that share a pixel tile when the launch is persistent, else 4 per tile; BatchNorm-backward
+// rows = one per such group, else per tile
+bool rv_tapconv6_plan(TapPlan* p);
+int rv_tapconv6_launch(const TapPlan& p, hipStream_t stream);
 // pointwise streaming GEMM (posconv.hip): 1x1 stride-1 layers C -> C (C = 256 / 128) on plain bf16 tensors, weights in registers,
 // pixels streamed through LDS; stats rows = one (sum, sum of squares) pair per workgroup (two for the paired 128 -> 128 form)
-bool rv_pointwise_plan(const TapConvArgs* a, bool scatter, int* grid, size_t* lds, int* stats_rows);
-int rv_pointwise_launch(const TapConvArgs& a, int grid, size_t lds, hipStream_t stream);
+bool rv_pointwise_plan(TapPlan* p);
+int rv_pointwise_launch(const TapPlan& p, hipStream_t stream);

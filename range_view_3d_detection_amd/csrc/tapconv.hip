@@ -315,13 +315,9 @@ __global__ __launch_bounds__(256, 2) void tapconv_kernel(const TapConvArgs a) {
 }
 
 template <int MT, int NT>
-int launch(const TapConvArgs& a, int grid_x, int grid_y, size_t lds, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)tapconv_kernel<MT, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    hipLaunchKernelGGL((tapconv_kernel<MT, NT>), dim3(grid_x, grid_y), dim3(256), lds, stream, a);
+int launch(const TapPlan& p, hipStream_t stream) {
+    RV_LDS_OPT_IN(160 * 1024, tapconv_kernel<MT, NT>);
+    hipLaunchKernelGGL((tapconv_kernel<MT, NT>), dim3(p.grid_x, p.grid_y), dim3(256), p.lds, stream, p.args);
     RV_CHECK_LAUNCH("tapconv_kernel");
     return 0;
 }
@@ -391,14 +387,57 @@ int rv_build_tap_table(const rvTapGeom* g, bool scatter, TapTable* tt, int* phas
     return 0;
 }
 
-static int tap_launch(const rvTapGeom* g, const rvTapShape* s, bool scatter, const void* src, const float* in_scale,
-                      const float* in_shift, const void* w, const float* bias, void* dst, float* stats,
-                      rvStream stream, bool dry_run, int* stats_rows, int* info = nullptr, const rvBnbEpilogue* bnb = nullptr,
-                      int* bnb_rows = nullptr, const void* residual = nullptr, int32_t ld_res = 0) {
-    TapConvArgs a;
-    memset(&a, 0, sizeof(a));
-    int phases, step;
-    if (rv_build_tap_table(g, scatter, &a.tt, &phases, &step)) return 1;
+// generic kernel: the last candidate takes every layer whose halo tile fits (a status, not "not eligible": nothing comes after it).
+// Tile selection: keep the LDS halo small for strided gathers; narrow N tile for thin outputs
+static int tapconv1_plan(TapPlan* p) {
+    TapConvArgs& a = p->args;
+    int mt = (a.step == 1) ? 4 : (a.step == 2 ? 2 : 1);
+    const int wm_total = a.W_dst / a.phases;
+    while (mt > 1 && 32 * mt / 2 >= wm_total) mt >>= 1;  // tiny images (tests)
+    const int nt = a.C_dst >= 128 ? 4 : (a.C_dst >= 64 ? 2 : 1);
+    const int BM = 32 * mt, BN = 32 * nt;
+    int a_elems = 0;
+    for (int r = 0; r < a.phases; ++r) {
+        a.tt.w_tile[r] = (BM - 1) * a.step + (a.tt.dw_max[r] - a.tt.dw_min[r]) + 1;
+        const int e = a.tt.rows * a.tt.w_tile[r] * kPix;
+        a_elems = a_elems > e ? a_elems : e;
+        RV_REQUIRE(a.tt.rows * a.tt.w_tile[r] * 4 <= 256 * kNaMax, "tap conv: halo tile too large (%d x %d)", a.tt.rows, a.tt.w_tile[r]);
+    }
+    a.lds_a_elems = a_elems;
+    size_t lds = (size_t)(a_elems + 2 * BN * kPix) * sizeof(bf16_t);
+    const size_t epi = (size_t)BM * (BN + 8) * sizeof(bf16_t);
+    if (lds < epi) lds = epi;
+    lds = (lds + 15) & ~(size_t)15;
+    a.lds_tab_offset = (int32_t)lds;
+    a.m_tiles = rv_ceil_div(wm_total, BM);
+    p->gen = 1;
+    p->mt = mt;
+    p->nt = nt;
+    p->lds = lds + 128;
+    p->grid_x = a.m_tiles * a.H * a.N * a.phases;
+    p->grid_y = rv_ceil_div(a.C_dst, BN);
+    p->stats_rows = p->grid_x * 2;
+    p->info[0] = 1, p->info[1] = mt * 16 + nt, p->info[2] = p->grid_x, p->info[3] = p->grid_y;
+    return 0;
+}
+
+static int tapconv1_launch(const TapPlan& p, hipStream_t stream) {
+#define RV_CASE(M, Nn) \
+    if (p.mt == M && p.nt == Nn) return launch<M, Nn>(p, stream);
+    RV_CASE(4, 4) RV_CASE(4, 2) RV_CASE(4, 1) RV_CASE(2, 4) RV_CASE(2, 2) RV_CASE(2, 1) RV_CASE(1, 4) RV_CASE(1, 2) RV_CASE(1, 1)
+#undef RV_CASE
+    RV_FAIL("tap conv: no kernel for tile %dx%d", p.mt, p.nt);
+}
+
+// Shape validation, tap table and kernel selection of one tap op: everything that needs no pointer.  want_bnb: the launch also forms
+// the BatchNorm-backward sums of its destination layer (rv_tap_data_grad_bnb); has_residual: it adds a residual of channel stride
+// ld_res (rv_tap_residual).
+static int tap_plan(const rvTapGeom* g, const rvTapShape* s, bool scatter, bool want_bnb, bool has_residual, int32_t ld_res, TapPlan* out) {
+    TapPlan base;
+    memset(&base, 0, sizeof(base));
+    base.scatter = scatter;
+    TapConvArgs& a = base.args;
+    if (rv_build_tap_table(g, scatter, &a.tt, &a.phases, &a.step)) return 1;
     RV_REQUIRE(s->Wv == s->Wu * g->stride_w, "tap shape: Wv (%d) must equal Wu (%d) * stride_w (%d)", s->Wv, s->Wu, g->stride_w);
     RV_REQUIRE(s->N > 0 && s->H > 0 && s->Wu > 0, "tap shape: empty tensor");
     const int cu = rv_pad32(g->cu), cv = rv_pad32(g->cv);
@@ -413,25 +452,50 @@ static int tap_launch(const rvTapGeom* g, const rvTapShape* s, bool scatter, con
     RV_REQUIRE(a.ld_src >= a.C_src && a.ld_dst >= a.C_dst, "tap shape: channel strides (%d,%d) smaller than padded channels (%d,%d)",
                a.ld_src, a.ld_dst, a.C_src, a.C_dst);
     RV_REQUIRE(a.ld_src % 8 == 0 && a.ld_dst % 8 == 0, "tap shape: channel strides must be multiples of 8");
-    a.phases = phases;
-    a.step = step;
     a.flags = s->flags & ~RV_SEL_MASK;
     a.sel = s->flags & RV_SEL_MASK;  // per-call kernel-selection hints (tests pin a generation / lift the tile-count heuristics)
-    a.res = (const bf16_t*)dst;  // RV_OUT_ACCUM adds into dst ...
-    a.ld_res = a.ld_dst;
-    if (residual) {  // ... rv_tap_residual adds another tensor of the same pixels
+    a.ld_res = a.ld_dst;             // RV_OUT_ACCUM adds into dst ...
+    if (has_residual) {              // ... rv_tap_residual adds another tensor of the same pixels
         RV_REQUIRE(!(a.flags & (RV_OUT_ACCUM | RV_OUT_STATS)), "rv_tap_residual: not together with RV_OUT_ACCUM / RV_OUT_STATS");
         RV_REQUIRE(ld_res >= a.C_dst && ld_res % 8 == 0, "rv_tap_residual: bad channel stride of the residual (%d)", ld_res);
         a.flags |= RV_OUT_ACCUM;
-        a.res = (const bf16_t*)residual;
         a.ld_res = ld_res;
-    } else {
-        RV_REQUIRE(dry_run || !(a.flags & RV_OUT_RES_RELU), "RV_OUT_RES_RELU belongs to rv_tap_residual");
     }
     RV_REQUIRE(!((a.flags & RV_OUT_F32) && (a.flags & RV_OUT_ACCUM)), "RV_OUT_ACCUM needs a bf16 destination");
-    RV_REQUIRE(dry_run || !(a.flags & RV_IN_AFFINE) || (in_scale && in_shift), "RV_IN_AFFINE without scale/shift");
-    RV_REQUIRE(dry_run || !(a.flags & RV_OUT_BIAS) || bias, "RV_OUT_BIAS without bias");
-    RV_REQUIRE(!(a.flags & RV_OUT_STATS) || stats || dry_run, "RV_OUT_STATS without a partial buffer");
+    if (want_bnb) a.flags |= RV_OUT_BNB;
+
+    // the candidates in order of preference; each works on its own copy of the shape (a rejected plan leaves nothing behind)
+    const auto take = [&](bool (*plan)(TapPlan*)) {
+        *out = base;
+        return plan(out);
+    };
+    // multi-tap layers with at least one round of 512-pixel x 128-channel tiles (tapconv6.hip)
+    if (!(a.sel & (RV_SEL_NO_GEN6 | RV_SEL_NO_GEN5)) && take(rv_tapconv6_plan)) return 0;
+    // multi-tap layers with 256-channel output tiles: input halo resident in LDS across the taps (tapconv5.hip)
+    if (!(a.sel & RV_SEL_NO_GEN5) && take(rv_tapconv5_plan)) return 0;
+    if (a.flags & RV_OUT_BNB) {  // only those two carry that epilogue: gen 0, bnb_rows 0 (the caller takes the separate reduce pass)
+        *out = base;
+        return 0;
+    }
+    // 1x1 stride-1 C -> C layers on plain tensors: the persistent streaming GEMM with the weights in registers (posconv.hip)
+    if (take(rv_pointwise_plan)) return 0;
+    // 256 x 256 (or x 128) tiles streamed by LDS-DMA, counted waits (tapconv4.hip); plain bf16 inputs only
+    if (take(rv_tapconv4_plan)) return 0;
+    // fast path: 2-row x 64-column tiles, 64-channel chunks (tapconv2.hip)
+    if (take(rv_tapconv2_plan)) return 0;
+    *out = base;
+    return tapconv1_plan(out);
+}
+
+// The launch of a plan: the checks that need the pointers, the pointer fields of the kernel arguments, the generation's launcher.
+static int tap_run(const TapPlan& plan, const void* src, const float* in_scale, const float* in_shift, const void* w, const float* bias,
+                   void* dst, float* stats, const rvBnbEpilogue* bnb, const void* residual, rvStream stream) {
+    TapPlan p = plan;
+    TapConvArgs& a = p.args;
+    RV_REQUIRE(residual || !(a.flags & RV_OUT_RES_RELU), "RV_OUT_RES_RELU belongs to rv_tap_residual");
+    RV_REQUIRE(!(a.flags & RV_IN_AFFINE) || (in_scale && in_shift), "RV_IN_AFFINE without scale/shift");
+    RV_REQUIRE(!(a.flags & RV_OUT_BIAS) || bias, "RV_OUT_BIAS without bias");
+    RV_REQUIRE(!(a.flags & RV_OUT_STATS) || stats, "RV_OUT_STATS without a partial buffer");
     a.src = (const bf16_t*)src;
     a.dst = dst;
     a.w = (const bf16_t*)w;
@@ -439,195 +503,82 @@ static int tap_launch(const rvTapGeom* g, const rvTapShape* s, bool scatter, con
     a.in_shift = in_shift;
     a.bias = bias;
     a.stats = stats;
-    if (bnb_rows) *bnb_rows = 0;
-    if (bnb || bnb_rows) {  // backward-data launch that also forms the BatchNorm-backward sums of its destination layer
-        a.flags |= RV_OUT_BNB;
-        if (bnb) {
-            RV_REQUIRE(bnb->y && bnb->scale && bnb->shift && bnb->mean && bnb->invstd && bnb->partial, "rv_tap_data_grad_bnb: null epilogue pointer");
-            RV_REQUIRE(bnb->ld_y >= a.C_dst && bnb->ld_y % 8 == 0, "rv_tap_data_grad_bnb: bad channel stride of y (%d)", bnb->ld_y);
-            a.bnb_y = (const bf16_t*)bnb->y;
-            a.ld_bnb_y = bnb->ld_y;
-            a.bnb_flags = bnb->flags;
-            a.bnb_scale = bnb->scale;
-            a.bnb_shift = bnb->shift;
-            a.bnb_mean = bnb->mean;
-            a.bnb_invstd = bnb->invstd;
-            a.bnb_partial = bnb->partial;
-        }
+    a.res = (const bf16_t*)(residual ? residual : dst);
+    if (bnb) {
+        RV_REQUIRE(bnb->y && bnb->scale && bnb->shift && bnb->mean && bnb->invstd && bnb->partial, "rv_tap_data_grad_bnb: null epilogue pointer");
+        RV_REQUIRE(bnb->ld_y >= a.C_dst && bnb->ld_y % 8 == 0, "rv_tap_data_grad_bnb: bad channel stride of y (%d)", bnb->ld_y);
+        a.bnb_y = (const bf16_t*)bnb->y;
+        a.ld_bnb_y = bnb->ld_y;
+        a.bnb_flags = bnb->flags;
+        a.bnb_scale = bnb->scale;
+        a.bnb_shift = bnb->shift;
+        a.bnb_mean = bnb->mean;
+        a.bnb_invstd = bnb->invstd;
+        a.bnb_partial = bnb->partial;
     }
-
-    // multi-tap layers with at least one round of 512-pixel x 128-channel tiles (tapconv6.hip)
-    if (!(a.sel & (RV_SEL_NO_GEN6 | RV_SEL_NO_GEN5))) {
-        int tiles, srows, brows;
-        size_t lds6;
-        TapConvArgs a6 = a;
-        if (rv_tapconv6_plan(&a6, &tiles, &lds6, &srows, &brows)) {
-            if (stats_rows) *stats_rows = srows;
-            if (bnb_rows) *bnb_rows = brows;
-            if (info) {
-                info[0] = 6;
-                info[1] = 128;
-                info[2] = tiles;
-                info[3] = a6.n_tiles;
-            }
-            if (dry_run) return 0;
-            return rv_tapconv6_launch(a6, lds6, (hipStream_t)stream);
-        }
-    }
-    // multi-tap layers with 256-channel output tiles: input halo resident in LDS across the taps (tapconv5.hip)
-    if (!(a.sel & RV_SEL_NO_GEN5)) {
-        int tiles, bn5;
-        size_t lds5;
-        TapConvArgs a5 = a;
-        if (rv_tapconv5_plan(&a5, &tiles, &lds5, &bn5)) {
-            if (stats_rows) *stats_rows = tiles * 2;
-            if (bnb_rows) *bnb_rows = tiles;
-            if (info) {
-                info[0] = 5;
-                info[1] = bn5;
-                info[2] = tiles;
-                info[3] = a5.n_tiles;
-            }
-            if (dry_run) return 0;
-            return rv_tapconv5_launch(a5, lds5, bn5, (hipStream_t)stream);
-        }
-    }
-    if (a.flags & RV_OUT_BNB) {  // only the fifth-generation kernel carries that epilogue
-        if (dry_run) return 0;   // (rows = 0: the caller takes the separate reduce pass)
-        RV_FAIL("rv_tap_data_grad_bnb: this launch has no fused BatchNorm-backward sums (rv_tap_bnb_rows returned 0)");
-    }
-    // 1x1 stride-1 C -> C layers on plain tensors: the persistent streaming GEMM with the weights in registers (posconv.hip, round 6)
-    {
-        int grid7, rows7;
-        size_t lds7;
-        if (rv_pointwise_plan(&a, scatter, &grid7, &lds7, &rows7)) {
-            if (stats_rows) *stats_rows = rows7;
-            if (info) {
-                info[0] = 7;
-                info[1] = a.C_dst;
-                info[2] = grid7;
-                info[3] = a.C_dst / a.C_src;  // 256-channel output slices per step group (1: also the paired 128 -> 128 form)
-            }
-            if (dry_run) return 0;
-            return rv_pointwise_launch(a, grid7, lds7, (hipStream_t)stream);
-        }
-    }
-    // 256 x 256 (or x 128) tiles streamed by LDS-DMA, counted waits (tapconv4.hip); plain bf16 inputs only
-    {
-        int tiles, bn, srows;
-        size_t lds4;
-        TapConvArgs a4 = a;
-        if (rv_tapconv4_plan(&a4, &tiles, &lds4, &bn, &srows)) {
-            if (stats_rows) *stats_rows = srows;
-            if (info) {
-                info[0] = 4;
-                info[1] = bn;
-                info[2] = tiles;
-                info[3] = a4.n_tiles;
-            }
-            if (dry_run) return 0;
-            return rv_tapconv4_launch(a4, lds4, bn, (hipStream_t)stream);
-        }
-    }
-    // fast path: 2-row x 64-column tiles, 64-channel chunks (tapconv2.hip)
-    {
-        int gx, gy, ks;
-        size_t lds2;
-        if (rv_tapconv2_plan(&a, &gx, &gy, &lds2, &ks)) {
-            if (stats_rows) *stats_rows = gx * 2;
-            if (info) {
-                info[0] = 2;
-                info[1] = ks;
-                info[2] = gx;
-                info[3] = gy;
-            }
-            if (dry_run) return 0;
-            return rv_tapconv2_launch(a, gx, gy, lds2, ks, (hipStream_t)stream);
-        }
-    }
-    // generic path -- tile selection: keep the LDS halo small for strided gathers; narrow N tile for thin outputs
-    int mt = (step == 1) ? 4 : (step == 2 ? 2 : 1);
-    const int wm_total = a.W_dst / phases;
-    while (mt > 1 && 32 * mt / 2 >= wm_total) mt >>= 1;  // tiny images (tests)
-    int nt = a.C_dst >= 128 ? 4 : (a.C_dst >= 64 ? 2 : 1);
-    const int BM = 32 * mt, BN = 32 * nt;
-    int a_elems = 0;
-    for (int r = 0; r < phases; ++r) {
-        a.tt.w_tile[r] = (BM - 1) * step + (a.tt.dw_max[r] - a.tt.dw_min[r]) + 1;
-        const int e = a.tt.rows * a.tt.w_tile[r] * kPix;
-        a_elems = a_elems > e ? a_elems : e;
-        RV_REQUIRE(a.tt.rows * a.tt.w_tile[r] * 4 <= 256 * kNaMax, "tap conv: halo tile too large (%d x %d)", a.tt.rows, a.tt.w_tile[r]);
-    }
-    a.lds_a_elems = a_elems;
-    size_t lds = (size_t)(a_elems + 2 * BN * kPix) * sizeof(bf16_t);
-    const size_t epi = (size_t)BM * (BN + 8) * sizeof(bf16_t);
-    if (lds < epi) lds = epi;
-    lds = (lds + 15) & ~(size_t)15;
-    a.lds_tab_offset = (int32_t)lds;
-    lds += 128;
-    a.m_tiles = rv_ceil_div(wm_total, BM);
-    const int grid_x = a.m_tiles * a.H * a.N * phases;
-    const int grid_y = rv_ceil_div(a.C_dst, BN);
-    if (stats_rows) *stats_rows = grid_x * 2;
-    if (info) {
-        info[0] = 1;
-        info[1] = mt * 16 + nt;
-        info[2] = grid_x;
-        info[3] = grid_y;
-    }
-    if (dry_run) return 0;
     hipStream_t st = (hipStream_t)stream;
-#define RV_CASE(M, Nn) \
-    if (mt == M && nt == Nn) return launch<M, Nn>(a, grid_x, grid_y, lds, st);
-    RV_CASE(4, 4) RV_CASE(4, 2) RV_CASE(4, 1) RV_CASE(2, 4) RV_CASE(2, 2) RV_CASE(2, 1) RV_CASE(1, 4) RV_CASE(1, 2) RV_CASE(1, 1)
-#undef RV_CASE
-    RV_FAIL("tap conv: no kernel for tile %dx%d", mt, nt);
+    switch (p.gen) {
+        case 6: return rv_tapconv6_launch(p, st);
+        case 5: return rv_tapconv5_launch(p, st);
+        case 7: return rv_pointwise_launch(p, st);
+        case 4: return rv_tapconv4_launch(p, st);
+        case 2: return rv_tapconv2_launch(p, st);
+        case 1: return tapconv1_launch(p, st);
+    }
+    RV_FAIL("rv_tap_data_grad_bnb: this launch has no fused BatchNorm-backward sums (rv_tap_bnb_rows returned 0)");
 }
 
 extern "C" {
 
 int32_t rv_tap_stats_rows(const rvTapGeom* g, const rvTapShape* s, int32_t scatter) {
-    int rows = 0;
-    if (tap_launch(g, s, scatter != 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, &rows)) return -1;
-    return rows;
+    TapPlan p;
+    return tap_plan(g, s, scatter != 0, false, false, 0, &p) ? -1 : p.stats_rows;
 }
 
 int rv_tap_launch_info(const rvTapGeom* g, const rvTapShape* s, int32_t scatter, int32_t* host_info) {
     RV_REQUIRE(g && s && host_info, "rv_tap_launch_info: null argument");
-    return tap_launch(g, s, scatter != 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, nullptr, host_info);
+    TapPlan p;
+    if (tap_plan(g, s, scatter != 0, false, false, 0, &p)) return 1;
+    memcpy(host_info, p.info, sizeof(p.info));
+    return 0;
 }
 
 int32_t rv_tap_bnb_rows(const rvTapGeom* g, const rvTapShape* s, int32_t scatter) {
-    int rows = 0;
     if (!g || !s) return 0;
-    if (tap_launch(g, s, scatter != 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, nullptr, nullptr, nullptr, &rows))
-        return -1;
-    return rows;
+    TapPlan p;
+    return tap_plan(g, s, scatter != 0, true, false, 0, &p) ? -1 : p.bnb_rows;
 }
 
 int rv_tap_data_grad_bnb(const rvTapGeom* g, const rvTapShape* s, int32_t scatter, const void* dout, const void* w, void* dx,
                          const rvBnbEpilogue* e, rvStream stream) {
     RV_REQUIRE(g && s && dout && w && dx && e, "rv_tap_data_grad_bnb: null argument");
-    return tap_launch(g, s, scatter != 0, dout, nullptr, nullptr, w, nullptr, dx, nullptr, stream, false, nullptr, nullptr, e);
+    TapPlan p;
+    if (tap_plan(g, s, scatter != 0, true, false, 0, &p)) return 1;
+    return tap_run(p, dout, nullptr, nullptr, w, nullptr, dx, nullptr, e, nullptr, stream);
 }
 
 int rv_tap_residual(const rvTapGeom* g, const rvTapShape* s, int32_t scatter, const void* src, const void* w, const float* bias,
                     const void* res, int32_t ld_res, void* dst, rvStream stream) {
     RV_REQUIRE(g && s && src && w && res && dst, "rv_tap_residual: null argument");
-    return tap_launch(g, s, scatter != 0, src, nullptr, nullptr, w, bias, dst, nullptr, stream, false, nullptr, nullptr, nullptr, nullptr, res,
-                      ld_res);
+    TapPlan p;
+    if (tap_plan(g, s, scatter != 0, false, true, ld_res, &p)) return 1;
+    return tap_run(p, src, nullptr, nullptr, w, bias, dst, nullptr, nullptr, res, stream);
 }
 
 int rv_tap_gather(const rvTapGeom* g, const rvTapShape* s, const void* V, const float* in_scale, const float* in_shift,
                   const void* gather_w, const float* bias, void* U, float* stats_partial, rvStream stream) {
     RV_REQUIRE(g && s && V && gather_w && U, "rv_tap_gather: null argument");
-    return tap_launch(g, s, false, V, in_scale, in_shift, gather_w, bias, U, stats_partial, stream, false, nullptr);
+    TapPlan p;
+    if (tap_plan(g, s, false, false, false, 0, &p)) return 1;
+    return tap_run(p, V, in_scale, in_shift, gather_w, bias, U, stats_partial, nullptr, nullptr, stream);
 }
 
 int rv_tap_scatter(const rvTapGeom* g, const rvTapShape* s, const void* U, const float* in_scale, const float* in_shift,
                    const void* scatter_w, const float* bias, void* V, float* stats_partial, rvStream stream) {
     RV_REQUIRE(g && s && U && scatter_w && V, "rv_tap_scatter: null argument");
-    return tap_launch(g, s, true, U, in_scale, in_shift, scatter_w, bias, V, stats_partial, stream, false, nullptr);
+    TapPlan p;
+    if (tap_plan(g, s, true, false, false, 0, &p)) return 1;
+    return tap_run(p, U, in_scale, in_shift, scatter_w, bias, V, stats_partial, nullptr, nullptr, stream);
 }
 
 }  // extern "C"

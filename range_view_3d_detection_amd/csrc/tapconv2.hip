@@ -344,7 +344,8 @@ __global__ __launch_bounds__(256, 2) void tapconv2_kernel(const TapConvArgs a) {
 }  // namespace
 
 // returns false when the layer is not eligible (caller falls back to tapconv_kernel)
-bool rv_tapconv2_plan(TapConvArgs* a, int* grid_x, int* grid_y, size_t* lds, int* ks) {
+bool rv_tapconv2_plan(TapPlan* p) {
+    TapConvArgs* a = &p->args;
     if (a->step != 1) return false;
     const int wm_total = a->W_dst / a->phases;
     if (wm_total < kTC || a->C_dst < 64 || a->H < 2) return false;
@@ -375,22 +376,22 @@ bool rv_tapconv2_plan(TapConvArgs* a, int* grid_x, int* grid_y, size_t* lds, int
     if (bytes > 80 * 1024) return false;  // keep two workgroups per CU
     a->m_tiles = rv_ceil_div(wm_total, kTC);
     a->h_tiles = rv_ceil_div(a->H, kTR);
-    *grid_x = a->m_tiles * a->h_tiles * a->N * a->phases;
-    *grid_y = rv_ceil_div(a->C_dst, kBN);
-    *lds = bytes;
-    *ks = KS;
+    p->gen = 2;
+    p->ks = KS;
+    p->grid_x = a->m_tiles * a->h_tiles * a->N * a->phases;
+    p->grid_y = rv_ceil_div(a->C_dst, kBN);
+    p->lds = bytes;
+    p->stats_rows = p->grid_x * 2;
+    p->info[0] = 2, p->info[1] = KS, p->info[2] = p->grid_x, p->info[3] = p->grid_y;
     return true;
 }
 
-int rv_tapconv2_launch(const TapConvArgs& a, int grid_x, int grid_y, size_t lds, int ks, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)tapconv2_kernel<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv2_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    if (ks == 2) hipLaunchKernelGGL((tapconv2_kernel<2, true>), dim3(grid_x, grid_y), dim3(256), lds, stream, a);  // (weights by LDS-DMA)
-    else hipLaunchKernelGGL((tapconv2_kernel<1, true>), dim3(grid_x, grid_y), dim3(256), lds, stream, a);
+template <int KS>
+static int launch2(const TapPlan& p, hipStream_t stream) {
+    RV_LDS_OPT_IN(160 * 1024, tapconv2_kernel<KS, true>);
+    hipLaunchKernelGGL((tapconv2_kernel<KS, true>), dim3(p.grid_x, p.grid_y), dim3(256), p.lds, stream, p.args);  // (weights by LDS-DMA)
     RV_CHECK_LAUNCH("tapconv2_kernel");
     return 0;
 }
+
+int rv_tapconv2_launch(const TapPlan& p, hipStream_t stream) { return p.ks == 1 ? launch2<1>(p, stream) : launch2<2>(p, stream); }

@@ -419,13 +419,8 @@ __global__ __launch_bounds__(512, 2) void tapconv4_kernel(const TapConvArgs a) {
 // it so that the parity tests run the production kernels on crops the CPU oracle can afford.
 
 // returns false when the layer is not eligible (caller falls back to tapconv2 / the generic kernel)
-static int tapconv4_grid(const TapConvArgs& a) {
-    int grid = 8 * a.tiles_per_xcd * a.n_tiles;
-    if (grid > rv_cu_count()) grid = rv_persistent_grid();  // persistent: one workgroup per CU
-    return grid;
-}
-
-bool rv_tapconv4_plan(TapConvArgs* a, int* tiles, size_t* lds, int* bn, int* stats_rows) {
+bool rv_tapconv4_plan(TapPlan* p) {
+    TapConvArgs* a = &p->args;
     if (a->step != 1) return false;
     if (a->flags & (RV_IN_AFFINE | RV_IN_RELU | RV_OUT_F32)) return false;  // the DMA path has no register prologue
     if (a->C_src % kBK != 0 || a->C_dst % 128 != 0) return false;
@@ -441,35 +436,31 @@ bool rv_tapconv4_plan(TapConvArgs* a, int* tiles, size_t* lds, int* bn, int* sta
     a->n_tiles = a->C_dst / BN;
     a->tiles_per_xcd = rv_ceil_div(a->total_tiles, 8);
     if ((int64_t)a->total_tiles * a->n_tiles < ((a->sel & RV_SEL_SMALL_GRIDS) ? 1 : rv_cu_count())) return false;  // too few tiles to fill the chip
-    *tiles = a->total_tiles;
-    *bn = BN;
-    const int grid = tapconv4_grid(*a), nslots = grid / 8;
+    int grid = 8 * a->tiles_per_xcd * a->n_tiles;
+    if (grid > rv_cu_count()) grid = rv_persistent_grid();  // persistent: one workgroup per CU
+    const int nslots = grid / 8;
     a->stats_per_wg = (grid < 8 * a->tiles_per_xcd * a->n_tiles && nslots % a->n_tiles == 0) ? 1 : 0;  // persistent, channel tile fixed per workgroup
-    *stats_rows = a->stats_per_wg ? (grid / a->n_tiles) * 2 : a->total_tiles * 2;
-    *lds = (size_t)stat_acc_offset(BN) + 8 * 4 * 16 * 2 * sizeof(float);
+    p->gen = 4;
+    p->bn = BN;
+    p->epi = (a->flags & RV_OUT_ACCUM) ? 2 : 0;
+    p->grid_x = grid;
+    p->stats_rows = a->stats_per_wg ? (grid / a->n_tiles) * 2 : a->total_tiles * 2;
+    p->lds = (size_t)stat_acc_offset(BN) + 8 * 4 * 16 * 2 * sizeof(float);
     const size_t epi = (size_t)kTR * kTC * (BN + 8) * sizeof(bf16_t);
-    if (*lds < epi) *lds = epi;
+    if (p->lds < epi) p->lds = epi;
+    p->info[0] = 4, p->info[1] = BN, p->info[2] = a->total_tiles, p->info[3] = a->n_tiles;
     return true;
 }
 
-int rv_tapconv4_launch(const TapConvArgs& a, size_t lds, int bn, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)tapconv4_kernel<256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv4_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv4_kernel<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv4_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    const int grid = tapconv4_grid(a);
-    const bool acc = (a.flags & RV_OUT_ACCUM) != 0;
-    if (bn == 256) {
-        if (acc) hipLaunchKernelGGL((tapconv4_kernel<256, true>), dim3(grid), dim3(512), lds, stream, a);
-        else hipLaunchKernelGGL((tapconv4_kernel<256, false>), dim3(grid), dim3(512), lds, stream, a);
-    } else {
-        if (acc) hipLaunchKernelGGL((tapconv4_kernel<128, true>), dim3(grid), dim3(512), lds, stream, a);
-        else hipLaunchKernelGGL((tapconv4_kernel<128, false>), dim3(grid), dim3(512), lds, stream, a);
-    }
+template <int BN, bool ACC>
+static int launch4(const TapPlan& p, hipStream_t stream) {
+    RV_LDS_OPT_IN(160 * 1024, tapconv4_kernel<BN, ACC>);
+    hipLaunchKernelGGL((tapconv4_kernel<BN, ACC>), dim3(p.grid_x), dim3(512), p.lds, stream, p.args);
     RV_CHECK_LAUNCH("tapconv4_kernel");
     return 0;
+}
+
+int rv_tapconv4_launch(const TapPlan& p, hipStream_t stream) {
+    if (p.epi == 0) return p.bn == 256 ? launch4<256, false>(p, stream) : launch4<128, false>(p, stream);
+    return p.bn == 256 ? launch4<256, true>(p, stream) : launch4<128, true>(p, stream);
 }

@@ -540,14 +540,14 @@ __global__ __launch_bounds__(512, 2) void tapconv5_kernel(const TapConvArgs a) {
 
 
 // returns false when the layer is not eligible (caller falls back to tapconv4 / tapconv3 / ...)
-bool rv_tapconv5_plan(TapConvArgs* a, int* tiles, size_t* lds, int* bn) {
+bool rv_tapconv5_plan(TapPlan* p) {
+    TapConvArgs* a = &p->args;
     if (a->step != 1) return false;
     if (a->flags & (RV_IN_AFFINE | RV_IN_RELU | RV_OUT_F32)) return false;  // the DMA path has no register prologue
     if ((a->flags & RV_OUT_BNB) && (a->flags & RV_OUT_ACCUM)) return false;  // (sums over an ACCUMULATED gradient: not formed in an epilogue)
     if (a->C_src % kBK != 0 || a->C_dst % 128 != 0) return false;
     const int kBN = a->C_dst % 256 == 0 ? 256 : 128;  // narrow layers: 128-channel tiles, one weight piece per K tile
     const int min_taps = kBN == 256 ? 3 : 6;          // (K tiles the next chunk's halo needs to land, see the kernel)
-    *bn = kBN;
     const int wm_total = a->W_dst / a->phases;
     if (wm_total < kTC || a->H < kTR) return false;
     if (kTR + a->tt.rows - 1 > kHaloRows) return false;
@@ -580,38 +580,30 @@ bool rv_tapconv5_plan(TapConvArgs* a, int* tiles, size_t* lds, int* bn) {
     a->n_tiles = a->C_dst / kBN;
     a->tiles_per_xcd = rv_ceil_div(a->total_tiles, 8);
     if ((int64_t)a->total_tiles * a->n_tiles < ((a->sel & RV_SEL_SMALL_GRIDS) ? 1 : rv_cu_count())) return false;  // too few tiles to fill the chip
-    *tiles = a->total_tiles;  // stats rows = 2 * tiles
-    *lds = (size_t)kLds;
+    p->gen = 5;
+    p->bn = kBN;
+    p->epi = (a->flags & RV_OUT_BNB) ? 1 : ((a->flags & RV_OUT_ACCUM) ? 2 : 0);
+    p->grid_x = 8 * a->tiles_per_xcd * a->n_tiles;
+    if (p->grid_x > rv_cu_count()) p->grid_x = rv_persistent_grid();  // one workgroup per CU (154 KB of LDS each)
+    p->stats_rows = a->total_tiles * 2;
+    p->bnb_rows = a->total_tiles;
+    p->lds = (size_t)kLds;
     const size_t epi = (size_t)kTR * kTC * (kBN + 8) * sizeof(bf16_t);
-    if (*lds < epi) *lds = epi;
+    if (p->lds < epi) p->lds = epi;
+    p->info[0] = 5, p->info[1] = kBN, p->info[2] = a->total_tiles, p->info[3] = a->n_tiles;
     return true;
 }
 
-int rv_tapconv5_launch(const TapConvArgs& a, size_t lds, int bn, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)tapconv5_kernel<256, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv5_kernel<128, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv5_kernel<256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv5_kernel<128, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv5_kernel<256, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv5_kernel<128, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    int grid = 8 * a.tiles_per_xcd * a.n_tiles;
-    if (grid > rv_cu_count()) grid = rv_persistent_grid();  // one workgroup per CU (154 KB of LDS each)
-    const int epi = (a.flags & RV_OUT_BNB) ? 1 : ((a.flags & RV_OUT_ACCUM) ? 2 : 0);
-#define RV_T5_LAUNCH(BN_, EPI_) hipLaunchKernelGGL((tapconv5_kernel<BN_, EPI_>), dim3(grid), dim3(512), lds, stream, a)
-    if (bn == 256) {
-        if (epi == 1) RV_T5_LAUNCH(256, 1);
-        else if (epi == 2) RV_T5_LAUNCH(256, 2);
-        else RV_T5_LAUNCH(256, 0);
-    } else {
-        if (epi == 1) RV_T5_LAUNCH(128, 1);
-        else if (epi == 2) RV_T5_LAUNCH(128, 2);
-        else RV_T5_LAUNCH(128, 0);
-    }
-#undef RV_T5_LAUNCH
+template <int BN, int EPI>
+static int launch5(const TapPlan& p, hipStream_t stream) {
+    RV_LDS_OPT_IN(160 * 1024, tapconv5_kernel<BN, EPI>);
+    hipLaunchKernelGGL((tapconv5_kernel<BN, EPI>), dim3(p.grid_x), dim3(512), p.lds, stream, p.args);
     RV_CHECK_LAUNCH("tapconv5_kernel");
     return 0;
+}
+
+int rv_tapconv5_launch(const TapPlan& p, hipStream_t stream) {
+    if (p.epi == 0) return p.bn == 256 ? launch5<256, 0>(p, stream) : launch5<128, 0>(p, stream);
+    if (p.epi == 1) return p.bn == 256 ? launch5<256, 1>(p, stream) : launch5<128, 1>(p, stream);
+    return p.bn == 256 ? launch5<256, 2>(p, stream) : launch5<128, 2>(p, stream);
 }

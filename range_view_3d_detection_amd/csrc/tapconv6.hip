@@ -482,13 +482,8 @@ __global__ __launch_bounds__(512, 2) void tapconv6_kernel(const TapConvArgs a) {
 
 
 // returns false when the layer is not eligible (caller falls back to tapconv5 / tapconv4 / ...)
-static int tapconv6_grid(const TapConvArgs& a) {
-    int grid = 8 * a.tiles_per_xcd * a.n_tiles;
-    if (grid > rv_cu_count()) grid = rv_persistent_grid();  // one workgroup per CU
-    return grid;
-}
-
-bool rv_tapconv6_plan(TapConvArgs* a, int* tiles, size_t* lds, int* stats_rows, int* bnb_rows) {
+bool rv_tapconv6_plan(TapPlan* p) {
+    TapConvArgs* a = &p->args;
     if (a->step != 1) return false;
     if (a->flags & (RV_IN_AFFINE | RV_IN_RELU | RV_OUT_F32)) return false;  // the DMA path has no register prologue
     // BatchNorm-backward sums over an ACCUMULATED gradient (the round-3/4 "masked last-writer" form: three 16-byte prefetches per
@@ -529,30 +524,30 @@ bool rv_tapconv6_plan(TapConvArgs* a, int* tiles, size_t* lds, int* stats_rows, 
     a->n_tiles = a->C_dst / kBN;
     a->tiles_per_xcd = rv_ceil_div(a->total_tiles, 8);
     if ((int64_t)a->total_tiles * a->n_tiles < ((a->sel & RV_SEL_SMALL_GRIDS6) ? 1 : rv_cu_count())) return false;  // fewer tiles than CUs: the 256-pixel tiles fill the chip better
-    *tiles = a->total_tiles;
-    const int grid = tapconv6_grid(*a), nslots = grid / 8;
+    int grid = 8 * a->tiles_per_xcd * a->n_tiles;
+    if (grid > rv_cu_count()) grid = rv_persistent_grid();  // one workgroup per CU
+    const int nslots = grid / 8;
     a->stats_per_wg = (nslots % a->n_tiles == 0) ? 1 : 0;
-    *stats_rows = a->stats_per_wg ? (grid / a->n_tiles) * 4 : a->total_tiles * 4;
-    *bnb_rows = a->stats_per_wg ? grid / a->n_tiles : a->total_tiles;
-    *lds = (size_t)kLds;
+    p->gen = 6;
+    p->epi = (a->flags & RV_OUT_BNB) ? 1 : ((a->flags & RV_OUT_ACCUM) ? 2 : 0);
+    p->grid_x = grid;
+    p->stats_rows = a->stats_per_wg ? (grid / a->n_tiles) * 4 : a->total_tiles * 4;
+    p->bnb_rows = a->stats_per_wg ? grid / a->n_tiles : a->total_tiles;
+    p->lds = (size_t)kLds;
     const size_t epi = (size_t)kTR * kTC * (kBN + 8) * sizeof(bf16_t);
-    if (*lds < epi) *lds = epi;
+    if (p->lds < epi) p->lds = epi;
+    p->info[0] = 6, p->info[1] = kBN, p->info[2] = a->total_tiles, p->info[3] = a->n_tiles;
     return true;
 }
 
-int rv_tapconv6_launch(const TapConvArgs& a, size_t lds, hipStream_t stream) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)tapconv6_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv6_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)tapconv6_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr_set = true;
-    }
-    const int grid = tapconv6_grid(a);
-    const int epi = (a.flags & RV_OUT_BNB) ? 1 : ((a.flags & RV_OUT_ACCUM) ? 2 : 0);
-    if (epi == 1) hipLaunchKernelGGL((tapconv6_kernel<1>), dim3(grid), dim3(512), lds, stream, a);
-    else if (epi == 2) hipLaunchKernelGGL((tapconv6_kernel<2>), dim3(grid), dim3(512), lds, stream, a);
-    else hipLaunchKernelGGL((tapconv6_kernel<0>), dim3(grid), dim3(512), lds, stream, a);
+template <int EPI>
+static int launch6(const TapPlan& p, hipStream_t stream) {
+    RV_LDS_OPT_IN(160 * 1024, tapconv6_kernel<EPI>);
+    hipLaunchKernelGGL((tapconv6_kernel<EPI>), dim3(p.grid_x), dim3(512), p.lds, stream, p.args);
     RV_CHECK_LAUNCH("tapconv6_kernel");
     return 0;
+}
+
+int rv_tapconv6_launch(const TapPlan& p, hipStream_t stream) {
+    return p.epi == 0 ? launch6<0>(p, stream) : p.epi == 1 ? launch6<1>(p, stream) : launch6<2>(p, stream);
 }

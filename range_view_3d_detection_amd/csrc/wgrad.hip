@@ -936,11 +936,7 @@ extern "C" int rv_tap_wgrad(const rvTapGeom* g, const rvTapShape* s, const void*
         const int grid2 = p.main_blocks + p.left_blocks;
         const bool dma = wgrad_dma_eligible(g, s);
         if (dma) {
-            static bool attr_set = false;
-            if (!attr_set) {
-                (void)hipFuncSetAttribute((const void*)wgrad3_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr_set = true;
-            }
+            RV_LDS_OPT_IN(160 * 1024, wgrad3_kernel);
             hipLaunchKernelGGL(wgrad3_kernel, dim3(grid2), dim3(512), kW3Lds, st2, b);
             RV_CHECK_LAUNCH("wgrad3_kernel");
         } else {

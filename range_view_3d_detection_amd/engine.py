@@ -181,8 +181,9 @@ def _launch(name: str, flops: float, fn, nbytes: float = 0.0) -> None:
 
 
 def tap_kernel_name(geom, shape, scatter: bool) -> str:
-    info = (ctypes.c_int32 * 4)()
-    L.call("rv_tap_launch_info", ctypes.byref(geom), ctypes.byref(shape), L.i32(1 if scatter else 0), info)
+    info = L.tap_launch_info(geom, shape, scatter)
+    if info is None:
+        raise L.RvError(f"rv_tap_launch_info failed: {L.load().rv_last_error().decode()}")
     if info[0] in (4, 5, 6):
         name = f"tapconv{info[0]}_kernel<{info[1]}>"
     elif info[0] in (2, 3):
@@ -520,9 +521,8 @@ BNB_FUSE = True
 
 def _dma_generation(geom, n: int, h: int, wu: int, wv: int, ld_src: int, ld_dst: int, scatter: bool) -> int:
     """Kernel generation the library would pick for this launch on a PLAIN bf16 operand (rv_tap_launch_info)."""
-    info = (ctypes.c_int32 * 4)()
-    shape = L.TapShape(n, h, wu, wv, ld_src, ld_dst, 0)
-    return info[0] if L.load().rv_tap_launch_info(ctypes.byref(geom), ctypes.byref(shape), 1 if scatter else 0, info) == 0 else 0
+    info = L.tap_launch_info(geom, L.TapShape(n, h, wu, wv, ld_src, ld_dst, 0), scatter)
+    return info[0] if info is not None else 0
 
 
 def _dma_eligible(geom, n: int, h: int, wu: int, wv: int, ld_src: int, ld_dst: int, scatter: bool) -> bool:
@@ -534,6 +534,26 @@ def _dma_eligible(geom, n: int, h: int, wu: int, wv: int, ld_src: int, ld_dst: i
 # tapconv2 + wgrad2 (profiles/r06_ab_notes.md).  Other 1x1 shapes keep the folded operand (the tiled kernel saves what the pass costs).
 MATERIALIZE_FOR_POINTWISE = True
 MATERIALIZE_POINTWISE_C = (256,)  # input widths that take it (128: time-neutral on rv-waymo, +0.27 ms on rv-av2 -- profiles/r06_ab_notes.md section 4; profiles/tools/diag_waymo_stem.py adds it back)
+
+
+def _materialize_operand(x, layer, src, wu: int, wv: int, out, out_f32: bool, eval_bn) -> bool:
+    """Whether ``ConvOp`` writes a folded BatchNorm(+ReLU) operand out once so that its conv runs on a kernel that takes plain operands only."""
+    if not (isinstance(x, Lazy) and MATERIALIZE_FOR_DMA and not out_f32):
+        return False
+    g, form = layer.geom, layer.fwd_form
+    # multi-tap layers on the LDS-DMA kernels (not 1x1 layers in general: there the extra pass costs what the faster kernel saves)
+    if g.kh * g.kw > 1 and _dma_eligible(g, src.N, src.H, wu, wv, src.ld, pad32(layer.c_out), form == "scatter"):
+        return True
+    # 1x1 layers on the pointwise streaming GEMM.  (256 input channels only -- rv-av2's stem.  For 128 input channels (rv-waymo's stem conv, the
+    # 1/2 .. 1/8-resolution layers of both models) the write-out is time-neutral on rv-waymo and +0.27 ms per rv-av2 step: off on that measurement,
+    # profiles/r06_ab_notes.md section 4 -- the fault first met on this route was wgrad3's, fixed there.  Asked with the strides the launch will really have.)
+    if (MATERIALIZE_FOR_POINTWISE and g.kh * g.kw == 1 and layer.bias is None and eval_bn is None and pad32(layer.c_in) in MATERIALIZE_POINTWISE_C
+            and _dma_generation(g, src.N, src.H, wu, wv, pad32(layer.c_in), out.ld if out is not None else pad32(layer.c_out), form == "scatter") == 7):
+        return True
+    # strided multi-tap conv: the FOLDED stride-1 form (forward and weight gradient) then runs on the LDS-DMA kernels instead of the
+    # generic strided ones
+    return (form == "gather" and g.stride_w > 1 and g.kh * g.kw > 1 and layer.fold_geom() is not None and src.ld == src.cp
+            and src.W == g.stride_w * wu and _dma_eligible(layer.fold_geom(), src.N, src.H, wu, wu, g.stride_w * src.ld, pad32(layer.c_out), False))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -935,26 +955,7 @@ class ConvOp(Op):
             w_out = wv
         assert src.cp == pad32(layer.c_in), (src.cp, layer.c_in)
         self.x_plain = None
-        # (not for 1x1 layers in general: there the extra pass costs what the faster kernel saves)
-        if (isinstance(x, Lazy) and MATERIALIZE_FOR_DMA and not out_f32 and g.kh * g.kw > 1
-                and _dma_eligible(g, src.N, src.H, wu, wv, src.ld, pad32(layer.c_out), form == "scatter")):
-            self.x_plain = src = x.materialized()
-            sc = sh = None
-            flags = 0
-        elif (isinstance(x, Lazy) and MATERIALIZE_FOR_DMA and MATERIALIZE_FOR_POINTWISE and not out_f32 and g.kh * g.kw == 1 and layer.bias is None
-              and eval_bn is None and pad32(layer.c_in) in MATERIALIZE_POINTWISE_C
-              and _dma_generation(g, src.N, src.H, wu, wv, pad32(layer.c_in), out.ld if out is not None else pad32(layer.c_out), form == "scatter") == 7):
-            # (256 input channels only -- rv-av2's stem.  For 128 input channels (rv-waymo's stem conv, the 1/2 .. 1/8-resolution layers of both models) the
-            #  write-out is time-neutral on rv-waymo and +0.27 ms per rv-av2 step: off on that measurement, profiles/r06_ab_notes.md section 4 -- the fault
-            #  first met on this route was wgrad3's, fixed there.  Asked with the strides the launch will really have.)
-            self.x_plain = src = x.materialized()
-            sc = sh = None
-            flags = 0
-        elif (isinstance(x, Lazy) and MATERIALIZE_FOR_DMA and not out_f32 and form == "gather" and g.stride_w > 1 and g.kh * g.kw > 1
-              and layer.fold_geom() is not None and src.ld == src.cp and src.W == g.stride_w * wu
-              and _dma_eligible(layer.fold_geom(), src.N, src.H, wu, wu, g.stride_w * src.ld, pad32(layer.c_out), False)):
-            # strided multi-tap conv fed by a folded BatchNorm+ReLU: written out once, the FOLDED stride-1 form (forward and
-            # weight gradient) then runs on the LDS-DMA kernels instead of the generic strided ones
+        if _materialize_operand(x, layer, src, wu, wv, out, out_f32, eval_bn):
             self.x_plain = src = x.materialized()
             sc = sh = None
             flags = 0

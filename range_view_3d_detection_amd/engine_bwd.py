@@ -132,8 +132,8 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
             # two on the hardware queues: the intent is that the weight gradient's workgroups take CUs as the last round leaves them idle;
             # when they take some earlier, this launch's rounds stretch by the same amount.  Kept on the measurement alone: rv-waymo
             # -1.0 ms chained / -0.15 ms free-running, rv-av2 (no ragged launch) unchanged (profiles/r04_ab_notes.md, r05_ab_notes.md)
-            info = (ctypes.c_int32 * 4)()
-            if (L.load().rv_tap_launch_info(ctypes.byref(bg), ctypes.byref(bshape), 1 if bwd == "scatter" else 0, info) == 0 and info[0] == 6):
+            info = L.tap_launch_info(bg, bshape, bwd == "scatter")
+            if info is not None and info[0] == 6:
                 wg_tiles, cus = info[2] * info[3], E.cu_count(t.device)
                 if wg_tiles / (cus * ((wg_tiles + cus - 1) // cus)) < E.EARLY_WGRAD_FILL:
                     early_ready = torch.cuda.Event()
