@@ -505,6 +505,38 @@ int rv_nms_sweeps(const float* scores, const int64_t* cats, const float* cuboids
                   float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms,
                   int32_t cap, int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts,
                   void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream);
+/* ---------------------------------------------------------------------------------------
+ * Hard NMS (`post_processing_config.nms_mode: HARD`) -- replaces `detectron2.layers.nms.nms_rotated(boxes, scores,
+ * iou_threshold) -> keep` as `hard_multiclass_nms` uses it (math/ops/nms.py:10-61) and, for a batch, that function's
+ * per-class loop inside `batched_multiclass_nms` (:181-266).  detectron2 is not part of the reference tree, so the last bit
+ * of its IoU is not pinned (parity unpinned at the last bit of the IoU, as for rv_wnms); declared semantics:
+ *   1. boxes are visited in descending score order (ties: ascending input index); a box not yet suppressed is kept;
+ *   2. a kept box suppresses every later box whose rotated BEV IoU with it is STRICTLY GREATER than `iou_threshold`;
+ *      a suppressed box suppresses nothing;
+ *   3. the IoU is rv_rotated_iou's (rectangle [x1,y1,x2,y2,ry], unfused fp32, sin / cos = fp32 roundings of the fp64
+ *      values).  detectron2 puts a box's width axis at (cos a, -sin a) -- `angle` runs counter-clockwise in IMAGE
+ *      coordinates, y pointing down -- and the reference passes `-yaw` in degrees (nms.py:39): the rectangle whose length
+ *      axis lies at +yaw, which is the one rv_nms_sweeps builds from the cuboid ([x - l/2, y - w/2, x + l/2, y + w/2, yaw]).
+ *      The batch entry builds it that way, never through degrees.
+ * Hard NMS is a SELECTION: every output row of rv_nms_sweeps_hard is a row of `cuboids` / `scores`, bit for bit.
+ *
+ * rv_nms_rotated -- one score-sorted list (the counterpart of rv_wnms_classes): boxes (n,5) = [x1,y1,x2,y2,ry] f32 sorted by
+ * score descending, `cats` (n,) i32 or NULL (boxes of different classes do not suppress each other); writes the sorted
+ * positions of the kept boxes, ascending, to `keep` (n,) i64 -- a DEVICE buffer owned by the caller, as is `workspace`
+ * (rv_nms_rotated_workspace_bytes(n) bytes) -- and returns their number through `host_num_out` after synchronising `stream`.
+ *
+ * rv_nms_sweeps_hard -- the device-resident batch path: the arguments, the `resume` / `out_counts` protocol and the
+ * per-candidate `workspace` (rv_nms_sweeps_workspace_bytes) of rv_nms_sweeps, without `merge_thresh`; there is ONE pair mask,
+ * so `mask_workspace` is B x `mask_words` 64-bit words.  Rows per sweep: classes ascending, score descending (ties:
+ * candidate index ascending), at most num_post_nms per class of the at most num_pre_nms best candidates of the class.
+ * Asynchronous. */
+int64_t rv_nms_rotated_workspace_bytes(int64_t n);
+int rv_nms_rotated(const float* boxes, const int32_t* cats, int64_t n, float iou_threshold, int64_t* keep, void* workspace,
+                   int64_t* host_num_out, rvStream stream);
+int rv_nms_sweeps_hard(const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
+                       float min_confidence, float iou_threshold, int32_t num_pre_nms, int32_t num_post_nms, int32_t cap,
+                       int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts, void* workspace,
+                       void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream);
 int rv_rotated_iou(const float* a, int64_t n, const float* b, int64_t m, float* out, rvStream stream);
 
 /* ---------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@
 //      merge row with the boxes still alive (=> cluster membership);
 //   3. cluster merge: one wave per kept box, lanes = data columns, members visited in ascending
 //      index order (fixed summation order => reproducible).
+// Hard NMS (`rv_nms_rotated`: detectron2's `nms_rotated` on a score-sorted list, math/ops/nms.py:40-44) is stages 1 and 2
+// with the mode as a template parameter: one mask (IoU > iou_threshold), a scan that reads it and writes `keep`, no stage 3.
 #include "common.h"
 #include "nms_geom.h"
 
@@ -27,6 +29,8 @@ __global__ void sincos_kernel(const float* boxes, int64_t n, float* sc) {
 // grid (col_block, row_block); only col_block >= row_block does work
 // cats (optional): class id per box -- boxes of different classes neither suppress nor merge (all classes of a sweep in
 // one launch instead of the reference's per-class loop)
+// HARD: the suppression mask only (merge_t / merge_mask are not read)
+template <bool HARD>
 __global__ __launch_bounds__(64) void iou_mask_kernel(const float* boxes, const float* sc, const int32_t* cats, int64_t n, int cb,
                                                       float nms_t, float merge_t, unsigned long long* nms_mask,
                                                       unsigned long long* merge_mask) {
@@ -55,7 +59,7 @@ __global__ __launch_bounds__(64) void iou_mask_kernel(const float* boxes, const 
     // too, so skipping them changes no bit of the masks (the thresholds are positive)
     const float cxi = 0.5f * (a[0] + a[2]), cyi = 0.5f * (a[1] + a[3]);
     const float ri = 0.5f * sqrtf((a[2] - a[0]) * (a[2] - a[0]) + (a[3] - a[1]) * (a[3] - a[1]));
-    const bool skip_far = nms_t >= 0.f && merge_t >= 0.f;
+    const bool skip_far = nms_t >= 0.f && (HARD || merge_t >= 0.f);
     unsigned long long bits_n = 0ull, bits_m = 0ull;
     const int jn = (int)((n - j0) < 64 ? (n - j0) : 64);
     for (int j = 0; j < jn; ++j) {
@@ -65,10 +69,11 @@ __global__ __launch_bounds__(64) void iou_mask_kernel(const float* boxes, const 
         if (skip_far && dx * dx + dy * dy > (ri + rj) * (ri + rj) * 1.001f + 1e-4f) continue;
         const float iou = rotated_iou(a, sa, ca, cbox[j], cbox[j][5], cbox[j][6]);
         if (iou > nms_t) bits_n |= 1ull << j;
-        if (iou > merge_t) bits_m |= 1ull << j;
+        if constexpr (!HARD)
+            if (iou > merge_t) bits_m |= 1ull << j;
     }
     nms_mask[i * cb + col] = bits_n;
-    merge_mask[i * cb + col] = bits_m;
+    if constexpr (!HARD) merge_mask[i * cb + col] = bits_m;
 }
 
 // One workgroup; remv (suppressed set) lives in LDS.  The scan walks the boxes in blocks of 64 (one mask word): inside a block
@@ -76,6 +81,8 @@ __global__ __launch_bounds__(64) void iou_mask_kernel(const float* boxes, const 
 // steps, no barrier); then every thread owning a later word w folds the rows of the block's kept boxes into remv[w] (and
 // masks their merge rows with the boxes alive at their visit) -- one round of global loads and two barriers per 64 boxes
 // instead of per kept box.  Same visiting order and the same sets as the box-by-box loop (oracle/nms.py).
+// HARD: no merge mask -- a later word of a kept box is one read of nms_mask.
+template <bool HARD>
 __global__ __launch_bounds__(1024) void scan_kernel(int64_t n, int cb, const unsigned long long* nms_mask,
                                                     unsigned long long* merge_mask, long long* keep, long long* num_out) {
     extern __shared__ unsigned long long remv[];
@@ -91,16 +98,18 @@ __global__ __launch_bounds__(1024) void scan_kernel(int64_t n, int cb, const uns
             const unsigned long long diag = in ? nms_mask[i * cb + wi] : 0ull;
             const unsigned long long in_bits = __ballot(in);
             const uint32_t dlo = (uint32_t)diag, dhi = (uint32_t)(diag >> 32);
-            unsigned long long rem = remv[wi], kept = 0ull, alive_mine = 0ull;
+            unsigned long long rem = remv[wi], kept = 0ull;
+            [[maybe_unused]] unsigned long long alive_mine = 0ull;
             for (int q = 0; q < 64; ++q) {  // uniform loop; lane q's diagonal word through readlane
                 if (!((in_bits >> q) & 1ull) || ((rem >> q) & 1ull)) continue;
                 kept |= 1ull << q;
-                if (b == q) alive_mine = ~rem;
+                if constexpr (!HARD)
+                    if (b == q) alive_mine = ~rem;
                 rem |= ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, q) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)dlo, q);
             }
             if ((kept >> b) & 1ull) {
                 keep[kept_total + __popcll(kept & ((1ull << b) - 1ull))] = i;
-                merge_mask[i * cb + wi] &= alive_mine;  // cluster = merge candidates not suppressed before i was visited
+                if constexpr (!HARD) merge_mask[i * cb + wi] &= alive_mine;  // cluster = merge candidates not suppressed before i was visited
             }
             if (b == 0) {
                 remv[wi] = rem;
@@ -116,7 +125,7 @@ __global__ __launch_bounds__(1024) void scan_kernel(int64_t n, int cb, const uns
                 const int q = __ffsll((long long)bits) - 1;
                 bits &= bits - 1;
                 const int64_t i = (int64_t)wi * 64 + q;
-                merge_mask[i * cb + w] &= ~r;
+                if constexpr (!HARD) merge_mask[i * cb + w] &= ~r;
                 r |= nms_mask[i * cb + w];
             }
             remv[w] = r;
@@ -198,10 +207,10 @@ extern "C" int rv_wnms_classes(const float* boxes, const float* data, const int3
     float* sc = (float*)(ws + 2 * align256(n * cb64 * 8));
     long long* num_out = (long long*)(ws + 2 * align256(n * cb64 * 8) + align256(n * 2 * 4));
     hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, boxes, n, sc);
-    hipLaunchKernelGGL(iou_mask_kernel, dim3(cb, cb), dim3(64), 0, st, boxes, sc, cats, n, cb, nms_thresh, merge_thresh, nms_mask,
+    hipLaunchKernelGGL(iou_mask_kernel<false>, dim3(cb, cb), dim3(64), 0, st, boxes, sc, cats, n, cb, nms_thresh, merge_thresh, nms_mask,
                        merge_mask);
-    RV_LDS_OPT_IN(160 * 1024 - 256, scan_kernel);  // + the static word
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(cb < 1024 ? ((cb + 63) / 64) * 64 : 1024), (size_t)cb * 8, st, n, cb,
+    RV_LDS_OPT_IN(160 * 1024 - 256, scan_kernel<false>);  // + the static word
+    hipLaunchKernelGGL(scan_kernel<false>, dim3(1), dim3(cb < 1024 ? ((cb + 63) / 64) * 64 : 1024), (size_t)cb * 8, st, n, cb,
                        nms_mask, merge_mask, (long long*)keep, num_out);
     hipLaunchKernelGGL(merge_kernel, dim3((unsigned)n), dim3(64), 0, st, data, d, cb, merge_mask, (const long long*)keep,
                        num_out, output, (long long*)count);
@@ -210,6 +219,40 @@ extern "C" int rv_wnms_classes(const float* boxes, const float* data, const int3
     hipError_t e = hipMemcpyAsync(&host, num_out, sizeof(host), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) RV_FAIL("rv_wnms: %s", hipGetErrorString(e));
+    *host_num_out = host;
+    return 0;
+}
+
+extern "C" int64_t rv_nms_rotated_workspace_bytes(int64_t n) {
+    const int64_t cb = (n + 63) / 64;
+    return align256(n * cb * 8) + align256(n * 2 * 4) + 256;
+}
+
+extern "C" int rv_nms_rotated(const float* boxes, const int32_t* cats, int64_t n, float iou_threshold, int64_t* keep, void* workspace,
+                              int64_t* host_num_out, rvStream stream) {
+    RV_REQUIRE(host_num_out, "rv_nms_rotated: null host_num_out");
+    *host_num_out = 0;
+    if (n == 0) return 0;
+    RV_REQUIRE(boxes && keep && workspace, "rv_nms_rotated: null argument");
+    const int64_t cb64 = (n + 63) / 64;
+    RV_REQUIRE(cb64 * 8 <= 160 * 1024 - 256, "rv_nms_rotated: too many boxes (%lld)", (long long)n);
+    const int cb = (int)cb64;
+    hipStream_t st = (hipStream_t)stream;
+    uint8_t* ws = (uint8_t*)workspace;
+    unsigned long long* nms_mask = (unsigned long long*)ws;
+    float* sc = (float*)(ws + align256(n * cb64 * 8));
+    long long* num_out = (long long*)(ws + align256(n * cb64 * 8) + align256(n * 2 * 4));
+    hipLaunchKernelGGL(sincos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, boxes, n, sc);
+    hipLaunchKernelGGL(iou_mask_kernel<true>, dim3(cb, cb), dim3(64), 0, st, boxes, sc, cats, n, cb, iou_threshold, 0.f, nms_mask,
+                       (unsigned long long*)nullptr);
+    RV_LDS_OPT_IN(160 * 1024 - 256, scan_kernel<true>);  // + the static word
+    hipLaunchKernelGGL(scan_kernel<true>, dim3(1), dim3(cb < 1024 ? ((cb + 63) / 64) * 64 : 1024), (size_t)cb * 8, st, n, cb, nms_mask,
+                       (unsigned long long*)nullptr, (long long*)keep, num_out);
+    RV_CHECK_LAUNCH("nms_rotated kernels");
+    long long host = 0;
+    hipError_t e = hipMemcpyAsync(&host, num_out, sizeof(host), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) RV_FAIL("rv_nms_rotated: %s", hipGetErrorString(e));
     *host_num_out = host;
     return 0;
 }

@@ -27,6 +27,19 @@
 // reports the number (counts[.][3]) and the caller re-runs the mask stages (`resume`) over a buffer of that size -- the
 // ordering stages are not repeated.  The reference's pre-NMS cut (`scores.topk(num_pre_nms)` per class, nms.py:83-84) is
 // the end of the class segment: boxes past position seg[c] + num_pre_nms of their class take no part.
+//
+// HARD mode (`rv_nms_sweeps_hard`: the reference's `hard_multiclass_nms` over detectron2's `nms_rotated`, nms.py:10-61) is
+// the same pipeline with the mode as a template parameter of the stages that differ:
+//   1, 2, seg, 6   as above (shared instantiations);
+//   3. gather      rectangles, sin / cos for the IoU and classes only -- no merge rows;
+//   4. iou masks   ONE mask (IoU > iou_threshold): `mask_workspace` is B x mask_words words, so the same budget holds twice
+//                  the candidates per class;
+//   5. scan        reads the one mask and writes the kept flags -- no merge-mask read-modify-write per kept box and word;
+//   7. --          (no merge stage)
+//   8. post        within a class the kept order IS the output order (score descending, candidate index ascending on ties):
+//                  position = class base + index among the class's kept boxes, dropped at >= num_post_nms -- no ranking pass;
+//                  the 7 floats and the score are copied from the caller's `cuboids` / `scores` rows (order -> cand), so every
+//                  output row is an input row bit for bit (the yaw never passes through sin / cos / atan2).
 #include "common.h"
 #include "nms_geom.h"
 
@@ -59,9 +72,10 @@ struct Args {
     uint8_t* ws;
     int64_t ws_stride;      // bytes per sweep
     int64_t K;
-    unsigned long long* mask_ws;  // [B][2][mask_words]
+    unsigned long long* mask_ws;  // [B][n_masks][mask_words]
     int64_t mask_words;           // word budget per sweep and mask
     int32_t B, cap, cb, n_classes, num_post, num_pre, out_cap;
+    int32_t n_masks;        // 2: weighted (suppression + merge masks); 1: hard (suppression mask only)
     float min_conf, nms_t, merge_t;
     float* out_boxes;       // [B][cap][7]
     float* out_scores;      // [B][cap]
@@ -97,8 +111,8 @@ inline int64_t sweep_bytes(int cap, int cb) {
 
 __device__ __forceinline__ SweepPtrs sweep(const Args& a, int b) {
     SweepPtrs p = carve(a.ws + (int64_t)b * a.ws_stride, a.cap, a.cb);
-    p.nms_mask = a.mask_ws + (int64_t)b * 2 * a.mask_words;
-    p.merge_mask = p.nms_mask + a.mask_words;
+    p.nms_mask = a.mask_ws + (int64_t)b * a.n_masks * a.mask_words;
+    p.merge_mask = a.n_masks == 2 ? p.nms_mask + a.mask_words : nullptr;
     return p;
 }
 // mask word (box i of class c, global word index w) -- valid for seg[c] <= i < send[c], w within the words of [seg[c], send[c])
@@ -173,7 +187,8 @@ __global__ __launch_bounds__(256) void k_rank(const Args a) {
     if (i < n) p.order[rank] = i;
 }
 
-// 3. gather in sorted order + class segments
+// 3. gather in sorted order + class segments (HARD: no merge rows)
+template <bool HARD>
 __global__ __launch_bounds__(256) void k_gather(const Args a) {
     const int b = blockIdx.y;
     const SweepPtrs p = sweep(a, b);
@@ -188,9 +203,11 @@ __global__ __launch_bounds__(256) void k_gather(const Args a) {
         const float hl = l / 2, hw = w / 2;
         float* rc = p.rect + (int64_t)r * 5;
         rc[0] = x - hl; rc[1] = y - hw; rc[2] = x + hl; rc[3] = y + hw; rc[4] = yaw;
-        float* d = p.data + (int64_t)r * 9;
-        d[0] = x; d[1] = y; d[2] = q[2]; d[3] = l; d[4] = w; d[5] = q[5];
-        d[6] = sinf(yaw); d[7] = cosf(yaw); d[8] = s[src];
+        if constexpr (!HARD) {
+            float* d = p.data + (int64_t)r * 9;
+            d[0] = x; d[1] = y; d[2] = q[2]; d[3] = l; d[4] = w; d[5] = q[5];
+            d[6] = sinf(yaw); d[7] = cosf(yaw); d[8] = s[src];
+        }
         p.sc[2 * r] = (float)sin((double)yaw);
         p.sc[2 * r + 1] = (float)cos((double)yaw);
         p.cats[r] = (int32_t)c[src];
@@ -231,6 +248,7 @@ __global__ __launch_bounds__(256) void k_unkeep(const Args a) {
     if (r < n_of(p, a.cap)) p.kept[r] = 0;
 }
 
+template <bool HARD>
 __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, int col) {
     const int64_t j0 = (int64_t)col * 64, i0 = (int64_t)row * 64;
     __shared__ float cbox[64][7];
@@ -257,7 +275,7 @@ __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, i
     // too, so skipping them changes no bit of the masks (thresholds are positive) and skips ~all pairs of a spread-out scene
     const float cxi = 0.5f * (bx[0] + bx[2]), cyi = 0.5f * (bx[1] + bx[3]);
     const float ri = 0.5f * sqrtf((bx[2] - bx[0]) * (bx[2] - bx[0]) + (bx[3] - bx[1]) * (bx[3] - bx[1]));
-    const bool skip_far = a.nms_t >= 0.f && a.merge_t >= 0.f;
+    const bool skip_far = a.nms_t >= 0.f && (HARD || a.merge_t >= 0.f);
     unsigned long long bits_n = 0ull, bits_m = 0ull;
     const int jn = (int)((n - j0) < 64 ? (n - j0) : 64);
     for (int j = 0; j < jn; ++j) {
@@ -267,11 +285,12 @@ __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, i
         if (skip_far && dx * dx + dy * dy > (ri + rj) * (ri + rj) * 1.001f + 1e-4f) continue;
         const float iou = rotated_iou(bx, sa, ca, cbox[j], cbox[j][5], cbox[j][6]);
         if (iou > a.nms_t) bits_n |= 1ull << j;
-        if (iou > a.merge_t) bits_m |= 1ull << j;
+        if constexpr (!HARD)
+            if (iou > a.merge_t) bits_m |= 1ull << j;
     }
     const int64_t mw = mword(p, cat_i, (int)i, col);
     p.nms_mask[mw] = bits_n;
-    p.merge_mask[mw] = bits_m;
+    if constexpr (!HARD) p.merge_mask[mw] = bits_m;
     __syncthreads();  // (the LDS tile is reused by the next column block)
 }
 
@@ -282,6 +301,7 @@ __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, i
 constexpr int kIouCols = 16;
 constexpr int kIouRows = 512;    // row blocks per launch wave (32 768 boxes); larger sweeps loop
 constexpr int kMergeGrid = 16384;
+template <bool HARD>
 __global__ __launch_bounds__(64) void k_iou(const Args a) {
     const SweepPtrs p = sweep(a, blockIdx.z);
     const int n = n_of(p, a.cap);
@@ -294,7 +314,7 @@ __global__ __launch_bounds__(64) void k_iou(const Args a) {
         // on (or may have been cut by the pre-NMS top-k before this block: then only the diagonal block is left to do)
         const int w_last = (p.send[c_last] - 1) >> 6;
         const int col_last = w_last > row ? w_last : row;
-        for (int col = row + blockIdx.x; col <= col_last; col += kIouCols) k_iou_block(a, p, n, row, col);
+        for (int col = row + blockIdx.x; col <= col_last; col += kIouCols) k_iou_block<HARD>(a, p, n, row, col);
     }
 }
 
@@ -304,6 +324,9 @@ __global__ __launch_bounds__(64) void k_iou(const Args a) {
 // resolved by ONE wave from the 64 diagonal words held one per lane (64 register-only steps); then every thread owning a later
 // word w folds the rows of the block's kept boxes into remv[w] (and masks their merge rows with the boxes alive at their
 // visit) -- one round of global loads per 64 boxes instead of one per kept box.
+// HARD: there is no merge mask -- a later word of a kept box is one read of nms_mask (weighted: that read plus a
+// read-modify-write of merge_mask), and a kept box writes its flag only.
+template <bool HARD>
 __global__ __launch_bounds__(256) void k_scan(const Args a) {
     const SweepPtrs p = sweep(a, blockIdx.y);
     const int cls = blockIdx.x;
@@ -322,16 +345,18 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
             const unsigned long long diag = in_seg ? p.nms_mask[mword(p, cls, i, wi)] : 0ull;
             const unsigned long long seg_bits = __ballot(in_seg);
             const uint32_t dlo = (uint32_t)diag, dhi = (uint32_t)(diag >> 32);
-            unsigned long long rem = remv[wi - w0], kept = 0ull, alive_mine = 0ull;
+            unsigned long long rem = remv[wi - w0], kept = 0ull;
+            [[maybe_unused]] unsigned long long alive_mine = 0ull;
             for (int q = 0; q < 64; ++q) {  // uniform loop; lane q's diagonal word through readlane
                 if (!((seg_bits >> q) & 1ull) || ((rem >> q) & 1ull)) continue;
                 kept |= 1ull << q;
-                if (b == q) alive_mine = ~rem;
+                if constexpr (!HARD)
+                    if (b == q) alive_mine = ~rem;
                 rem |= ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, q) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)dlo, q);
             }
             if ((kept >> b) & 1ull) {
                 p.kept[i] = 1;
-                p.merge_mask[mword(p, cls, i, wi)] &= alive_mine;  // cluster = merge candidates not suppressed before i was visited
+                if constexpr (!HARD) p.merge_mask[mword(p, cls, i, wi)] &= alive_mine;  // cluster = merge candidates not suppressed before i was visited
             }
             if (b == 0) {
                 remv[wi - w0] = rem;
@@ -347,7 +372,7 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
                 const int q = __ffsll((long long)bits) - 1;
                 bits &= bits - 1;
                 const int64_t mw = mword(p, cls, wi * 64 + q, w);
-                p.merge_mask[mw] &= ~r;
+                if constexpr (!HARD) p.merge_mask[mw] &= ~r;
                 r |= p.nms_mask[mw];
             }
             remv[w - w0] = r;
@@ -464,30 +489,78 @@ __global__ __launch_bounds__(256) void k_post(const Args a) {
     a.out_cats[(int64_t)b * a.out_cap + pos] = co;
 }
 
-}  // namespace
-
-extern "C" int64_t rv_nms_sweeps_workspace_bytes(int32_t B, int32_t cap) {
-    if (B <= 0 || cap <= 0) return 0;
-    return (int64_t)B * sweep_bytes(cap, (cap + 63) / 64);
+// 8 (HARD). per-class prefix of the kept boxes and the final order: grid (blocks over kept boxes, sweep).  keep[] is in
+// ascending sorted position = class ascending, score descending, candidate index ascending on ties -- the output order of
+// the reference's per-class `topk(num_post_nms)` over rows that are already in descending score order -- so a kept box's
+// row is its class's base plus its index among the class's kept boxes.  Rows are copied from the caller's arrays.
+__global__ __launch_bounds__(256) void k_post_hard(const Args a) {
+    const int b = blockIdx.y;
+    const SweepPtrs p = sweep(a, b);
+    const int k = p.n[1];
+    if (blockIdx.x != 0 && (int)(blockIdx.x * 256) >= k) return;
+    __shared__ int cls_first[kMaxClasses + 1], cls_base[kMaxClasses + 1];
+    if (threadIdx.x <= kMaxClasses) {  // first kept box of class >= c (classes are contiguous in keep[])
+        const int c = threadIdx.x;
+        int lo = 0, hi = k;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (p.cats[p.keep[mid]] < c) lo = mid + 1; else hi = mid;
+        }
+        cls_first[c] = lo;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int acc = 0;
+        for (int c = 0; c < kMaxClasses; ++c) {
+            const int cnt = cls_first[c + 1] - cls_first[c];
+            cls_base[c] = acc;
+            acc += cnt < a.num_post ? cnt : a.num_post;
+        }
+        cls_base[kMaxClasses] = acc;
+        if (blockIdx.x == 0) {  // (same protocol as k_post)
+            a.out_counts[4 * b] = p.n[0] > a.cap ? -2 : (p.mbase[kMaxClasses] > a.mask_words ? -1 : acc);
+            a.out_counts[4 * b + 1] = p.n[0];
+            a.out_counts[4 * b + 2] = k;
+            a.out_counts[4 * b + 3] = p.mbase[kMaxClasses];
+        }
+    }
+    __syncthreads();
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= k) return;
+    const int i = p.keep[o];
+    const int co = p.cats[i];
+    const int rank = o - cls_first[co];
+    if (rank >= a.num_post) return;
+    const int pos = cls_base[co] + rank;
+    if (pos >= a.out_cap) return;  // (cannot happen when out_cap >= min(cap, n_classes * num_post_nms): checked on the host)
+    const int64_t src = (int64_t)b * a.K + p.cand[p.order[i]];
+    const float* q = a.cuboids + src * 7;
+    float* ob = a.out_boxes + ((int64_t)b * a.out_cap + pos) * 7;
+#pragma unroll
+    for (int c = 0; c < 7; ++c) ob[c] = q[c];
+    a.out_scores[(int64_t)b * a.out_cap + pos] = a.scores[src];
+    a.out_cats[(int64_t)b * a.out_cap + pos] = co;
 }
 
-extern "C" int rv_nms_sweeps(const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
-                             float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms,
-                             int32_t cap, int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts,
-                             void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
+template <bool HARD>
+int launch_sweeps(const char* who, const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
+                  float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms, int32_t cap,
+                  int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts, void* workspace,
+                  void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
     RV_REQUIRE(scores && cats && cuboids && out_boxes && out_scores && out_cats && out_counts && workspace && mask_workspace,
-               "rv_nms_sweeps: null argument");
-    RV_REQUIRE(B > 0 && K > 0 && cap >= 64 && cap % 64 == 0 && cap <= 262144, "rv_nms_sweeps: bad sizes (cap: multiple of 64, <= 262144)");
-    RV_REQUIRE(n_classes >= 1 && n_classes <= kMaxClasses, "rv_nms_sweeps: 1..%d classes", kMaxClasses);
-    RV_REQUIRE(num_post_nms >= 1 && num_pre_nms >= 1, "rv_nms_sweeps: num_pre_nms / num_post_nms must be positive");
-    RV_REQUIRE(mask_words >= 1, "rv_nms_sweeps: mask_words must be positive");
+               "%s: null argument", who);
+    RV_REQUIRE(B > 0 && K > 0 && cap >= 64 && cap % 64 == 0 && cap <= 262144, "%s: bad sizes (cap: multiple of 64, <= 262144)", who);
+    RV_REQUIRE(n_classes >= 1 && n_classes <= kMaxClasses, "%s: 1..%d classes", who, kMaxClasses);
+    RV_REQUIRE(num_post_nms >= 1 && num_pre_nms >= 1, "%s: num_pre_nms / num_post_nms must be positive", who);
+    RV_REQUIRE(mask_words >= 1, "%s: mask_words must be positive", who);
     const int64_t rows_max = (int64_t)n_classes * num_post_nms < cap ? (int64_t)n_classes * num_post_nms : cap;
-    RV_REQUIRE(out_cap >= rows_max, "rv_nms_sweeps: out_cap %d below min(cap, n_classes * num_post_nms) = %lld", out_cap, (long long)rows_max);
+    RV_REQUIRE(out_cap >= rows_max, "%s: out_cap %d below min(cap, n_classes * num_post_nms) = %lld", who, out_cap, (long long)rows_max);
     Args a;
     a.scores = scores; a.cats = cats; a.cuboids = cuboids;
     a.ws = (uint8_t*)workspace;
     a.mask_ws = (unsigned long long*)mask_workspace;
     a.mask_words = mask_words;
+    a.n_masks = HARD ? 1 : 2;
     a.cb = (cap + 63) / 64;
     a.ws_stride = sweep_bytes(cap, a.cb);
     a.K = K; a.B = B; a.cap = cap; a.n_classes = n_classes; a.num_post = num_post_nms; a.num_pre = num_pre_nms; a.out_cap = out_cap;
@@ -499,18 +572,47 @@ extern "C" int rv_nms_sweeps(const float* scores, const int64_t* cats, const flo
         hipLaunchKernelGGL(k_zero, dim3(B), dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_compact, dim3(cblocks, B), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_rank, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_gather, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_gather<HARD>, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
         hipLaunchKernelGGL(k_seg, dim3(B), dim3(128), 0, st, a);
     } else {
         hipLaunchKernelGGL(k_unkeep, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
     }
-    hipLaunchKernelGGL(k_iou, dim3(kIouCols, a.cb < kIouRows ? a.cb : kIouRows, B), dim3(64), 0, st, a);
-    RV_LDS_OPT_IN(64 * 1024, k_scan);
+    hipLaunchKernelGGL(k_iou<HARD>, dim3(kIouCols, a.cb < kIouRows ? a.cb : kIouRows, B), dim3(64), 0, st, a);
+    RV_LDS_OPT_IN(64 * 1024, k_scan<HARD>);
     const int seg_max = cap < num_pre_nms ? cap : num_pre_nms;  // longest class segment that takes part
-    hipLaunchKernelGGL(k_scan, dim3(n_classes, B), dim3(256), (size_t)(seg_max / 64 + 3) * 8, st, a);
+    hipLaunchKernelGGL(k_scan<HARD>, dim3(n_classes, B), dim3(256), (size_t)(seg_max / 64 + 3) * 8, st, a);
     hipLaunchKernelGGL(k_keep, dim3(B), dim3(1024), 0, st, a);
-    hipLaunchKernelGGL(k_merge, dim3(cap < kMergeGrid ? cap : kMergeGrid, B), dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_post, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
-    RV_CHECK_LAUNCH("rv_nms_sweeps kernels");
+    if constexpr (HARD) {
+        hipLaunchKernelGGL(k_post_hard, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(k_merge, dim3(cap < kMergeGrid ? cap : kMergeGrid, B), dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_post, dim3((cap + 255) / 256, B), dim3(256), 0, st, a);
+    }
+    RV_CHECK_LAUNCH(who);
     return 0;
+}
+
+}  // namespace
+
+extern "C" int64_t rv_nms_sweeps_workspace_bytes(int32_t B, int32_t cap) {
+    if (B <= 0 || cap <= 0) return 0;
+    return (int64_t)B * sweep_bytes(cap, (cap + 63) / 64);
+}
+
+extern "C" int rv_nms_sweeps(const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
+                             float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms,
+                             int32_t cap, int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts,
+                             void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
+    return launch_sweeps<false>("rv_nms_sweeps", scores, cats, cuboids, B, K, n_classes, min_confidence, nms_thresh, merge_thresh, num_pre_nms,
+                                num_post_nms, cap, out_cap, out_boxes, out_scores, out_cats, out_counts, workspace, mask_workspace, mask_words,
+                                resume, stream);
+}
+
+extern "C" int rv_nms_sweeps_hard(const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
+                                  float min_confidence, float iou_threshold, int32_t num_pre_nms, int32_t num_post_nms, int32_t cap,
+                                  int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts,
+                                  void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
+    return launch_sweeps<true>("rv_nms_sweeps_hard", scores, cats, cuboids, B, K, n_classes, min_confidence, iou_threshold, 0.f, num_pre_nms,
+                               num_post_nms, cap, out_cap, out_boxes, out_scores, out_cats, out_counts, workspace, mask_workspace, mask_words,
+                               resume, stream);
 }

@@ -1,9 +1,14 @@
-"""Weighted multi-class NMS -- mirrors ``torchbox3d/math/ops/nms.py:64-266``.
+"""Multi-class NMS, ``nms_mode`` WEIGHTED and HARD -- mirrors ``torchbox3d/math/ops/nms.py:10-266``.
 
 ``weighted_nms`` keeps the reference wrapper's signature and contract around the op-level FFI
 ``weighted_nms_ext.wnms_gpu`` (``nms.py:126-177``); here that FFI is ``rv_wnms`` of
 ``librv3d_hip.so``.  The kernel's arithmetic is not in the reference tree (third-party, un-pinned):
 the semantics implemented are declared in ``DESIGN.md`` / ``oracle/nms.py`` -- parity unpinned.
+
+``hard_multiclass_nms`` is the reference's function of that name (``nms.py:10-61``) around ``detectron2.layers.nms.nms_rotated``;
+here that call is ``rv_nms_rotated`` (declared semantics in ``include/rv3d.h``: descending score, ties by ascending index, a kept
+box suppresses later boxes with rotated BEV IoU strictly above the threshold).  Hard NMS is a selection: every output row is
+an input row, bit for bit.
 """
 
 from __future__ import annotations
@@ -46,13 +51,23 @@ def weighted_nms(boxes: Tensor, data2merge: Tensor, scores: Tensor, nms_threshol
 # ``FUSED_CLASSES_MAX`` (or more than 64 classes) takes the reference-shaped per-class loop over the FFI below.
 FUSED_CLASSES_MAX = 262144
 MASK_WORDS = 4 * 1024 * 1024
+NMS_MODES = ("WEIGHTED", "HARD")
+
+
+def _check_mode(nms_mode: str) -> str:
+    mode = nms_mode.upper()
+    if mode not in NMS_MODES:
+        raise NotImplementedError(f"NMS Mode: {mode} is not implemented.")  # (the reference's message, nms.py:240)
+    return mode
 
 
 def nms_sweeps(cuboids: Tensor, scores: Tensor, categories: Tensor, n_classes: int, iou_threshold: float, min_confidence: float,
-               num_post_nms: int, cap: int, num_pre_nms: int = 2**31 - 1) -> Tuple[Tensor, Tensor, Tensor, List[int]]:
+               num_post_nms: int, cap: int, num_pre_nms: int = 2**31 - 1, mode: str = "WEIGHTED") -> Tuple[Tensor, Tensor, Tensor, List[int]]:
     """(B,K,7), (B,K), (B,K) -> padded (B,R,7) boxes, (B,R) scores, (B,R) int32 classes and the per-sweep row counts
-    (-2: the sweep had more than ``cap`` candidates -- its rows are not valid)."""
+    (-2: the sweep had more than ``cap`` candidates -- its rows are not valid).  ``mode`` HARD: ``rv_nms_sweeps_hard`` -- one pair
+    mask per sweep instead of two, rows copied from the inputs."""
     _require_cuda(cuboids, "cuboids")
+    hard = _check_mode(mode) == "HARD"
     dev = cuboids.device
     B, K, _ = cuboids.shape
     cub = cuboids.detach().float().contiguous()
@@ -67,10 +82,14 @@ def nms_sweeps(cuboids: Tensor, scores: Tensor, categories: Tensor, n_classes: i
     num_pre = int(min(num_pre_nms, 2**31 - 1))
 
     def run(mask_words: int, resume: int) -> List[List[int]]:
-        masks = torch.empty((B, 2, mask_words), dtype=torch.int64, device=dev)
-        L.call("rv_nms_sweeps", L.ptr(sc), L.ptr(ct), L.ptr(cub), L.i32(B), L.i64(K), L.i32(n_classes), L.f32(min_confidence), L.f32(iou_threshold),
-               L.f32(0.5), L.i32(num_pre), L.i32(num_post_nms), L.i32(cap), L.i32(out_cap), L.ptr(ob), L.ptr(os_), L.ptr(oc), L.ptr(counts), L.ptr(ws),
-               L.ptr(masks), L.i64(mask_words), L.i32(resume), L.stream_ptr())
+        masks = torch.empty((B, 1 if hard else 2, mask_words), dtype=torch.int64, device=dev)
+        head = (L.ptr(sc), L.ptr(ct), L.ptr(cub), L.i32(B), L.i64(K), L.i32(n_classes), L.f32(min_confidence), L.f32(iou_threshold))
+        tail = (L.i32(num_pre), L.i32(num_post_nms), L.i32(cap), L.i32(out_cap), L.ptr(ob), L.ptr(os_), L.ptr(oc), L.ptr(counts), L.ptr(ws),
+                L.ptr(masks), L.i64(mask_words), L.i32(resume), L.stream_ptr())
+        if hard:
+            L.call("rv_nms_sweeps_hard", *head, *tail)
+        else:
+            L.call("rv_nms_sweeps", *head, L.f32(0.5), *tail)
         return counts.tolist()  # the one device->host read of the batch (a second one only when the mask budget was exceeded)
 
     budget = int(min(MASK_WORDS, max(1, (cap // 64 + 1) * cap)))  # (small inputs: no more than one class could need)
@@ -116,19 +135,61 @@ def weighted_multiclass_nms(cuboids_i: Tensor, scores_i: Tensor, categories_i: T
     return torch.cat(out_b), torch.cat(out_s), torch.cat(out_c)
 
 
+def nms_rotated_sorted(boxes: Tensor, iou_threshold: float, cats: Tensor = None) -> Tensor:
+    """``rv_nms_rotated``: rectangles (n,5) [x1,y1,x2,y2,ry] SORTED by score descending (``cats``: optional class per box, boxes of
+    different classes do not interact) -> sorted positions of the kept boxes, ascending, int64 on the device."""
+    _require_cuda(boxes, "boxes")
+    b = boxes.detach().float().contiguous()
+    n = b.shape[0]
+    c = None if cats is None else cats.detach().to(torch.int32).contiguous()
+    keep = torch.empty(n, dtype=torch.long, device=b.device)
+    ws = torch.empty(L.load().rv_nms_rotated_workspace_bytes(L.i64(n)), dtype=torch.uint8, device=b.device)
+    num_out = ctypes.c_int64(0)
+    L.call("rv_nms_rotated", L.ptr(b), L.ptr(c), L.i64(n), L.f32(iou_threshold), L.ptr(keep), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
+    return keep[: int(num_out.value)]
+
+
+def hard_multiclass_nms(cuboids_i: Tensor, scores_i: Tensor, categories_i: Tensor, iou_threshold: float, num_pre_nms: int,
+                        num_post_nms: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Per class (ascending ``unique``): top-k pre, hard rotated NMS, top-k post (``nms.py:10-61``); rows are input rows."""
+    n = scores_i.shape[0]
+    if 0 < n <= FUSED_CLASSES_MAX:
+        n_cls = int(categories_i.max().item()) + 1
+        if n_cls <= 64:
+            b, s, c, cnt = nms_sweeps(cuboids_i[None], scores_i[None], categories_i[None], n_cls, iou_threshold, -math.inf, num_post_nms, _capacity(n),
+                                      num_pre_nms, mode="HARD")
+            return b[0, : cnt[0]], s[0, : cnt[0]], c[0, : cnt[0]].to(s.dtype)
+    out_b: List[Tensor] = []
+    out_s: List[Tensor] = []
+    out_c: List[Tensor] = []
+    for j in categories_i.unique():
+        sel = categories_i == j
+        s, b = scores_i[sel], cuboids_i[sel]
+        # (``topk`` leaves the order of equal scores open; the declared rule is ascending index: a stable sort)
+        s, rank = s.sort(dim=0, descending=True, stable=True)
+        k = min(len(s), num_pre_nms)
+        s, b = s[:k], b[rank[:k]]
+        half = b[:, 3:5] / 2
+        rect = torch.cat([b[:, :2] - half, b[:, :2] + half, b[:, 6:7]], dim=-1)
+        keep = nms_rotated_sorted(rect, iou_threshold)[:num_post_nms]  # kept rows are in descending score order: top-k = prefix
+        out_b.append(b[keep])
+        out_s.append(s[keep])
+        out_c.append(torch.full_like(out_s[-1], fill_value=float(j)))
+    return torch.cat(out_b), torch.cat(out_s), torch.cat(out_c)
+
+
 def batched_multiclass_nms(cuboids: Tensor, scores: Tensor, categories: Tensor, num_pre_nms: int, num_post_nms: int,
                            iou_threshold: float, min_confidence: float, nms_mode: str, n_classes: int = None) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
     """Per sweep: ``score >= min_confidence`` filter, then per-class NMS (``nms.py:181-266``)."""
-    nms_mode = nms_mode.upper()
-    if nms_mode != "WEIGHTED":
-        raise NotImplementedError("NMS mode HARD (detectron2 nms_rotated) is not selected by the rv-* configs (conf/model/baseline.yaml:52)")
+    nms_mode = _check_mode(nms_mode)
+    multiclass_nms = hard_multiclass_nms if nms_mode == "HARD" else weighted_multiclass_nms
     bs, ss, cs, ids = [], [], [], []
     B, K = scores.shape
     fast = None
     cap = _capacity(K)
     if FUSED_CLASSES_MAX > 0 and n_classes is not None and n_classes <= 64:
         # device-resident path for the whole batch; sweeps that overflow its capacity fall through to the loop below
-        fast = nms_sweeps(cuboids, scores, categories, n_classes, iou_threshold, min_confidence, num_post_nms, cap, num_pre_nms)
+        fast = nms_sweeps(cuboids, scores, categories, n_classes, iou_threshold, min_confidence, num_post_nms, cap, num_pre_nms, mode=nms_mode)
     for i in range(B):
         if fast is not None and fast[3][i] >= 0:
             k = fast[3][i]
@@ -143,7 +204,7 @@ def batched_multiclass_nms(cuboids: Tensor, scores: Tensor, categories: Tensor, 
         m = scores[i] >= min_confidence
         if not bool(m.any()):
             continue
-        b, s, c = weighted_multiclass_nms(cuboids[i, m], scores[i, m], categories[i, m], iou_threshold, num_pre_nms, num_post_nms)
+        b, s, c = multiclass_nms(cuboids[i, m], scores[i, m], categories[i, m], iou_threshold, num_pre_nms, num_post_nms)
         bs.append(b)
         ss.append(s)
         cs.append(c)
