@@ -600,6 +600,51 @@ int rv_table_to_range_view(const float* table, int32_t n_cols, int64_t hw, int32
  * column map is applied (mask, extra feature maps).  Every other channel is copied through the column map bit for bit. */
 int rv_augment(const float* in, float* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ix, int32_t iy, int32_t iz,
                int32_t irange, const double* params, rvStream stream);
+/* rv_augment with a `point_dropout` inside the chain (prototype/loader.py:506-512 `_point_dropout`, applied at its position in
+ * `augmentations_config` by apply_augmentations, :514-549).  `params` as rv_augment (the whole chain); `post_params`: the same 32-double
+ * layout for the steps AFTER the dropout only (a_post, b_post, A_post, t_post, Ar_post, tr_post, use_range_post = a
+ * random_global_scale follows the dropout).  keep (B, H*W) u8 in the frame of the dropout step: the output pixel (h, w) looks at
+ * keep[h * W + (a_post * w + b_post) mod W].  A kept pixel gets exactly what rv_augment gives it.  A dropped pixel is an empty pixel
+ * from that step on: 0 in every non-Cartesian channel, A_post 0 + t_post in x / y / z and, in the `irange` channel,
+ * ||Ar_post 0 + tr_post|| when use_range_post != 0 (else 0). */
+int rv_augment_dropout(const float* in, float* out, int32_t B, int32_t C, int32_t H, int32_t W, int32_t ix, int32_t iy, int32_t iz,
+                       int32_t irange, const double* params, const double* post_params, const uint8_t* keep, rvStream stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Object-database sampling, "GT paste" (prototype/loader.py:708-789 `sample_database`, called from DataLoader.__getitem__ :672-682
+ * on the UNPADDED image, after the augmentations and before subsample_range_view).  The database is one CSR block on the device:
+ * points (P, 3 + F) fp32 = x, y, z, then the F feature columns; range (P) fp32 (>= 0); index (P) i32 = flat pixel h * W + w;
+ * offsets (n_obj + 1) i64.  samples (B, S) i32: object id per (sweep, slot), -1 = empty slot; keep (B, S) u8: the verdict of the
+ * collision steps (:726-733, through rv_rotated_iou).
+ *
+ * rv_db_paste_keys -- :741-742 (concat in sample order, sort by range, unique("index", keep="first")): the nearest point wins each
+ *   pixel.  One unit of work per (sweep, slot, point) of the kept slots, listed by a prefix sum over their point counts;
+ *   atomicMin(keys[b][index], float_bits(range) << 32 | work index).  TIE RULE: equal ranges on one pixel go to the lower
+ *   (slot, point) position (the reference leaves them to an unstable sort).  The library initialises the keys and clears `owned`
+ *   (B, S) u8.  `index_max`: the largest index of the block (checked against H * W here, on the host; the kernel also skips an index
+ *   outside the image); `max_work`: an upper bound of the batch's point count (sizes the grid; < 2^32).  workspace:
+ *   rv_db_paste_workspace_bytes(B, S, H, W) bytes, handed on to rv_db_paste_resolve.  Two launches.
+ * rv_db_paste_resolve -- :744-772, one pass over the B * H * W pixels, in -> out (distinct buffers): a pixel whose key was taken
+ *   gets its winner's F features, x / y / z in `cart` and mask = sqrtf(x*x + y*y + z*z) > 0 (fp32, :756) and sets owned[b][slot] = 1
+ *   (:744-745: a sample that owns no pixel leaves the annotations); EVERY pixel leaves with features * mask (:772).  A pasted point
+ *   overwrites the scene's pixel: there is no depth test against the scene.  mask: u8 0 / 1.  One launch.
+ * Both are asynchronous. */
+int64_t rv_db_paste_workspace_bytes(int32_t B, int32_t S, int32_t H, int32_t W);
+int rv_db_paste_keys(const int32_t* samples, const uint8_t* keep, int32_t B, int32_t S, const int64_t* offsets, int64_t n_obj,
+                     const float* range, const int32_t* index, int64_t index_max, int64_t max_work, int32_t H, int32_t W,
+                     uint8_t* owned, void* workspace, rvStream stream);
+int rv_db_paste_resolve(const float* features_in, const float* cart_in, const uint8_t* mask_in, float* features_out, float* cart_out,
+                        uint8_t* mask_out, int32_t B, int32_t F, int32_t H, int32_t W, const int32_t* samples, int32_t S,
+                        const int64_t* offsets, const float* points, const void* workspace, uint8_t* owned, rvStream stream);
+/* The database BUILDER's kernel (the reference ships none; the layout is what `sample_database` reads): for every row of `cuboids` /
+ * `box_offsets` (as rv_assign_targets) the pixels of its sweep with mask != 0 that lie inside the cuboid -- the interior test of
+ * rv_assign_targets (compute_interior_points_mask, math/polytope.py:14-56).  out_index == NULL: count pass and scan, counts (m) i64
+ * and obj_offsets (m + 1) i64 are written; out_index != NULL (capacity entries, >= obj_offsets[m]): fill pass, object k's flat
+ * pixel indices at obj_offsets[k] .. obj_offsets[k + 1], ascending (independent of scheduling).  A pixel inside two overlapping
+ * cuboids belongs to both objects.  mask: u8 (B, H*W).  Asynchronous. */
+int rv_db_extract(const float* cart, const uint8_t* mask, int32_t B, int32_t H, int32_t W, const double* cuboids, int32_t m,
+                  const int32_t* box_offsets, int64_t* counts, int64_t* obj_offsets, int32_t* out_index, int64_t capacity, rvStream stream);
+
 /* subsample_range_view's W padding at x_stride 1 (prototype/loader.py:792-815): out (C,H,W+2*pad) = pad(image * mask);
  * mask (H,W) may be NULL; circular != 0 wraps around in azimuth, else zeros.  AV2 pad 4 (1800 -> 1808), Waymo 3. */
 int rv_pad_range_view(const float* image, const float* mask, int32_t C, int32_t H, int32_t W, int32_t pad,

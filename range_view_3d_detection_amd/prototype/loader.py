@@ -163,13 +163,27 @@ class SweepTransform:
         self.t = torch.zeros(3, dtype=torch.float64)
         self.Ar, self.tr, self.use_range = torch.eye(3, dtype=torch.float64), torch.zeros(3, dtype=torch.float64), False
         self.ops: List[Any] = []
+        # a ``point_dropout`` inside the chain (loader.py:506-512 at its position, :514-549): its probability, and the composite of the
+        # steps AFTER it (same forms) -- what moves and rewrites a pixel that the dropout emptied
+        self.dropout_p: Optional[float] = None
+        self.post: Optional["SweepTransform"] = None
 
     def _then_cols(self, a2: int, b2: int) -> None:
         # new_out[w] = old_out[(a2*w + b2) mod W] = in[(a*(a2*w + b2) + b) mod W]
         self.a, self.b = self.a * a2, (self.a * b2 + self.b) % self.W
+        if self.post is not None:
+            self.post._then_cols(a2, b2)
 
     def _then_affine(self, M: Tensor, d: Tensor) -> None:
         self.A, self.t = M @ self.A, M @ self.t + d
+        if self.post is not None:
+            self.post._then_affine(M, d)
+
+    def dropout(self, p: float) -> None:  # loader.py:506-512: every column times ``rand(rows, 1) <= p`` at THIS step of the chain
+        if self.post is not None:
+            raise L.RvError("point_dropout appears twice in one augmentation chain")
+        self.dropout_p, self.post = float(p), SweepTransform(self.W)
+        self.ops.append(("dropout", float(p)))
 
     def flip(self) -> None:  # loader.py:948-990
         self._then_cols(-1, self.W - 1)
@@ -186,6 +200,8 @@ class SweepTransform:
     def scale(self, s: float) -> None:  # loader.py:885-915: range := ||xyz|| at this point of the chain
         self._then_affine(s * torch.eye(3, dtype=torch.float64), torch.zeros(3, dtype=torch.float64))
         self.Ar, self.tr, self.use_range = self.A.clone(), self.t.clone(), True
+        if self.post is not None:
+            self.post.Ar, self.post.tr, self.post.use_range = self.post.A.clone(), self.post.t.clone(), True
         self.ops.append(("scale", s))
 
     def translate(self, t: Sequence[float]) -> None:  # loader.py:918-945 (the range column is left as it is)
@@ -225,7 +241,9 @@ class SweepTransform:
 def draw_sweep_transform(width: int, augmentations_config: Mapping[str, Mapping[str, float]], rng=_random) -> SweepTransform:
     """The draws of ``Dataset.apply_augmentations`` (``loader.py:514-549``) for ONE sweep, in config order, with the
     reference's own ``random`` calls (flip: ``random() > p`` skips; rotation: ``random() > p`` skips, then ``uniform``;
-    scale: ``uniform``; translation: three ``normalvariate``)."""
+    scale: ``uniform``; translation: three ``normalvariate``).  A ``point_dropout`` draws nothing from ``rng`` (the reference draws its
+    keep mask from numpy's global generator, ``loader.py:508``): its position in the chain is recorded, and the transform keeps the
+    composite of the steps after it (``SweepTransform.post``)."""
     tr = SweepTransform(width)
     for k, v in augmentations_config.items():
         if k == "flip_azimuth":
@@ -241,17 +259,18 @@ def draw_sweep_transform(width: int, augmentations_config: Mapping[str, Mapping[
         elif k == "random_global_translation":
             tr.translate([rng.normalvariate(0, v["std_x"]), rng.normalvariate(0, v["std_y"]), rng.normalvariate(0, v["std_z"])])
         elif k == "point_dropout":
-            raise NotImplementedError("point_dropout inside a chain: supported at the HEAD of augmentations_config only (train_batch_from_tables folds its "
-                                      "keep mask into the table -> image kernel); no shipped rv-* recipe enables it")
+            tr.dropout(v["p"])  # the position is recorded; augment_batch draws the keep mask (numpy's generator, not ``rng``)
         else:
             raise KeyError(f"unknown augmentation {k!r}")
     return tr
 
 
 def apply_sweep_transforms(x: Tensor, transforms: Sequence[SweepTransform], xyz_channels: Optional[Sequence[int]] = None,
-                           range_channel: int = -1) -> Tensor:
+                           range_channel: int = -1, keep: Optional[Tensor] = None) -> Tensor:
     """(B, C, H, W) tensor -> augmented copy (``rv_augment``).  ``xyz_channels`` = positions of x, y, z among the channels
-    (None: apply the column map only -- the mask); bool tensors go through as fp32 0 / 1."""
+    (None: apply the column map only -- the mask); bool tensors go through as fp32 0 / 1.  ``keep``: (B, H*W) uint8 on the device,
+    the keep masks of a ``point_dropout`` inside the chain, in the frame of the dropout step (``rv_augment_dropout``; a sweep whose
+    chain holds no dropout keeps everything)."""
     _require_cuda(x, "tensor")
     was_bool = x.dtype == torch.bool
     src = x.float().contiguous()
@@ -260,6 +279,12 @@ def apply_sweep_transforms(x: Tensor, transforms: Sequence[SweepTransform], xyz_
     params = torch.stack([t.packed() for t in transforms]).to(src.device)
     out = torch.empty_like(src)
     ix, iy, iz = (-1, -1, -1) if xyz_channels is None else xyz_channels
+    if keep is not None:
+        assert keep.dtype == torch.uint8 and keep.shape == (b, h * w) and keep.is_contiguous()
+        post = torch.stack([(t.post if t.post is not None else SweepTransform(w)).packed() for t in transforms]).to(src.device)
+        L.call("rv_augment_dropout", L.ptr(src), L.ptr(out), L.i32(b), L.i32(c), L.i32(h), L.i32(w), L.i32(ix), L.i32(iy), L.i32(iz),
+               L.i32(range_channel), L.ptr(params), L.ptr(post), L.ptr(keep), L.stream_ptr())
+        return out > 0.5 if was_bool else out
     L.call("rv_augment", L.ptr(src), L.ptr(out), L.i32(b), L.i32(c), L.i32(h), L.i32(w), L.i32(ix), L.i32(iy), L.i32(iz), L.i32(range_channel),
            L.ptr(params), L.stream_ptr())
     return out > 0.5 if was_bool else out
@@ -282,13 +307,28 @@ def augment_batch(batch: Dict[str, Any], feature_column_names: Sequence[str], au
     if width is not None and feats.shape[-1] != int(width):
         raise L.RvError(f"augment_batch on a batch of width {feats.shape[-1]}, configured width {width}: augment BEFORE the W padding "
                         "(range_view_from_table(..., pad=False) -> augment_batch -> pad_batch)")
-    trs = [draw_sweep_transform(feats.shape[-1], augmentations_config, rng) for _ in range(feats.shape[0])]
+    import numpy as np
+
+    hw = feats.shape[-2] * feats.shape[-1]
+    trs, keeps = [], []
+    for _ in range(feats.shape[0]):
+        tr = draw_sweep_transform(feats.shape[-1], augmentations_config, rng)
+        trs.append(tr)
+        # ``_point_dropout`` (loader.py:506-512): ``np.random.rand(rows, 1) <= p`` from numpy's GLOBAL generator, one draw per sweep in
+        # sweep order, at the dropout's position in the chain (``rng`` and numpy's generator are separate streams)
+        keeps.append((np.random.rand(hw, 1) <= tr.dropout_p).reshape(-1) if tr.dropout_p is not None else None)
+    keep = None
+    if any(k is not None for k in keeps):
+        host = np.stack([k if k is not None else np.ones(hw, dtype=bool) for k in keeps]).astype(np.uint8)
+        keep = torch.from_numpy(host).pin_memory().to(feats.device, non_blocking=True)
     xyz = [names.index(n) for n in ("x", "y", "z")] if all(n in names for n in ("x", "y", "z")) else None
+    if keep is not None and xyz is None:
+        raise L.RvError("point_dropout inside a chain needs x, y and z among feature_column_names (a dropped pixel's coordinates follow the later steps)")
     out = dict(batch)
-    out["features"] = apply_sweep_transforms(feats, trs, xyz, names.index("range") if "range" in names and xyz is not None else -1)
-    out["cart"] = apply_sweep_transforms(cart, trs, (0, 1, 2))
+    out["features"] = apply_sweep_transforms(feats, trs, xyz, names.index("range") if "range" in names and xyz is not None else -1, keep)
+    out["cart"] = apply_sweep_transforms(cart, trs, (0, 1, 2), keep=keep)
     # mask' = (augmented range > 0): [x, y, z, valid] through the same kernel with `valid` in the range slot
-    aux = apply_sweep_transforms(torch.cat([cart.float(), mask.float()], dim=1), trs, (0, 1, 2), 3)
+    aux = apply_sweep_transforms(torch.cat([cart.float(), mask.float()], dim=1), trs, (0, 1, 2), 3, keep)
     out["mask"] = aux[:, 3:4] > 0
     ann = batch.get("annotations")
     if ann is not None and ann.shape[0] > 0:
@@ -326,12 +366,21 @@ def annotations_for_sweep(table: Mapping[str, Any], timestamp_ns: int, tasks: Ma
 
 def train_batch_from_tables(tables: Sequence[Mapping[str, Any]], annotations: Optional[Tensor], range_view_config: Mapping[str, Any],
                             dataset_name: str, augmentations_config: Optional[Mapping[str, Mapping[str, float]]], x_stride: int = 1,
-                            padding_mode: str = "constant", rng=_random, device="cuda") -> Dict[str, Any]:
+                            padding_mode: str = "constant", rng=_random, device="cuda", db=None, db_config=None, tasks=None) -> Dict[str, Any]:
     """The train-split item chain of ``DataLoader.__getitem__`` (``loader.py:594-705``) for a batch of sweep tables, in the
-    reference's order: ROI filter + table -> image (unpadded) -> augmentations -> ``features *= mask`` + W padding.
-    ``annotations``: (M, 13) fp64 rows in ``COLS`` order (``batch_index`` = position in ``tables``) or None."""
+    reference's order: ROI filter + table -> image (unpadded) -> augmentations -> object-database paste -> ``features *= mask`` + W
+    padding.  ``annotations``: (M, 13) fp64 rows in ``COLS`` order (``batch_index`` = position in ``tables``) or None.
+    ``db`` (an :class:`..database.ObjectDatabase` on the device), ``db_config`` (category -> num_samples) and ``tasks``: the reference's
+    ``enable_database`` (``loader.py:672-682``) -- one :func:`..database.draw_database_samples` per sweep from ``rng``, then
+    :func:`..database.paste_database`; pasted objects are not augmented."""
     import numpy as np
 
+    if db is not None and db_config is None:
+        raise RuntimeError("Database config must be defined.")  # loader.py:683
+    if db is None and db_config is not None:
+        raise L.RvError("db_config without a database: pass db=ObjectDatabase.from_directory(...).to(device) (the reference's enable_database)")
+    if db is not None and tasks is None:
+        raise L.RvError("the object-database paste needs `tasks` (targets_config.tasks): pasted rows get their task_id / offset from it")
     aug = dict(augmentations_config) if augmentations_config else {}
     keeps = [None] * len(tables)
     if aug and next(iter(aug)) == "point_dropout":
@@ -346,4 +395,8 @@ def train_batch_from_tables(tables: Sequence[Mapping[str, Any]], annotations: Op
         batch["annotations"] = annotations
     if aug:
         batch = augment_batch(batch, range_view_config["feature_column_names"], aug, rng, width=int(range_view_config["width"]))
+    if db is not None:
+        from .database import draw_database_samples, paste_database
+
+        batch = paste_database(batch, db, [draw_database_samples(db, db_config, rng) for _ in tables], tasks)
     return pad_batch(batch, dataset_name, x_stride, padding_mode)
