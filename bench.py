@@ -5,6 +5,9 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W          (already a rank: WORLD_SIZE must equal --gpus)
     python bench.py --steps K --warmup W --dump-outputs DIR   (+ DIR/<name>.npy: what the K-th timed step returned, `dump_outputs`)
+    python bench.py --steps K --warmup W --full               (+ every other measurement below, each a run of its own: minutes)
+
+A run without ``--full`` sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints the line: a few seconds beside the steps.
 
 One "step" = one pass of the hot path over one batch of synthetic sweeps per GPU: MetaKernel stem +
 DLA backbone + cls/reg towers (forward), device target assignment + varifocal/L1 loss, backward
@@ -15,7 +18,12 @@ across ranks (weak scaling, 4 sweeps per GPU), gradient all-reduce over RCCL per
 (engine.GradSync: the towers' gradients travel under the backbone's backward; RV3D_DDP=1: torch DDP),
 BatchNorm statistics all-reduced (SyncBN as in conf/trainer/train.yaml:15).
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
+Rank 0 prints ONE JSON line.  Always: the headline (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`), `gpu` (shader
+clock and power sampled by a host thread during the timed region), `config` (workload, last loss, collectives, peak HBM) and
+  "whole_step":   3 x the model's forward FLOPs over the step time, against the dense bf16 MFMA peak; `traffic_ratio` =
+                  HBM-side bytes of ALL kernels per step (PMC passes) over the algorithmic bytes of the step;
+  "kernels":      per-kernel event timings inside the timed region.
+With ``--full`` also, each from steps or a run of its own behind the timed region and the dump:
   "roofline":     the dominant kernel (tapconv6: 512-pixel x 128-channel-tile bf16 MFMA tap-conv with the input halo resident in LDS)
                   against the dense bf16 MFMA peak.  `achieved` / `frac` / `avg_launch_us`: HIP events around each of its launches INSIDE
                   the timed region, on the stream it runs on -- the configuration that produced ms_per_step, where a backward-data launch
@@ -25,11 +33,10 @@ Rank 0 prints ONE JSON line (contract in the task statement) including
   "roofline_hbm": the HBM-bound kernel group (BatchNorm backward, element-wise block passes, MetaKernel stem, head-final passes) against
                   8 TB/s: events around each of its launches in the timed configuration (`isolated`: side stream off), algorithmic bytes
                   from the C-ABI arguments, HBM-side traffic from the same PMC passes;
-  "whole_step":   3 x the model's forward FLOPs over the step time, against the same peak; `traffic_ratio` =
-                  HBM-side bytes of ALL kernels per step (PMC passes) over the algorithmic bytes of the step;
+  "kernels_isolated": the per-kernel event timings with nothing else on the GPU (side stream off);
   "loss_first_step": the loss of the seed-0 model on sweep 0 of the seed-1234 batch before any update (one reproducible number;
                   tests/test_gpu_fullsize_train.py compares it with the fp32 oracle);
-  "kernels" / "kernels_isolated": per-kernel event timings inside the timed region / with nothing else on the GPU;
+  "forward_only" / "rv_waymo": the eval forward + decode + NMS and the rv-waymo training step (BASELINE configs[1], [4]; N == 1 only);
   "cpu_baseline": the oracle (CPU restatement of the reference, ``oracle/``) timed on this box's host
                   cores on a bounded sample (N == 1 only).
 """
@@ -58,14 +65,18 @@ def parse_args(argv=None):
     ap.add_argument("--widths", default="rv-av2", help="rv-av2 (the metric's configuration), rv-waymo, or c<int> debug widths")
     ap.add_argument("--features", type=int, default=5, help="input channels: 5 (AV2) or 6 (Waymo)")
     ap.add_argument("--classes", type=int, default=AV2_CLASSES)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps (and --dump-outputs), also measure everything else the JSON line can carry: the isolated and "
+                         "HBM-group passes (roofline, roofline_hbm, kernels_isolated), loss_first_step, the forward_only and rv_waymo legs and "
+                         "the CPU baseline (minutes).  Without it: set-up, warm-up, the timed steps, the result line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-baseline", choices=["auto", "sample", "full"], default="auto",
-                    help="auto: the whole 64x2048 sweep when the host is fast enough (one or two timed iterations), else the cropped sample; "
-                         "sample: a 64xW crop (~45 s); full: 1 warm-up + 2 timed iterations of the whole sweep (minutes)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the forward_only and rv_waymo legs (extra keys of the JSON line)")
+                    help="with --full.  auto: the whole 64x2048 sweep when the host is fast enough (one or two timed iterations), else the cropped "
+                         "sample; sample: a 64xW crop (~45 s); full: 1 warm-up + 2 timed iterations of the whole sweep (minutes)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the forward_only and rv_waymo legs (extra keys of the JSON line)")
     ap.add_argument("--no-sync-bn", action="store_true")
-    ap.add_argument("--timed-only", action="store_true", help="warm-up + timed steps and nothing else (no isolated / HBM-group passes, no extra legs, "
-                                                              "no CPU baseline): the command the profiler passes of profiles/tools/collect_round.sh run")
+    ap.add_argument("--timed-only", action="store_true", help="warm-up + timed steps and nothing else, --full or not: what a run without --full "
+                                                              "does anyway (kept for the profiler passes of profiles/tools/, which give it)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the LAST timed step handed to its caller (loss, gradients, updated parameters, BatchNorm "
                          "running statistics) as DIR/<name>.npy (float32 / float64; seeded samples of the large arrays, see dump_outputs)")
@@ -861,11 +872,12 @@ def main(args=None) -> None:
     # (before the extra steps below move the parameters on)
     dumped = dump_outputs(args.dump_outputs, loss, model, opt) if args.dump_outputs and rank == 0 else None
     sync_calls, sync_bytes = E.COLLECTIVES.calls / args.steps, E.COLLECTIVES.bytes / args.steps
+    full = args.full and not args.timed_only  # every measurement below that takes a run of its own
     # the same per-kernel events once more, outside the timed region, with the weight-gradient side stream off: with
     # it on, kernels of the two streams share the CUs and each one's event-to-event time includes its neighbour's
     iso = E.KernelProfile()
     hbm_group = {}
-    if not args.timed_only:
+    if full:
         E.PROFILE, overlap = iso, E.OVERLAP_WGRAD
         E.OVERLAP_WGRAD = False
         for _ in range(2):
@@ -909,13 +921,12 @@ def main(args=None) -> None:
                                        "gradient_sync": ("DistributedDataParallel" if use_ddp else "engine.GradSync (flat buffer, one all-reduce per autograd node)") if dist_on else None,
                                        "note": "SyncBN: (2C+1) fp32 per BatchNorm layer and direction, layers that become available together share one all-reduce"},
                        "peak_hbm_gb": round(torch.cuda.max_memory_allocated(dev) / 2**30, 2)},
-            "roofline": roofline(prof, iso),
-            "roofline_hbm": hbm_group,
             "kernels": prof.summary(),
-            # the same launches with nothing else on the GPU (side stream off, two steps outside the timed region): with the small
-            # layers' weight gradients on the side stream the live event-to-event times of overlapping kernels include their neighbour
-            "kernels_isolated": iso.summary(),
         }
+        if full:
+            # kernels_isolated: the same launches with nothing else on the GPU (side stream off, two steps outside the timed region): with the
+            # small layers' weight gradients on the side stream the live event-to-event times of overlapping kernels include their neighbour
+            out.update(roofline=roofline(prof, iso), roofline_hbm=hbm_group, kernels_isolated=iso.summary())
         if dumped is not None:
             out["outputs_dumped"] = dumped
         if (args.widths, args.width) in FWD_TFLOP_PER_SWEEP and args.height == 64:
@@ -924,11 +935,11 @@ def main(args=None) -> None:
             if tr is not None:  # (per GPU: the PMC passes are one rank's)
                 out["whole_step"]["traffic_ratio"] = tr
         headline = (args.widths, args.width, args.height, args.features) == ("rv-av2", 2048, 64, 5)
-        if world == 1 and headline and not args.timed_only:
+        if full and world == 1 and headline:
             # (the model of the timed region has taken optimizer steps; this is a fresh one: 0.3 s)
             out["loss_first_step"] = {"value": first_step_loss(dev), "what": "train-mode loss of the seed-0 model on sweep 0 of the seed-1234 batch, B = 1, "
                                       "before any update; the fp32 oracle's value of the same quantity is asserted in tests/test_gpu_fullsize_train.py (1e-2)"}
-        if world == 1 and not args.no_extra and headline and not args.timed_only:
+        if full and world == 1 and not args.no_extra and headline:
             # extra keys, outside the timed region: BASELINE configs[1] (forward only + decode + NMS) and the one-GPU shard of configs[4]
             _progress("forward_only leg (eval forward + decode + weighted NMS)")
             out["forward_only"] = forward_only_leg(model, batch, args.classes, dev)
@@ -937,7 +948,7 @@ def main(args=None) -> None:
             torch.cuda.empty_cache()
             _progress("rv_waymo leg (64x2656x6, training step)")
             out["rv_waymo"] = rv_waymo_leg(dev)
-        if world == 1 and not args.no_cpu_baseline and not args.timed_only:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(full=args.cpu_baseline == "full", auto_full_limit=160.0 if args.cpu_baseline == "auto" else 0.0)
         print(json.dumps(out))
     if dist_on:

@@ -8,4 +8,4 @@ python3 profiles/tools/shape_prof.py --widths rv-waymo --width 2656 --features 6
 bash profiles/tools/trace_step.sh ${tag}_step_kernels > /dev/null 2>&1 && echo step ok
 bash profiles/tools/trace_step.sh ${tag}_step_kernels_waymo --widths rv-waymo --width 2656 --features 6 --classes 3 > /dev/null 2>&1 && echo step waymo ok
 bash profiles/tools/trace_gaps.sh ${tag}_gap_analysis > /dev/null 2>&1 && echo gaps ok
-python3 bench.py > gpurun_out/${tag}_bench.json 2> gpurun_out/${tag}_bench.err && echo bench ok
+mkdir -p out && python3 bench.py --full > out/${tag}_bench.json 2> out/${tag}_bench.err && echo bench ok

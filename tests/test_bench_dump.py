@@ -76,11 +76,15 @@ def _bench(out_dir, steps, extra=()):
 
 @pytest.mark.gpu
 def test_dump_is_the_last_timed_step_and_steps_sets_the_timed_steps(tmp_path):
-    """Three runs of the same seeded configuration: two timed steps with nothing behind them (``--timed-only``), two timed steps
-    followed by bench.py's untimed passes (six more optimizer steps: the dump must not see them), and three timed steps."""
-    ja, a = _bench(tmp_path / "a", 2, ["--timed-only"])
-    jb, b = _bench(tmp_path / "b", 2)
-    jc, c = _bench(tmp_path / "c", 3, ["--timed-only"])
+    """Three runs of the same seeded configuration: two timed steps with nothing behind them (the plain run), two timed steps
+    followed by bench.py's untimed passes (``--full``: six more optimizer steps, the dump must not see them), and three timed steps."""
+    ja, a = _bench(tmp_path / "a", 2)
+    jb, b = _bench(tmp_path / "b", 2, ["--full"])
+    jc, c = _bench(tmp_path / "c", 3)
+    # the passes that take steps of their own ran behind --full and nowhere else
+    assert jb["kernels_isolated"] and jb["roofline_hbm"]["per_entry_point"] and jb["roofline"]["isolated"]["launches"] > 0
+    assert not {"kernels_isolated", "roofline_hbm", "roofline", "cpu_baseline", "forward_only", "rv_waymo", "loss_first_step"} & (set(ja) | set(jc))
+    assert ja["value"] > 0 and ja["unit"] == "sweeps/s" and ja["higher_is_better"] is True and ja["dtype"] == "bf16" and ja["ms_per_step"] > 0
     assert set(a) == set(b) == set(c) and "loss" in a and any(k.startswith("grad.") for k in a) and any(k.startswith("param.") for k in a)
     assert sum(v.nbytes for v in a.values()) <= 64 << 20
     assert float(a["loss"]) == pytest.approx(ja["config"]["loss"], rel=1e-6)

@@ -393,6 +393,17 @@ def test_bench_gpus_flag_launches_the_ranks_itself():
     assert "[bench launcher]" not in one.stderr and "needs an MI355X" in one.stderr
 
 
+def test_bench_full_is_an_option_and_off_by_default():
+    """A plain ``bench.py --gpus 1 --steps N --warmup W`` is the lean run; the measurements that take runs of their own are behind ``--full``,
+    which the options that narrow them (and ``--timed-only``, which the profiler scripts give) may accompany."""
+    import bench
+
+    assert bench.parse_args(["--gpus", "1", "--steps", "10", "--warmup", "3"]).full is False
+    a = bench.parse_args(["--full", "--no-extra", "--no-cpu-baseline", "--dump-outputs", "d"])
+    assert a.full is True and a.no_extra and a.no_cpu_baseline and a.dump_outputs == "d" and (a.steps, a.warmup) == (10, 3)
+    assert bench.parse_args(["--timed-only"]).full is False
+
+
 def _gfx950_code_objects(path):
     """The gfx950 code objects of a HIP shared library (the clang offload bundles of its .hip_fatbin section)."""
     import re
