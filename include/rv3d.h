@@ -809,6 +809,60 @@ int rv_detection_loss_multilevel_backward_aff(const rvLossEntry* host_entries, i
                                               const float* const* host_affinity_maps, const double* sums, float grad_scale,
                                               rvStream stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Detection evaluation: matching, AP, ATE / ASE / AOE, CDS with the AV2 sensor-dataset metric definitions (csrc/evaluate.hip).
+ * The reference calls av2's CPU evaluator (nn/arch/detector.py:457-479); av2 is not part of the reference tree, so -- as for rv_wnms --
+ * the semantics are DECLARED here: they restate the published AV2 detection metric and are not pinned against av2's binaries.
+ * Pinned to the reference: max_range_m 150 / inf / 55 (datasets/__init__.py:27-39), the detections' range filter on the centre norm
+ * (detector.py:573-584), the ground-truth filter num_interior_pts > 0 (prototype/loader.py:583-589) and ASE's IoU
+ * prod(min(lwh)) / prod(max(lwh)) (math/ops/iou.py:50-55).
+ *
+ * Rows are (n,10) f32 [tx_m, ty_m, tz_m, length_m, width_m, height_m, qw, qx, qy, qz]; yaw of a row = 2 atan2(qz, qw), in fp64.
+ * Per (sweep, category) segment:
+ *   1. evaluated ground truth: gt_valid != 0 (num_interior_pts > 0; NULL = all) and norm2 <= max_range_m^2;
+ *   2. evaluated detections: norm2 <= max_range_m^2, in score order, the first `max_num_dts` of them;
+ *      norm2 = ((x*x + y*y) + z*z) in fp64 from the fp32 centre, unfused -- every comparison below is on such squares, so that
+ *      the flags are bit-reproducible against NumPy;
+ *   3. every evaluated detection picks ITS nearest evaluated ground truth (squared centre distance d2 = ((dx*dx + dy*dy) + dz*dz),
+ *      fp64 differences of the fp32 centres; ties: the ground truth that comes first in the segment).  A ground truth picked by several
+ *      detections goes to the first of them in score order; the others are unmatched (they do not fall through to their second-nearest);
+ *   4. tp[t] = matched and d2 <= thresholds_m[t]^2;
+ *   5. matched and d2 <= tp_threshold_m^2: err = [ATE = sqrt(d2), ASE = 1 - prod(min(lwh_a, lwh_b)) / prod(max(lwh_a, lwh_b)),
+ *      AOE = |yaw_dt - yaw_gt| wrapped to [0, pi]], computed in fp64 and rounded to fp32; NaN otherwise.
+ *
+ * rv_eval_match -- ONE launch, n_segments + 1 workgroups, asynchronous, no workspace.  The caller orders the rows: dt_order (n_dt) i64
+ * lists the detection rows by (segment ascending, score descending, ties in input order), dt_offsets (n_segments + 1) i64 bounds the
+ * segments in that list; rows before dt_offsets[0] or from dt_offsets[n_segments] on belong to no segment and are not evaluated.
+ * gt_order / gt_offsets: the same for the ground truth, by (segment, input order).  All of them are DEVICE arrays (the grid does not
+ * depend on their contents; offsets are clamped to the row counts and an order entry that names no row is skipped).  No bound on the
+ * ground truth of a segment (staged through LDS in chunks); max_num_dts <= RV_EVAL_MAX_DTS; n_thresholds <= RV_EVAL_MAX_THRESHOLDS;
+ * thresholds_m is a HOST array read at call time.  Outputs in INPUT row order, every element written: dt_evaluated (n_dt) u8,
+ * tp (n_dt, n_thresholds) u8, err (n_dt, 3) f32, matched_gt (n_dt) i32 (ground-truth row or -1), gt_evaluated (n_gt) u8.  Claims are
+ * resolved with an integer atomicMin in LDS: the result does not depend on scheduling.
+ *
+ * rv_eval_summarize -- from the rows of all sweeps, ordered by (category ascending, score descending, ties in accumulation order),
+ * evaluated rows only in [cat_offsets[c], cat_offsets[c + 1]) (DEVICE, n_categories + 1, i64; rows beyond cat_offsets[n_categories]
+ * are ignored), flags (n_rows, n_thresholds) u8 = tp, err (n_rows, 3) f32, n_gt (n_categories) i64 (DEVICE) = evaluated ground truth:
+ *   per category and threshold: tp = cumsum(flag), recall = tp / n_gt, precision = tp / (index + 1), made non-increasing from the
+ *   right; sampled at linspace(0, 1, num_recall_samples) by linear interpolation as numpy.interp does it (left = precision[0],
+ *   right = 0); AP_t = mean of the samples, 0 for a category without evaluated ground truth or detections; AP = mean over t;
+ *   ATE / ASE / AOE = mean of the err columns over the rows where they are not NaN, else (tp_threshold_m, default_ase, default_aoe);
+ *   CDS = AP * mean(1 - min(ATE / tp_threshold_m, 1), 1 - min(ASE, 1), 1 - min(AOE / pi, 1)).
+ * table (n_categories + 1, 5) f64 [AP, ATE, ASE, AOE, CDS], last row = column means over the categories; ap_per_threshold
+ * (n_categories, n_thresholds) f64.  fp64 throughout, sums in a fixed order (bit-identical from run to run).  Two launches (one
+ * workgroup per (category, threshold); one workgroup for the table), asynchronous.  workspace: rv_eval_summarize_workspace_bytes
+ * (12 bytes per row and threshold), 8-byte aligned, need not be initialised.  n_rows < 2^31. */
+#define RV_EVAL_MAX_THRESHOLDS 8
+#define RV_EVAL_MAX_DTS 1024
+int rv_eval_match(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
+                  const uint8_t* gt_valid, const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments,
+                  const double* host_thresholds_m, int32_t n_thresholds, double tp_threshold_m, double max_range_m, int32_t max_num_dts,
+                  uint8_t* dt_evaluated, uint8_t* tp, float* err, int32_t* matched_gt, uint8_t* gt_evaluated, rvStream stream);
+int64_t rv_eval_summarize_workspace_bytes(int64_t n_rows, int32_t n_categories, int32_t n_thresholds);
+int rv_eval_summarize(const uint8_t* flags, const float* err, const int64_t* cat_offsets, const int64_t* n_gt, int64_t n_rows,
+                      int32_t n_categories, int32_t n_thresholds, double tp_threshold_m, int32_t num_recall_samples, double default_ase,
+                      double default_aoe, void* workspace, double* table, double* ap_per_threshold, rvStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,140 @@
+"""Detection evaluation, the part that needs no GPU: the NumPy restatement of the declared semantics (``tests/eval_ref.py``) against
+the hand-computed cases of ``tests/golden/eval_cases.json``, the exports of both builds, the configuration factory and the
+no-CPU-fallback contract of ``DetectionEvaluator``."""
+
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import eval_ref as ref
+
+CASES = ref.load_cases()
+EVAL_SYMBOLS = ("rv_eval_match", "rv_eval_summarize", "rv_eval_summarize_workspace_bytes")
+
+
+def _cfg(n_cat=1, **kw):
+    from range_view_3d_detection_amd.evaluation import DetectionCfg
+
+    return DetectionCfg(categories=tuple(f"C{i}" for i in range(n_cat)), **kw)
+
+
+def check_case(case, out, table):
+    """``out`` / ``table`` (category rows, then the average row) against a hand-computed case: flags exact, numbers to 1e-6."""
+    exp = case["expect"]
+    for key in ("evaluated", "tp", "matched_gt", "gt_evaluated"):
+        assert np.array_equal(np.asarray(out[key]), np.asarray(exp[key])), (case["name"], key)
+    assert np.allclose(np.asarray(out["err"], np.float64), exp["err"], rtol=0, atol=1e-6, equal_nan=True), case["name"]
+    want = np.asarray(exp["table"], np.float64)
+    assert np.allclose(table[:-1], want, rtol=0, atol=1e-6), (case["name"], table)
+    assert np.allclose(table[-1], want.mean(0), rtol=0, atol=1e-6), case["name"]
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_restatement_equals_the_hand_computed_cases(case):
+    out, _, table, _ = ref.evaluate_ref(case["dts"], case["scores"], case["dt_sweep"], case["dt_cat"], case["gts"], case["gt_valid"],
+                                        case["gt_sweep"], case["gt_cat"], case["n_sweeps"], case["n_cat"], _cfg(case["n_cat"]))
+    check_case(case, out, table)
+
+
+def test_the_cases_cover_what_the_declaration_singles_out():
+    by_name = {c["name"]: c for c in CASES}
+    assert {"exact", "shared_nearest", "exactly_two_metres", "range_boundary", "cap", "no_interior_points",
+            "category_without_detections", "yaw_wrap"} <= set(by_name)
+    # the loser of `shared_nearest` has a second ground truth within the widest threshold, and still fails everywhere
+    c = by_name["shared_nearest"]
+    d = np.linalg.norm(c["dts"][1, :3].astype(np.float64) - c["gts"][1, :3], axis=-1)
+    assert d <= 4.0 and not np.asarray(c["expect"]["tp"])[1].any()
+    # the dropped row of `range_boundary` is the very next fp32 above 150
+    x = by_name["range_boundary"]["dts"][:, 0]
+    assert x[0] == np.float32(150) and x[1] == np.nextafter(np.float32(150), np.float32(np.inf))
+    assert len(by_name["cap"]["dts"]) == 130 and int(np.sum(by_name["cap"]["expect"]["evaluated"])) == 100
+
+
+def test_sort_key_orders_like_a_stable_descending_argsort():
+    from range_view_3d_detection_amd.evaluation.detection import _sort_key
+
+    g = np.random.default_rng(5)
+    scores = np.round(g.random(4000), 2).astype(np.float32)  # many ties
+    scores[:40] = [0.0, -0.0, 1e-40, -1e-40] * 10  # signed zeros tie, denormals do not
+    scores[40:60] = -scores[60:80]
+    seg = g.integers(0, 7, 4000)
+    order = torch.sort(_sort_key(torch.from_numpy(seg), torch.from_numpy(scores)), stable=True)[1].numpy()
+    want = np.concatenate([np.nonzero(seg == s)[0][np.argsort(-scores[seg == s], kind="stable")] for s in range(7)])
+    assert np.array_equal(order, want)
+
+
+@pytest.mark.parametrize("tag", ["bf16", "f16"])
+def test_both_builds_export_the_evaluation_entry_points(tag):
+    from range_view_3d_detection_amd import _lib
+
+    handle = _lib.load(tag)
+    assert set(EVAL_SYMBOLS) <= set(_lib.declared_symbols())
+    assert all(hasattr(handle, s) for s in EVAL_SYMBOLS)
+    # 12 bytes per row and threshold + the per-category sums, each part rounded up to 256 bytes
+    assert handle.rv_eval_summarize_workspace_bytes(_lib.i64(1000), _lib.i32(26), _lib.i32(4)) == 32000 + 16128 + 1024
+    assert handle.rv_eval_summarize_workspace_bytes(_lib.i64(-1), _lib.i32(26), _lib.i32(4)) == 0
+
+
+def test_argument_checks_need_no_device():
+    """The entry points reject what they cannot run before they launch anything."""
+    import ctypes
+
+    from range_view_3d_detection_amd import _lib as L
+
+    thr = (ctypes.c_double * 9)(*([1.0] * 9))
+    null = ctypes.c_void_p(0)
+    with pytest.raises(L.RvError, match="thresholds"):
+        L.call("rv_eval_match", null, null, null, L.i64(0), null, null, null, null, L.i64(0), L.i32(1), thr, L.i32(9), L.f64(2.0), L.f64(150.0),
+               L.i32(100), null, null, null, null, null, null)
+    with pytest.raises(L.RvError, match="max_num_dts"):
+        L.call("rv_eval_match", null, null, null, L.i64(0), null, null, null, null, L.i64(0), L.i32(1), thr, L.i32(4), L.f64(2.0), L.f64(150.0),
+               L.i32(L.EVAL_MAX_DTS + 1), null, null, null, null, null, null)
+    with pytest.raises(L.RvError, match="null"):
+        L.call("rv_eval_summarize", null, null, null, null, L.i64(0), L.i32(1), L.i32(4), L.f64(2.0), L.i32(100), L.f64(1.0), L.f64(math.pi),
+               null, null, null, null)
+
+
+def test_detection_cfg_and_factory():
+    from range_view_3d_detection_amd._lib import RvError
+    from range_view_3d_detection_amd.evaluation import DetectionCfg, detection_cfg_factory
+
+    cfg = DetectionCfg()
+    assert cfg.affinity_thresholds_m == (0.5, 1.0, 2.0, 4.0) and cfg.tp_threshold_m == 2.0 and cfg.max_range_m == 150.0
+    assert cfg.max_num_dts_per_category == 100 and cfg.num_recall_samples == 100 and cfg.metrics_defaults == (2.0, 1.0, math.pi)
+    assert detection_cfg_factory("av2", ["B", "A"]).max_range_m == 150.0
+    assert detection_cfg_factory("waymo", ["A"]).max_range_m == math.inf
+    assert detection_cfg_factory("nuscenes-mini", ["A"]).max_range_m == 55.0
+    assert detection_cfg_factory("AV2", ["B", "A", "B"]).categories == ("A", "B")
+    with pytest.raises(RvError):
+        detection_cfg_factory("kitti", ["A"])
+
+
+def test_update_on_cpu_tensors_raises():
+    from range_view_3d_detection_amd._lib import RvError
+    from range_view_3d_detection_amd.evaluation import DetectionEvaluator, evaluate
+
+    ev = DetectionEvaluator(_cfg(2), ["C0", "C1"])
+    with pytest.raises(RvError, match="no CPU fallback"):
+        ev.update(torch.zeros(3, 10), torch.zeros(3), torch.zeros(3), torch.zeros(3), torch.zeros(0, 13, dtype=torch.float64))
+    with pytest.raises(RvError, match="before any update"):
+        ev.compute()
+    with pytest.raises(RvError, match="no CPU fallback"):
+        evaluate(None, None, _cfg(1), device="cpu")
+    with pytest.raises(RvError, match="categories is empty"):
+        DetectionEvaluator(_cfg(0), [])
+
+
+def test_class_numbering_follows_the_task_table():
+    """Annotation rows carry (task_id, offset); the head numbers classes task after task (``RangeDecoder.decode``)."""
+    from range_view_3d_detection_amd.evaluation.detection import _task_bases
+
+    tasks = {0: ["REGULAR_VEHICLE"], 1: ["BOLLARD", "PEDESTRIAN"], 2: ["BUS"]}
+    names, bases = _task_bases(["REGULAR_VEHICLE", "BOLLARD", "PEDESTRIAN", "BUS"], tasks)
+    assert bases == {0: 0, 1: 1, 2: 3} and names[bases[1] + 1] == "PEDESTRIAN"
+    frame = {"category": list(names), "task_id": [0, 1, 1, 2], "offset": [0, 0, 1, 0]}
+    assert _task_bases(frame, None) == (names, bases)
+    assert _task_bases(["A", "B"], None)[1] == {0: 0}
