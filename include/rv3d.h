@@ -863,6 +863,95 @@ int rv_eval_summarize(const uint8_t* flags, const float* err, const int64_t* cat
                       int32_t n_categories, int32_t n_thresholds, double tp_threshold_m, int32_t num_recall_samples, double default_ase,
                       double default_aoe, void* workspace, double* table, double* ap_per_threshold, rvStream stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Detection evaluation with the Waymo Open Dataset metric definitions: rotated BEV / 3-D IoU, maximum-weight ("Hungarian") matching,
+ * AP and APH per object type, range and difficulty level (csrc/evaluate_waymo.hip).  The reference hands its detections to
+ * waymo_open_dataset's evaluator (evaluation/evaluate.py:367-466); that library (and TensorFlow) is not part of the reference tree,
+ * so -- as for rv_eval_match -- the semantics are DECLARED here and are not pinned against its binaries.  Pinned to the reference: the
+ * ground-truth filter and the level rule (evaluate.py:325-333), the object types (:68), frames = the sweeps that have ground truth
+ * (:382-389), yaw from the quaternion (:269-286) rounded to fp32 with the box (:407-408), the configuration (:289-319) and the
+ * result layout (:70-243).  The declared choices, so that a mismatch with another implementation can be traced to one of them:
+ * the weight quantum 1000, the tie rule of the search, matching by prefix insertion, "ignored at this level", the AP integration.
+ *
+ * Rows are boxes (n,7) f32 [x, y, z, length, width, height, yaw].  A SEGMENT is one (sweep, object type): segment = sweep * 4 + type - 1,
+ * type 1 VEHICLE, 2 PEDESTRIAN, 3 SIGN, 4 CYCLIST.  The caller orders the rows as for rv_eval_match: dt_order (n_dt) i64 lists the
+ * detections by (segment ascending, score descending, ties in input order), dt_offsets (n_segments + 1) i64 bounds the segments in that
+ * list, gt_order / gt_offsets the ground truth by (segment, input order); all DEVICE arrays, offsets clamped to the row counts, an order
+ * entry that names no row is skipped, rows outside every segment are not evaluated.  For another order of a segment's detections the
+ * result is not defined, but every kernel terminates and stays inside its buffers.
+ *
+ * IoU of a pair (both fp32, unfused).  BEV: rv_rotated_iou of the rectangles [x - l/2, y - w/2, x + l/2, y + w/2, yaw] (halves formed
+ * as 0.5f * l), bit for bit.  3-D: inter = area * max(0, min(za + ha/2, zb + hb/2) - max(za - ha/2, zb - hb/2)) with `area` the
+ * intersection area that BEV IoU was formed from, vol = (l * w) * h, iou = inter / (vol_a + vol_b - inter); 0 where a volume or
+ * the union is not positive.  A pair whose footprints' circumscribed circles are more than 0.05 % apart is 0 in both without clipping
+ * (the clip returns exactly 0 for it as well).
+ *
+ * Problems.  One per (segment, box type in {BEV, 3-D}, shard in {all ranges, [0,30), [30,50), [50,inf) m}).  A row belongs to a range
+ * shard by ITS OWN centre: r2 = ((x*x + y*y) + z*z) in fp64 from the fp32 centre against 900 and 2500, lower bound inclusive -- a
+ * detection at 29.9 m on ground truth at 30.1 m is matched in "all ranges" and is a false positive in [0,30).  Ground truth takes part
+ * with gt_level != 0 (the caller writes 0 for num_interior_pts <= 0), whatever its level.  Cutoffs: c_k = fp32(k * 0.01), k = 0 .. 99,
+ * c_100 = 1; a detection takes part at the cutoffs c_k <= score (fp32 compare; a NaN or negative score at none).
+ *
+ * Weights.  w(d, g) = min(1000, floor(1000 * iou)) (fp32 product) if iou >= iou_thresholds[type] (fp32 compare), else 0: an integer.
+ * A matching maximises the sum of w; a pair of weight 0 is no match.
+ *
+ * Which optimum, and every cutoff in one pass.  The detections are inserted one at a time in score order, each by ONE shortest-
+ * augmenting-path search with potentials on the integer costs -w (Jonker-Volgenant form), with one always-free zero-cost column
+ * "unmatched".  Row potentials u and column potentials v start at 0 and are carried from row to row.  Search for row r: every column
+ * unused, minv = +inf; i0 = r.  Step: for every unused column j, cur = -w(i0, j) - u[i0] - v[j]; if cur < minv[j], minv[j] = cur and j
+ * remembers the column i0 was reached from; "unmatched" likewise keeps dmin = min(dmin, -u[i0]) (strict <: the first row that reached
+ * the value).  delta = the least of dmin and the minv of the unused columns: ties go to "unmatched" first, then to the lowest
+ * ground-truth position.  u[r] and the u of the owner of every used column grow by delta, v of every used column falls by delta, minv of
+ * every unused column and dmin fall by delta.  If "unmatched" won, the search ends there: the row that reached it becomes unmatched
+ * (it is never moved again) and every row before it on the path takes the column it was reached from.  Otherwise the winning column
+ * becomes used; if it has no owner the path is handed down the same way, else i0 = its owner and the next step follows.  All arithmetic
+ * is integer, so the sequential procedure defines the result exactly.  The matching at cutoff c_k is the state after every row with
+ * score >= c_k has been inserted: by the invariant of the method it is a maximum-weight matching of exactly those rows, so it differs
+ * from a from-scratch solve per cutoff only in WHICH of several equally good assignments is reported.
+ * Compaction: a row without any pair of weight > 0 sees cost -v[j] >= 0 = the cost of "unmatched" at every column (v never rises above 0),
+ * so its search ends in its first step with delta 0 and changes nothing; a column without such a pair keeps v = 0 and costs -u[i0] from
+ * every row, never less than dmin, so with ties going to "unmatched" it is never used.  Neither ever enters a path: the kernel leaves
+ * them out of the search (keeping the order of the rest) and counts them directly, with the identical result.
+ *
+ * Counts per (box type, breakdown row, level L in {1, 2}, cutoff k), summed over the sweeps, int64 [TP, FP, FN, heading]:
+ * TP = matched pairs whose ground truth has level <= L; a detection matched to ground truth of level > L is ignored (neither TP nor
+ * FP); FP = inserted detections without a match; FN = ground truth of level <= L without a match; heading = sum over the TPs of
+ * rint(2^40 * (1 - d / pi)), d = fmod(|yaw_d - yaw_g|, 2 pi) folded to [0, pi] (2 pi - d above pi), fp64 (0 for a NaN).  Every
+ * accumulator is an integer: the tables do not depend on how the sweeps are split into calls, on scheduling or on the number of ranks.
+ * Breakdown rows: 0 .. 3 the types over all ranges, 4 + 3 (type - 1) + (shard - 1) the type in a range shard.
+ *
+ * rv_waymo_iou -- the (BEV, 3-D) IoU of every (detection, ground truth) pair of a segment into `workspace`, two launches, asynchronous.
+ * Layout: pair_off (n_segments + 1) i64 at byte 0, then, 256-byte aligned, (pairs, 2) f32; the pair (i-th detection, j-th ground truth
+ * of segment s, in the orders above) is at pair_off[s] + i * n_gt(s) + j.  A segment beyond a limit has no pairs.  n_segments is any
+ * positive number here (the type only enters rv_waymo_match).  workspace: rv_waymo_match_workspace_bytes, 8-byte aligned.
+ *
+ * rv_waymo_match -- ONE launch, n_sweeps * 32 workgroups (one per problem), asynchronous, on the workspace rv_waymo_iou filled for the same
+ * rows (n_segments = 4 * n_sweeps).  scores (n_dt) f32; gt_level (n_gt) u8; sweep_valid (n_sweeps) u8 or NULL: a sweep flagged 0 is no
+ * frame (no ground truth left) and none of its rows is counted.  iou_thresholds: 5 HOST floats indexed by type, read at call time.
+ * Adds to `tables` (2, 16, 2, 101, 4) i64 (box type, breakdown row, level - 1, cutoff, [TP, FP, FN, heading]; the caller zeroes it once)
+ * with 64-bit integer atomics and to `errors` (4) i32: [0] segments with more than RV_WAYMO_MAX_DTS detections, [1] with more than
+ * RV_WAYMO_MAX_GTS ground truth (such a segment is not evaluated at all: nothing is truncated), [2] segments whose pair offsets do not
+ * fit the workspace, [3] searches that hit their iteration bound (cannot happen; the row stays unmatched).
+ *
+ * rv_waymo_summarize -- tables -> out (2, 32, 2) f64 (box type, result row, [AP, APH]), one launch.  Result rows: the 4 types x 2 levels
+ * over all ranges (type-major), then per type the 3 range shards x 2 levels.  Per row: p_k = TP / (TP + FP), r_k = TP / (TP + FN), 0 when
+ * the denominator is 0; for APH both numerators are heading * 2^-40.  Precision is made non-increasing towards higher recall (running
+ * maximum from k = 0 upwards), AP = sum over k = 100 .. 0 of (r_k - r_prev) * p_k from r_prev = 0, fp64, in that order. */
+#define RV_WAYMO_MAX_DTS 1024
+#define RV_WAYMO_MAX_GTS 1024
+#define RV_WAYMO_MAX_SWEEPS 65536
+#define RV_WAYMO_NUM_CUTOFFS 101
+#define RV_WAYMO_NUM_BREAKDOWN_ROWS 16
+#define RV_WAYMO_NUM_RESULT_ROWS 32
+int64_t rv_waymo_match_workspace_bytes(int64_t n_dt, int64_t n_gt, int32_t n_segments);
+int rv_waymo_iou(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
+                 const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments, void* workspace, rvStream stream);
+int rv_waymo_match(const float* dts, const float* scores, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt,
+                   const float* gts, const uint8_t* gt_level, const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt,
+                   const uint8_t* sweep_valid, int32_t n_sweeps, const float* host_iou_thresholds, const void* workspace, int64_t* tables,
+                   int32_t* errors, rvStream stream);
+int rv_waymo_summarize(const int64_t* tables, double* out, rvStream stream);
+
 #ifdef __cplusplus
 }
 #endif

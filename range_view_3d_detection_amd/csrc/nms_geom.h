@@ -1,5 +1,5 @@
-// Rotated-BEV-IoU of two boxes [x1, y1, x2, y2, ry] (shared by nms.hip and nms2.hip; both are compiled with
-// -ffp-contract=off so that the result matches oracle/c/oracle.c bit for bit).
+// Rotated-BEV-IoU of two boxes [x1, y1, x2, y2, ry] (shared by nms.hip, nms2.hip, softassign.hip and evaluate_waymo.hip; all are
+// compiled without fused multiply-add contraction so that the result matches oracle/c/oracle.c bit for bit).
 #pragma once
 #include "common.h"
 
@@ -23,11 +23,9 @@ __device__ void corners(const float* b, float s, float c, Pt* out) {
     }
 }
 
-// rectangle A clipped by the four half-planes of rectangle B (Sutherland-Hodgman), shoelace area
-__device__ float rotated_iou(const float* a, float sa, float ca, const float* b, float sb, float cb) {
-    const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
-    const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
-    if (!(area_a > 0.0f) || !(area_b > 0.0f)) return 0.0f;
+// rectangle A clipped by the four half-planes of rectangle B (Sutherland-Hodgman), shoelace area: the area of the intersection, 0
+// when fewer than three vertices are left
+__device__ __forceinline__ float rotated_intersection(const float* a, float sa, float ca, const float* b, float sb, float cb) {
     Pt pa[4], pb[4], poly[16], tmp[16];
     corners(a, sa, ca, pa);
     corners(b, sb, cb, pb);
@@ -58,10 +56,26 @@ __device__ float rotated_iou(const float* a, float sa, float ca, const float* b,
         const Pt p = poly[k], q = poly[(k + 1 == n) ? 0 : k + 1];
         twice += (p.x - poly[0].x) * (q.y - poly[0].y) - (p.y - poly[0].y) * (q.x - poly[0].x);
     }
-    const float inter = 0.5f * fabsf(twice);
+    return 0.5f * fabsf(twice);
+}
+
+// IoU of the two rectangles and, through `inter`, the intersection area it was formed from (0 where the IoU is 0 by one of the early
+// exits; an empty intersection leaves early: 0 / uni would be the same +0)
+__device__ __forceinline__ float rotated_iou_inter(const float* a, float sa, float ca, const float* b, float sb, float cb, float& inter) {
+    inter = 0.0f;
+    const float area_a = (a[2] - a[0]) * (a[3] - a[1]);
+    const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
+    if (!(area_a > 0.0f) || !(area_b > 0.0f)) return 0.0f;
+    inter = rotated_intersection(a, sa, ca, b, sb, cb);
+    if (inter == 0.0f) return 0.0f;
     const float uni = area_a + area_b - inter;
     if (!(uni > 0.0f)) return 0.0f;
     return inter / uni;
+}
+
+__device__ float rotated_iou(const float* a, float sa, float ca, const float* b, float sb, float cb) {
+    float inter;
+    return rotated_iou_inter(a, sa, ca, b, sb, cb, inter);
 }
 
 }  // namespace

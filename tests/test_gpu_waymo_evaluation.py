@@ -1,0 +1,272 @@
+"""The Waymo detection metric on the device (``rv_waymo_iou`` / ``rv_waymo_match`` / ``rv_waymo_summarize``,
+``evaluation.WaymoDetectionEvaluator`` / ``evaluate_waymo``) against the hand-worked cases of ``tests/golden/waymo_eval_cases.json``
+and the NumPy restatement of the declared semantics (``tests/waymo_eval_ref.py``).
+
+Bar: the IoU is fp32 clipping against float64 clipping (1e-5 for centres within 30 m: the corners are rounded at the centre's
+magnitude), its BEV column is ``rv_rotated_iou``'s bit for bit; the count tables fed the device's own IoU are EXACT (integers); the
+values agree with the restatement to 1e-12 and are bit-identical from run to run and under any split of the sweeps into ``update`` calls.
+"""
+
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import waymo_eval_ref as ref
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+NAMES = ["VEHICLE", "PEDESTRIAN", "SIGN", "CYCLIST"]  # class index = type - 1
+
+
+def _dev(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    return t if dtype is None else t.to(dtype)
+
+
+def _accumulate(scene):
+    """A scene (``waymo_eval_ref.count_tables`` layout) through ``accumulate``: tables, errors, and the IoU tables per segment."""
+    from range_view_3d_detection_amd.evaluation import waymo as W
+
+    n_seg = 4 * scene["n_sweeps"]
+    tables = torch.zeros(W.TABLE_SHAPE, dtype=torch.int64, device=DEV)
+    errors = torch.zeros(4, dtype=torch.int32, device=DEV)
+    ws = W.accumulate(_dev(scene["dts"]), _dev(scene["scores"]), _dev(scene["dt_sweep"] * 4 + scene["dt_type"] - 1), _dev(scene["gts"]),
+                      _dev(scene["gt_level"].astype(np.uint8)), _dev(scene["gt_sweep"] * 4 + scene["gt_type"] - 1), scene["n_sweeps"],
+                      W.WaymoDetectionCfg(), tables, errors)
+    pair_off, iou = W._workspace_views(ws, n_seg)
+    pair_off, iou = pair_off.cpu().numpy(), iou.cpu().numpy()
+    per_segment = {}
+    for (s, t), (d, g) in ref.segment_orders(scene).items():
+        seg = s * 4 + t - 1
+        assert pair_off[seg + 1] - pair_off[seg] == len(d) * len(g)
+        per_segment[(s, t)] = iou[pair_off[seg]:pair_off[seg + 1]].reshape(len(d), len(g), 2)
+    return tables.cpu().numpy(), errors.cpu().numpy(), per_segment
+
+
+def _random_box(g, centre_range, n):
+    return np.concatenate([g.uniform(-centre_range, centre_range, (n, 2)), g.uniform(-1, 1, (n, 1)), g.uniform(2, 6, (n, 1)), g.uniform(1, 3, (n, 1)),
+                           g.uniform(1, 3, (n, 1)), g.uniform(-math.pi, math.pi, (n, 1))], 1)
+
+
+def test_pairwise_iou_against_float64_clipping():
+    """200 segments of 10 x 10 pairs: per segment ten ground truths and ten detections derived from them one by one (identical,
+    contained, shifted, edge-touching, far away, yaw near +-pi, a zero-size box, random), every pair of the segment evaluated."""
+    from range_view_3d_detection_amd import _lib as L
+    from range_view_3d_detection_amd.evaluation import waymo as W
+
+    g = np.random.default_rng(20261016)
+    n_seg, per = 200, 10
+    gts = np.zeros((n_seg, per, 7))
+    dts = np.zeros((n_seg, per, 7))
+    for s in range(n_seg):
+        near = s < 50  # (identical boxes are held to 1e-6 where the centre is within 2 m)
+        gt = _random_box(g, 2 if near else 20, per)
+        gt[5, 6] = math.pi - g.uniform(0, 1e-4)
+        gt[6, 6] = -math.pi + g.uniform(0, 1e-4)
+        dt = gt.copy()
+        dt[1, 3:5] *= 0.5  # contained
+        dt[2, :2] += g.uniform(-1, 1, 2)
+        dt[3, 0] += gt[3, 3] * math.cos(gt[3, 6])
+        dt[3, 1] += gt[3, 3] * math.sin(gt[3, 6])  # shifted by its own length along its axis: edges touch
+        dt[4, :2] += 100.0
+        dt[5, 6] = -math.pi + g.uniform(0, 1e-4)
+        dt[6, 6] = math.pi - g.uniform(0, 1e-4)
+        dt[7, 3] = 0.0  # no area
+        dt[8] = _random_box(g, 2 if near else 20, 1)[0]
+        dt[9, 2] += g.uniform(-3, 3)  # height overlap only partial
+        gts[s], dts[s] = gt, dt
+    gts32, dts32 = gts.reshape(-1, 7).astype(np.float32), dts.reshape(-1, 7).astype(np.float32)
+    order = _dev(np.arange(n_seg * per))
+    off = _dev(np.arange(n_seg + 1) * per)
+    ws = W.pairwise_iou(_dev(dts32), order, off, _dev(gts32), order, off, n_seg)
+    pair_off, iou = W._workspace_views(ws, n_seg)
+    assert np.array_equal(pair_off.cpu().numpy(), np.arange(n_seg + 1) * per * per)
+    iou = iou.cpu().numpy()[:n_seg * per * per].reshape(n_seg, per, per, 2)
+    # the BEV column and rv_rotated_iou on the same rectangles
+    half = np.float32(0.5)
+
+    def rect(b):
+        return np.stack([b[:, 0] - half * b[:, 3], b[:, 1] - half * b[:, 4], b[:, 0] + half * b[:, 3], b[:, 1] + half * b[:, 4], b[:, 6]], 1)
+
+    full = torch.empty((n_seg * per, n_seg * per), dtype=torch.float32, device=DEV)
+    ra, rb = _dev(rect(dts32)), _dev(rect(gts32))
+    L.call("rv_rotated_iou", L.ptr(ra), L.i64(n_seg * per), L.ptr(rb), L.i64(n_seg * per), L.ptr(full), L.stream_ptr())
+    full = full.cpu().numpy().reshape(n_seg, per, n_seg, per)
+    worst, n_zero = 0.0, 0
+    for s in range(n_seg):
+        assert np.array_equal(iou[s, :, :, 0].view(np.uint32), full[s, :, s, :].view(np.uint32)), s
+        for i in range(per):
+            for j in range(per):
+                d, t = dts32[s * per + i], gts32[s * per + j]
+                want = ref.iou_pair(d, t)
+                worst = max(worst, abs(iou[s, i, j, 0] - want[0]), abs(iou[s, i, j, 1] - want[1]))
+                reach = 0.5 * (math.hypot(d[3], d[4]) + math.hypot(t[3], t[4]))
+                if math.hypot(d[0] - t[0], d[1] - t[1]) > reach + 0.01 or i == 7:
+                    assert iou[s, i, j, 0] == 0.0 and iou[s, i, j, 1] == 0.0, (s, i, j)
+                    n_zero += 1
+        if s < 50:
+            assert np.all(np.abs(iou[s, 0, 0] - 1.0) <= 1e-6), (s, iou[s, 0, 0])
+    assert worst <= 1e-5, worst
+    assert n_zero > 2000
+
+
+def _crowded_scene(g, n_sweeps, big):
+    """Per (sweep, type in {1, 2, 4}): ground truth partly in crowds of mutually overlapping boxes, detections drawn around them with
+    exact duplicates (equal weights) and scores on a coarse grid (ties); ``big`` = (sweep, type, detections, ground truths)."""
+    dts, scores, dt_s, dt_t, gts, lvl, gt_s, gt_t = [], [], [], [], [], [], [], []
+    for s in range(n_sweeps):
+        for t in (1, 2, 4):
+            m, n = int(g.integers(0, 40)), int(g.integers(0, 150))
+            if (s, t) == big[:2]:
+                n, m = big[2], big[3]
+            centres = g.uniform(-60, 60, (max(m // 6, 1), 2))
+            pick = g.integers(0, len(centres), m)
+            size = (4.5, 2.0, 1.6) if t == 1 else (0.9, 0.8, 1.7) if t == 2 else (1.8, 0.8, 1.7)
+            gt = np.concatenate([centres[pick] + g.normal(0, 0.15 * size[0], (m, 2)), g.normal(0, 0.2, (m, 1)), np.tile(size, (m, 1)) * g.uniform(0.9, 1.1, (m, 3)),
+                                 g.uniform(-math.pi, math.pi, (m, 1))], 1)
+            if m:
+                src = gt[g.integers(0, m, n)]
+                dt = src + np.concatenate([g.normal(0, 0.08 * size[0], (n, 2)), g.normal(0, 0.1, (n, 1)), g.normal(0, 0.05, (n, 3)), g.normal(0, 0.1, (n, 1))], 1)
+                same = g.random(n) < 0.15
+                dt[same] = src[same]
+                dup = g.random(n) < 0.1
+                dt[dup] = dt[g.integers(0, n, int(dup.sum()))]
+            else:
+                dt = _random_box(g, 60, n)
+            gts.append(gt), lvl.append(g.choice([0, 1, 1, 2], m)), gt_s.append(np.full(m, s)), gt_t.append(np.full(m, t))
+            dts.append(dt), scores.append(np.round(g.random(n) * 20) / 20), dt_s.append(np.full(n, s)), dt_t.append(np.full(n, t))
+    dts, gts = np.concatenate(dts).astype(np.float32), np.concatenate(gts).astype(np.float32)
+    pd, pg = g.permutation(len(dts)), g.permutation(len(gts))
+    return {"n_sweeps": n_sweeps, "dts": dts[pd], "scores": np.concatenate(scores).astype(np.float32)[pd], "dt_sweep": np.concatenate(dt_s).astype(np.int64)[pd],
+            "dt_type": np.concatenate(dt_t).astype(np.int64)[pd], "gts": gts[pg], "gt_level": np.concatenate(lvl).astype(np.uint8)[pg],
+            "gt_sweep": np.concatenate(gt_s).astype(np.int64)[pg], "gt_type": np.concatenate(gt_t).astype(np.int64)[pg]}
+
+
+def test_matching_equals_the_restatement_on_the_devices_own_iou():
+    """Every int64 of every table, 8 sweeps x 3 types, one problem with 1000 detections on 300 crowded ground truths (augmenting
+    paths longer than one edge), tied scores, duplicated boxes."""
+    from range_view_3d_detection_amd.evaluation import waymo as W
+
+    g = np.random.default_rng(7)
+    scene = _crowded_scene(g, 8, (3, 1, 1000, 300))
+    tables, errors, iou = _accumulate(scene)
+    assert not errors.any()
+    want = ref.count_tables(scene, iou=iou)
+    assert np.array_equal(tables, want), np.argwhere(tables != want)[:10]
+    assert tables[:, :, :, :, 0].sum() > 1000 and tables[:, :, :, :, 1].sum() > 1000
+    values = W.summarize(_dev(tables)).cpu().numpy()
+    assert np.allclose(values, ref.summarize(want), rtol=0, atol=1e-12)
+    assert values.max() <= 1.0 and values[0, 0, 0] > 0.05
+
+
+def _evaluator(scene, splits=1):
+    from range_view_3d_detection_amd.evaluation import WaymoDetectionEvaluator
+
+    ev = WaymoDetectionEvaluator(idx_to_category=NAMES, max_sweeps=scene["n_sweeps"])
+    ann = np.zeros((len(scene["gt_rows"]), 13))
+    ann[:, :10], ann[:, 11], ann[:, 12] = scene["gt_rows"], scene["gt_type"] - 1, scene["gt_sweep"]
+    for sweeps in np.array_split(np.arange(scene["n_sweeps"]), splits):
+        d, a = np.isin(scene["dt_sweep"], sweeps), np.isin(scene["gt_sweep"], sweeps)
+        ev.update(_dev(scene["dt_rows"][d]), _dev(scene["scores"][d]), _dev(scene["dt_type"][d] - 1, torch.float32), _dev(scene["dt_sweep"][d], torch.float32),
+                  _dev(ann[a]), _dev(scene["gt_npts"][a]), _dev(scene["gt_difficulty"][a]))
+    return ev
+
+
+def _values(table):
+    v = np.asarray(table.column("value").to_pylist()).reshape(2, 2, ref.N_RROWS)  # (AP / APH, box type, row)
+    return np.stack([v[0], v[1]], -1)
+
+
+CASES = ref.load_cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_hand_worked_cases(case):
+    ev = _evaluator(case)
+    table = ev.compute()
+    assert [tuple(r) for r in zip(*[table.column(c).to_pylist() for c in table.column_names[:6]])] == ref.layout()
+    ref.check_case(case, ev.tables().cpu().numpy(), _values(table))
+
+
+def test_split_invariance_and_repeatability():
+    g = np.random.default_rng(11)
+    scene = _crowded_scene(g, 6, (2, 2, 400, 60))
+    scene["dt_rows"], scene["gt_rows"] = ref.rows_from_yaw(scene["dts"]), ref.rows_from_yaw(scene["gts"])
+    scene["gt_npts"] = np.where(scene["gt_level"] == 0, 0, np.where(scene["gt_level"] == 2, 3, 50))
+    scene["gt_difficulty"] = np.zeros_like(scene["gt_npts"])
+    runs = [_evaluator(scene, splits) for splits in (1, 3, 1, 6)]
+    tables = [ev.tables().cpu().numpy() for ev in runs]
+    results = [ev.compute() for ev in runs]
+    for t, r in zip(tables[1:], results[1:]):
+        assert np.array_equal(t, tables[0]) and r.equals(results[0])
+    scene["dts"], scene["gts"] = ref.boxes_from_rows(scene["dt_rows"]), ref.boxes_from_rows(scene["gt_rows"])
+    assert tables[0][:, :, :, :, 0].sum() > 500
+    summary = runs[0].summary(["VEHICLE", "CYCLIST"], results[0])
+    assert len(summary) == 2 * 2 * 2 * 4 and [r[2] for r in summary] == ["CYCLIST"] * 16 + ["VEHICLE"] * 16 and all(r[3] == 1 for r in summary)
+    assert all(r[6] == round(r[6], 3) and 0 <= r[6] <= 100 for r in summary)
+
+
+def test_a_segment_beyond_the_limit_raises():
+    from range_view_3d_detection_amd import _lib as L
+
+    n = L.WAYMO_MAX_DTS + 1
+    scene = {"n_sweeps": 1, "dt_rows": ref.rows_from_yaw(np.tile([10, 0, 0, 4, 2, 2, 0], (n, 1))), "scores": np.linspace(0.1, 0.9, n).astype(np.float32),
+             "dt_type": np.ones(n, np.int64), "dt_sweep": np.zeros(n, np.int64), "gt_rows": ref.rows_from_yaw([[10, 0, 0, 4, 2, 2, 0]]),
+             "gt_type": np.ones(1, np.int64), "gt_sweep": np.zeros(1, np.int64), "gt_npts": np.asarray([10]), "gt_difficulty": np.asarray([0])}
+    ev = _evaluator(scene)
+    with pytest.raises(L.RvError, match="RV_WAYMO_MAX_DTS"):
+        ev.compute()
+
+
+def test_decoder_output_through_update_equals_the_offline_form(golden, tmp_path):
+    """``RangeDecoder.decode`` of the tiny model's eval outputs + annotations -> ``update`` (no synchronisation) -> ``compute`` equals
+    ``evaluate_waymo`` on the feather files ``write_detections`` wrote, read back; two tasks."""
+    import pyarrow as pa
+
+    from range_view_3d_detection_amd.evaluation import WaymoDetectionEvaluator, evaluate_waymo
+    from range_view_3d_detection_amd.math.ops.coding import DETECTION_COLUMNS, build_dataframe, write_detections
+    from range_view_3d_detection_amd.nn.decoders.range_decoder import RangeDecoder
+
+    t = golden("tiny_model")
+    logits, reg, cart, mask = t["eval/logits"], t["eval/regressands"], t["cart"], t["mask"]
+    B = logits.shape[0]
+    tasks = {0: ["CYCLIST", "PEDESTRIAN", "VEHICLE"], 1: ["SIGN"]}
+    names = tasks[0] + tasks[1]
+    mo = {1: {"cart": cart.to(DEV), "mask": mask.to(DEV), 0: {"logits": logits[:, :3].contiguous().to(DEV), "regressands": reg.to(DEV)},
+              1: {"logits": logits[:, 3:4].contiguous().to(DEV), "regressands": reg.to(DEV)}}}
+    post = {"num_pre_nms": 50000, "num_post_nms": 200, "nms_threshold": 0.3, "min_confidence": 0.1, "nms_mode": "HARD"}
+    params, scores, cats, bidx = RangeDecoder(True, False, [], [], []).decode(mo, post, tasks, use_nms=True)
+    assert params.shape[0] > 20
+    # ground truth: every third detection, moved a little; annotation rows as the loader lays them out
+    g = torch.Generator().manual_seed(7)
+    pick = torch.arange(0, params.shape[0], 3)
+    box = params[pick].double().cpu()
+    box[:, :3] += torch.randn(len(pick), 3, generator=g, dtype=torch.float64) * 0.1
+    cls = cats[pick].long().cpu()
+    ann = torch.cat([box, (cls == 3).double()[:, None], torch.where(cls == 3, 0, cls).double()[:, None], bidx[pick].double().cpu()[:, None]], 1)
+    npts = torch.arange(len(pick)) % 9  # 0: dropped, 1 .. 5: level 2, above: level 1
+    ev = WaymoDetectionEvaluator(idx_to_category=names, tasks=tasks)
+    ev.update(params, scores, cats, bidx, ann, npts, n_sweeps=B)  # (first call: library load, lookup tables)
+    ev.reset()
+    ann_d, npts_d = ann.to(DEV), npts.to(DEV)
+    torch.cuda.synchronize()
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        ev.update(params, scores, cats, bidx, ann_d, npts_d, n_sweeps=B)
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    online = ev.compute()
+    uuids = {"batch_index": list(range(B)), "log_id": [f"log{b // 2}" for b in range(B)], "timestamp_ns": [1000 + b for b in range(B)]}
+    paths = write_detections(build_dataframe(params, scores, cats, bidx, uuids, names), str(tmp_path), "run")
+    dts = pa.concat_tables([pa.ipc.open_file(p).read_all() for p in paths])
+    b = ann[:, 12].long().tolist()
+    gts = pa.table({**{c: pa.array(ann[:, j].float().numpy()) for j, c in enumerate(DETECTION_COLUMNS)},
+                    "category": [names[int(k)] for k in cls], "num_interior_pts": npts.tolist(), "difficulty_level": [0] * len(b),
+                    "log_id": [uuids["log_id"][i] for i in b], "timestamp_ns": [uuids["timestamp_ns"][i] for i in b]})
+    offline = evaluate_waymo(dts, gts, device=DEV)
+    assert offline.equals(online)
+    assert max(online.column("value").to_pylist()) > 0.05 and online.num_rows == 128

@@ -1,0 +1,186 @@
+"""The Waymo detection metric without a GPU: the NumPy restatement of the declared semantics (``tests/waymo_eval_ref.py``) against the
+hand-worked cases and against SciPy's optimum, the pinned rules and layout, and the C ABI's argument checks (nothing is launched)."""
+
+from __future__ import annotations
+
+import ctypes
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import waymo_eval_ref as ref
+
+CASES = ref.load_cases()
+
+
+@pytest.mark.parametrize("case", CASES, ids=[c["name"] for c in CASES])
+def test_restatement_reproduces_the_hand_worked_cases(case):
+    tables = ref.count_tables(case)
+    ref.check_case(case, tables, ref.summarize(tables))
+
+
+def test_cases_cover_the_declared_choices():
+    names = {c["name"] for c in CASES}
+    assert {"exact_hit", "vehicle_iou_exactly_at_threshold", "vehicle_iou_just_below_threshold", "lower_score_higher_iou", "chain_optimum_is_not_greedy",
+            "level_2_ground_truth", "no_interior_points_dropped", "sweep_without_ground_truth", "range_boundary", "bev_match_fails_in_3d",
+            "heading_flipped", "sign_and_type_without_detections"} <= names
+    at = next(c for c in CASES if c["name"] == "vehicle_iou_exactly_at_threshold")
+    iou = ref.iou_table(at["dts"], at["gts"])[0, 0]
+    assert iou[0] == np.float32(0.7) and iou[1] == np.float32(0.7) and ref.weights(iou, 0.7).tolist() == [700, 700]
+
+
+def _random_table(g, kind):
+    n, m = int(g.integers(1, 41)), int(g.integers(1, 41))
+    if kind == 0:
+        W = g.integers(0, 1001, (n, m))
+    elif kind == 1:
+        W = g.integers(500, 1001, (n, m)) * (g.random((n, m)) < 0.12)
+    elif kind == 2:
+        W = g.choice([0, 500, 700, 1000], (n, m), p=[0.6, 0.2, 0.1, 0.1])
+    else:
+        W = g.integers(500, 1001, (n, m)) * (g.random((n, m)) < 0.3)
+        W[g.random(n) < 0.3] = 0
+        W[:, g.random(m) < 0.3] = 0
+    return W.astype(np.int64)
+
+
+def test_every_prefix_is_a_maximum_weight_matching_and_compaction_changes_nothing():
+    from scipy.optimize import linear_sum_assignment
+
+    g = np.random.default_rng(2026)
+    longest = 0
+    for trial in range(400):
+        W = _random_table(g, trial % 4)
+        states = list(ref.insert_rows(W))
+        for k, match in enumerate(states):
+            sub = W[:k + 1]
+            rows, cols = linear_sum_assignment(sub, maximize=True)
+            pairs = [(r, c) for r, c in enumerate(match) if c >= 0]
+            assert sum(sub[r, c] for r, c in pairs) == sub[rows, cols].sum(), (trial, k)
+            assert len({c for _, c in pairs}) == len(pairs) and all(sub[r, c] > 0 for r, c in pairs), (trial, k)
+            if k:  # a matched ground truth stays matched: recall does not fall with the cutoff
+                assert set(states[k - 1][states[k - 1] >= 0]) <= set(match[match >= 0])
+                longest = max(longest, int(np.sum(states[k - 1] != match[:k])))
+        keep_r, keep_c = np.flatnonzero(W.any(1)), np.flatnonzero(W.any(0))
+        if len(keep_r) and len(keep_c):
+            compact = list(ref.insert_rows(W[np.ix_(keep_r, keep_c)]))[-1]
+            full = states[-1]
+            assert [int(keep_c[c]) if c >= 0 else -1 for c in compact] == full[keep_r].tolist(), trial
+            assert np.all(np.delete(full, keep_r) == -1)
+    assert longest >= 2  # insertions that moved earlier rows: augmenting paths longer than one edge were exercised
+
+
+def test_difficulty_rule_type_table_and_layout():
+    from range_view_3d_detection_amd.evaluation import waymo as W
+
+    npts = torch.tensor([0, 1, 5, 6, 100, 3, 0, 7])
+    given = torch.tensor([0, 0, 0, 0, 0, 1, 2, 2])
+    assert W.difficulty_levels(npts, given).tolist() == [0, 2, 2, 1, 1, 1, 0, 2]
+    assert W.difficulty_levels(npts).tolist() == [0, 2, 2, 1, 1, 2, 0, 1]
+    assert [ref.level_of(int(n), int(d)) for n, d in zip(npts, given)] == [0, 2, 2, 1, 1, 1, 0, 2]
+    assert W.OBJECT_TYPES == {"VEHICLE": 1, "PEDESTRIAN": 2, "SIGN": 3, "CYCLIST": 4} == ref.TYPES
+    assert W.WaymoDetectionCfg().iou_thresholds == (0.0, 0.7, 0.5, 0.5, 0.5)
+    layout = W.result_layout()
+    assert layout == ref.layout() and len(layout) == 128 and len(set(layout)) == 128
+    inf = math.inf
+    assert layout[:3] == [("AP", "BEV", "VEHICLE", 1, 0.0, inf), ("AP", "BEV", "VEHICLE", 2, 0.0, inf), ("AP", "BEV", "PEDESTRIAN", 1, 0.0, inf)]
+    assert layout[8:14] == [("AP", "BEV", "VEHICLE", 1, 0.0, 30.0), ("AP", "BEV", "VEHICLE", 2, 0.0, 30.0), ("AP", "BEV", "VEHICLE", 1, 30.0, 50.0),
+                            ("AP", "BEV", "VEHICLE", 2, 30.0, 50.0), ("AP", "BEV", "VEHICLE", 1, 50.0, inf), ("AP", "BEV", "VEHICLE", 2, 50.0, inf)]
+    assert layout[31] == ("AP", "BEV", "CYCLIST", 2, 50.0, inf) and layout[32] == ("AP", "3D", "VEHICLE", 1, 0.0, inf)
+    assert layout[64] == ("APH", "BEV", "VEHICLE", 1, 0.0, inf) and layout[127] == ("APH", "3D", "CYCLIST", 2, 50.0, inf)
+    # the kernel's result-row decoding, restated: breakdown rows 0 .. 3 the types, 4 + 3 (type - 1) + (shard - 1) the range shards
+    assert [ref.result_row(r) for r in (0, 1, 7, 8, 9, 10, 13, 14, 31)] == [(0, 0), (0, 1), (3, 1), (4, 0), (4, 1), (5, 0), (6, 1), (7, 0), (15, 1)]
+    assert ref.CUTOFFS[1] == np.float32(0.01) and ref.CUTOFFS[99] == np.float32(0.99) and ref.CUTOFFS[100] == 1 and len(ref.CUTOFFS) == 101
+    assert [ref.range_shard([x, 0, 0]) for x in (0.0, 29.9, 30.0, 49.99, 50.0, 1e4, float("nan"))] == [1, 1, 2, 2, 3, 3, 0]
+    # yaw as quat_to_yaw forms it
+    assert np.allclose(ref.boxes_from_rows(ref.rows_from_yaw([[1, 2, 3, 4, 5, 6, 0.7]]))[0], [1, 2, 3, 4, 5, 6, 0.7], atol=1e-6)
+    assert np.array_equal(W.boxes_from_rows(torch.from_numpy(ref.rows_from_yaw([[1, 2, 3, 4, 5, 6, -2.5]]))).numpy(),
+                          ref.boxes_from_rows(ref.rows_from_yaw([[1, 2, 3, 4, 5, 6, -2.5]])))
+
+
+SYMBOLS = ("rv_waymo_iou", "rv_waymo_match", "rv_waymo_match_workspace_bytes", "rv_waymo_summarize")
+
+
+def test_both_builds_export_the_entries_and_the_limits_agree():
+    import re
+
+    from range_view_3d_detection_amd import _lib as L
+
+    assert set(SYMBOLS) <= set(L.declared_symbols())
+    for tag in ("bf16", "f16"):
+        lib = L.load(tag)
+        for name in SYMBOLS:
+            assert hasattr(lib, name), (tag, name)
+    header = open(L.HEADER_PATH).read()
+    limits = {k: int(v) for k, v in re.findall(r"#define (RV_WAYMO_\w+) (\d+)", header)}
+    assert limits == {"RV_WAYMO_MAX_DTS": L.WAYMO_MAX_DTS, "RV_WAYMO_MAX_GTS": L.WAYMO_MAX_GTS, "RV_WAYMO_MAX_SWEEPS": L.WAYMO_MAX_SWEEPS,
+                      "RV_WAYMO_NUM_CUTOFFS": L.WAYMO_NUM_CUTOFFS, "RV_WAYMO_NUM_BREAKDOWN_ROWS": L.WAYMO_NUM_BREAKDOWN_ROWS,
+                      "RV_WAYMO_NUM_RESULT_ROWS": L.WAYMO_NUM_RESULT_ROWS}
+    assert L.WAYMO_MAX_DTS >= 1024 and L.WAYMO_MAX_GTS >= 1024  # RangeDecoder emits up to 1000 rows per class and sweep
+    lib = L.load()
+    assert lib.rv_waymo_match_workspace_bytes(L.i64(-1), L.i64(1), L.i32(4)) == 0 and lib.rv_waymo_match_workspace_bytes(L.i64(1), L.i64(1), L.i32(0)) == 0
+    small, capped = (lib.rv_waymo_match_workspace_bytes(L.i64(100), L.i64(m), L.i32(8)) for m in (10, 5000))
+    assert small >= 9 * 8 + 100 * 10 * 8 and capped >= 100 * L.WAYMO_MAX_GTS * 8 and capped < 100 * 5000 * 8
+
+
+def test_argument_checks_reject_before_anything_is_launched():
+    from range_view_3d_detection_amd import _lib as L
+
+    lib = L.load()
+    buf = (ctypes.c_int64 * 64)()  # (a host buffer: only ever checked for null / alignment, never dereferenced by a rejected call)
+    p, null, thr = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_void_p(0), (L.f32 * 5)(0.0, 0.7, 0.5, 0.5, 0.5)
+    odd = ctypes.c_void_p(ctypes.addressof(buf) + 4)
+
+    def rejected(name, *args, match):
+        assert getattr(lib, name)(*args) == 1, name
+        assert match in lib.rv_last_error().decode(), lib.rv_last_error()
+
+    iou = lambda **k: [k.get("dts", p), k.get("dt_order", p), k.get("dt_off", p), L.i64(k.get("n_dt", 4)), k.get("gts", p), k.get("gt_order", p),
+                       k.get("gt_off", p), L.i64(k.get("n_gt", 4)), L.i32(k.get("n_seg", 4)), k.get("ws", p), null]
+    rejected("rv_waymo_iou", *iou(n_dt=-1), match="n_dt")
+    rejected("rv_waymo_iou", *iou(n_seg=0), match="segments")
+    rejected("rv_waymo_iou", *iou(dt_off=null), match="null")
+    rejected("rv_waymo_iou", *iou(ws=null), match="null")
+    rejected("rv_waymo_iou", *iou(ws=odd), match="aligned")
+    rejected("rv_waymo_iou", *iou(dts=null), match="null detection")
+    rejected("rv_waymo_iou", *iou(gt_order=null), match="null ground-truth")
+    match = lambda **k: [k.get("dts", p), k.get("scores", p), p, k.get("dt_off", p), L.i64(k.get("n_dt", 4)), p, k.get("level", p), p, p,
+                         L.i64(k.get("n_gt", 4)), null, L.i32(k.get("n_sweeps", 1)), k.get("thr", thr), k.get("ws", p), k.get("tables", p),
+                         k.get("errors", p), null]
+    rejected("rv_waymo_match", *match(n_gt=-3), match="n_gt")
+    rejected("rv_waymo_match", *match(n_sweeps=0), match="sweeps")
+    rejected("rv_waymo_match", *match(n_sweeps=L.WAYMO_MAX_SWEEPS + 1), match="sweeps")
+    rejected("rv_waymo_match", *match(tables=null), match="null")
+    rejected("rv_waymo_match", *match(errors=null), match="null")
+    rejected("rv_waymo_match", *match(thr=null), match="null")
+    rejected("rv_waymo_match", *match(scores=null), match="null detection")
+    rejected("rv_waymo_match", *match(level=null), match="null ground-truth")
+    rejected("rv_waymo_match", *match(thr=(L.f32 * 5)(0.0, 1.7, 0.5, 0.5, 0.5)), match="threshold")
+    rejected("rv_waymo_summarize", null, p, null, match="null")
+    rejected("rv_waymo_summarize", p, null, null, match="null")
+
+
+def test_cpu_tensors_and_unknown_categories_raise():
+    import pyarrow as pa
+
+    from range_view_3d_detection_amd._lib import RvError
+    from range_view_3d_detection_amd.evaluation import WaymoDetectionCfg, WaymoDetectionEvaluator, evaluate_waymo
+    from range_view_3d_detection_amd.evaluation import waymo as W
+    from range_view_3d_detection_amd.math.ops.coding import DETECTION_COLUMNS
+
+    ev = WaymoDetectionEvaluator(WaymoDetectionCfg(), ["VEHICLE", "PEDESTRIAN"])
+    with pytest.raises(RvError, match="no CPU fallback"):
+        ev.update(torch.zeros(1, 10), torch.zeros(1), torch.zeros(1), torch.zeros(1), torch.zeros(1, 13), torch.ones(1))
+    with pytest.raises(RvError, match="before any update"):
+        ev.compute()
+    with pytest.raises(RvError, match="no CPU fallback"):
+        W.summarize(torch.zeros(W.TABLE_SHAPE, dtype=torch.int64))
+    with pytest.raises(RvError, match="not Waymo object types"):
+        WaymoDetectionEvaluator(idx_to_category=["VEHICLE", "BUS"])
+    frame = {c: pa.array([0.0], type=pa.float32()) for c in DETECTION_COLUMNS}
+    dts = pa.table({**frame, "score": pa.array([0.5], type=pa.float32()), "log_id": ["a"], "timestamp_ns": [1], "category": ["VEHICLE"]})
+    gts = pa.table({**frame, "num_interior_pts": [3], "log_id": ["a"], "timestamp_ns": [1], "category": ["VEHICLE"]})
+    with pytest.raises(RvError, match="no CPU fallback"):
+        evaluate_waymo(dts, gts, device="cpu")
