@@ -952,6 +952,58 @@ int rv_waymo_match(const float* dts, const float* scores, const int64_t* dt_orde
                    int32_t* errors, rvStream stream);
 int rv_waymo_summarize(const int64_t* tables, double* out, rvStream stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Waymo range image -> sweep: polar (sensor frame, per-pixel pose) to Cartesian (vehicle frame at the frame's timestamp).
+ * What the reference's offline exporter (converters/waymo/export.py:55-147 convert_range_image_to_cartesian, :255-285) gets from
+ * waymo_open_dataset's range_image_utils.extract_point_cloud_from_range_image, compute_inclination and
+ * transform_utils.get_rotation_matrix, for the FIRST return of the TOP lidar (all the reference exports).  DECLARED semantics:
+ * neither TensorFlow nor waymo_open_dataset is available to this project, so the rules below restate those functions and are NOT
+ * pinned against their binaries (tests/waymo_convert_ref.py is the NumPy restatement the kernels are tested against).
+ *
+ * Inputs (device pointers, B frames per call):
+ *   range_image    (B, H, W, 4) fp32, 16-byte aligned: range, intensity, elongation, nlz.  range <= 0 (or NaN): no return;
+ *                  nlz == 1.0: the pixel lies in a no-label zone.
+ *   extrinsic      (B, 4, 4) fp64 row-major E: vehicle <- sensor.
+ *   inclination    (B, H) fp64: inclination of IMAGE ROW r (row 0 = the highest beam), i.e. the calibration's beam table reversed,
+ *                  or, for a uniform sensor, (r + 0.5) / H * (max - min) + min for r = 0 .. H-1, reversed.
+ *   pixel_pose     (B, H, W, 6) fp32 or NULL: roll, pitch, yaw, tx, ty, tz of world <- vehicle at the time the pixel was measured.
+ *   inv_frame_pose (B, 3, 4) fp64, required iff pixel_pose is given: the upper three rows of V = inverse(world <- vehicle at the
+ *                  frame's timestamp), inverted by the caller in fp64.
+ * Per pixel (row r, column c), everything in fp64 from the fp32 / fp64 inputs, rounded to fp32 once at the end:
+ *   az_correction = atan2(E[1][0], E[0][0]);  ratio = (W - c - 0.5) / W;  azimuth = (2 ratio - 1) pi - az_correction
+ *     (column 0 is azimuth ~ +pi);
+ *   p_sensor  = range * [cos(azimuth) cos(incl_r), sin(azimuth) cos(incl_r), sin(incl_r)];
+ *   p_vehicle = E[:3,:3] p_sensor + E[:3,3];
+ *   with a pixel pose: R = Rz(yaw) Ry(pitch) Rx(roll), p_world = R p_vehicle + t, p = V[:3,:3] p_world + V[:3,3]; else p = p_vehicle;
+ *   valid = range > 0 and nlz != 1.0.  A valid pixel is [range, intensity, elongation, x, y, z] with the first three bit-equal to
+ *   the input; every other pixel is exact +0.0 in all six channels.  This is a SELECT, not the reference's product with a 0/1
+ *   mask: a NaN range or pose at an invalid pixel leaves zeros, not NaN (declared deviation).
+ *   num_pts[b] (int64, may be NULL; cleared by the call) = number of valid pixels of frame b -- the quantity behind the reference's
+ *   `num_pts >= 50000` filter of training frames.
+ * fp64 and not TensorFlow's fp32, because the detour through the world frame adds and subtracts kilometres (DESIGN 8.4 has the
+ * figures); a table made by the TensorFlow exporter differs from this one by that fp32 error.
+ *
+ * rv_waymo_range_image_to_sweep: -> sweep (B, H, W, 6) fp32 channel-last, 8-byte aligned: the reference's table, H*W rows of
+ *   range, intensity, elongation, x, y, z per frame.
+ * rv_waymo_range_image_to_batch: -> the loader's padded batch in the same single launch: features (B, n_feat, H, W + 2 pad) with
+ *   feature f = sweep channel host_feat_src[f] (0 .. 5, HOST array, <= 16 entries) through host_feat_op[f] (0 copy, 1 tanh: the
+ *   same device function on the same fp32 value as rv_table_to_range_view), cart (B, 3, H, W + 2 pad) = x, y, z,
+ *   mask (B, 1, H, W + 2 pad) u8 = valid.  The `pad` columns on either side are zeros, or, with circular != 0, the wrap-around in
+ *   azimuth (rv_pad_range_view's rule); num_pts counts the W image columns only.  Equal bit for bit to rv_table_to_range_view +
+ *   rv_pad_range_view on the sweep of the first entry.
+ * Both: asynchronous on `stream`, own no memory, one kernel launch (plus the clearing of num_pts).  They return non-zero BEFORE
+ * anything is launched for: a NULL required pointer, B / H / W <= 0, B or H > 65535 (the launch grid; pixel offsets are 64-bit),
+ * pixel_pose without inv_frame_pose or the reverse, a misaligned pointer, n_feat outside 1 .. 16, a feature source outside 0 .. 5,
+ * an op other than 0 / 1, pad < 0.
+ * ------------------------------------------------------------------------------------- */
+int rv_waymo_range_image_to_sweep(const float* range_image, const double* extrinsic, const double* inclination,
+                                  const float* pixel_pose, const double* inv_frame_pose, int32_t B, int32_t H, int32_t W, float* sweep,
+                                  int64_t* num_pts, rvStream stream);
+int rv_waymo_range_image_to_batch(const float* range_image, const double* extrinsic, const double* inclination,
+                                  const float* pixel_pose, const double* inv_frame_pose, int32_t B, int32_t H, int32_t W, int32_t n_feat,
+                                  const int32_t* host_feat_src, const int32_t* host_feat_op, int32_t pad, int32_t circular,
+                                  float* features, float* cart, uint8_t* mask, int64_t* num_pts, rvStream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -77,7 +77,7 @@ __global__ void table_to_range_view_kernel(const TableArgs a) {
         const float roi = a.roi_col >= 0 ? (a.table[(int64_t)a.roi_col * a.hw + i] != 0.f ? 1.f : 0.f) : 1.f;
         for (int f = 0; f < a.n_feat; ++f) {
             float v = a.table[(int64_t)a.feat_col[f] * a.hw + i] * roi;
-            if (a.feat_op[f] == 1) v = tanhf(v);
+            if (a.feat_op[f] == 1) v = rv_feature_tanh(v);
             else if (a.feat_op[f] == 2) v = (float)((double)v * 1e-9);
             a.features[(int64_t)f * a.hw + i] = v;
         }

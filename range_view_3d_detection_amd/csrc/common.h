@@ -120,6 +120,10 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
     return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
 }
 
+// feature op 1 of the loader's contract (tanh of the Waymo intensity, prototype/loader.py:625-626): ONE device function for every kernel that
+// forms the feature (rv_table_to_range_view, rv_waymo_range_image_to_batch), so that the routes agree bit for bit on the same fp32 value
+__device__ __forceinline__ float rv_feature_tanh(float v) { return tanhf(v); }
+
 // Opaque pass-through: consumers of `v` cannot be scheduled above this point.  Used on prefetch registers so that
 // hipcc does not hoist the unpack/transform of freshly loaded data (and with it an s_waitcnt vmcnt(0)) in front of
 // the MFMA section the loads are supposed to overlap with.
