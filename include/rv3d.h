@@ -864,6 +864,80 @@ int rv_eval_summarize(const uint8_t* flags, const float* err, const int64_t* cat
                       double default_aoe, void* workspace, double* table, double* ap_per_threshold, rvStream stream);
 
 /* ---------------------------------------------------------------------------------------
+ * AV2 region of interest (ROI) on the device: the map raster, per-point and per-box flags, the evaluation filter (csrc/roi.hip, and
+ * rv_eval_match_roi in csrc/evaluate.hip).  The reference flags every lidar return with av2's map API (converters/av2/export.py:91-97:
+ * city_SE3_ego.transform_from, get_raster_layer_points_boolean(ROI)) and evaluates AV2 with eval_only_roi_instances = True
+ * (datasets/__init__.py:27-30, nn/arch/detector.py:457-472).  av2 is not part of the reference tree, so -- as for rv_eval_match -- the
+ * semantics are DECLARED here and not pinned against av2's binaries.  The free choices, so that a mismatch with av2 can be traced to one
+ * of them: (1) raster coordinates are TRUNCATED toward zero to the cell index; (2) a box is inside iff one of its 8 VERTICES is;
+ * (3) the matcher applies the per-category CAP BEFORE the ROI flag; (4) the builder fills a pixel by its CENTRE; (5) the dilation keeps
+ * offsets with du^2 + dv^2 <= r^2 (`<=`).
+ *
+ * Atlas: the rasters of any number of logs in ONE u8 device buffer `raster` (raster_bytes long) and a DEVICE table of n_layers rvRoiLayer
+ * records: layer k is the row-major (height, width) image at raster + offset, cell (v, u) at offset + v * width + u; (s, tx, ty) is av2's
+ * array_Sim2_city with R = I.  rv_roi_atlas_check validates a HOST copy of the table against raster_bytes (every layer inside the
+ * buffer, s > 0, finite) before it is uploaded; the kernels additionally never read outside [0, raster_bytes).
+ * Sweep table (DEVICE): layer_index (n_sweeps) i32 and city_SE3_ego (n_sweeps, 12) f64, the row-major 3 x 4 [R | t] of each sweep.
+ *
+ * Lookup of an ego-frame point p = (x, y, z) of sweep b, fp64 from the input type, no fused multiply-add, in this order:
+ *   pcx = ((T[0]*x + T[1]*y) + T[2]*z) + T[3];  pcy = ((T[4]*x + T[5]*y) + T[6]*z) + T[7]      (T = city_SE3_ego[b]; z of the city point unused)
+ *   a = (pcx + tx) * s;  b = (pcy + ty) * s;  u = (int64)a, v = (int64)b truncating toward zero, as a NumPy integer cast does -- a
+ *   coordinate in (-1, 0) therefore lands in cell 0;
+ *   flag = raster[v, u] != 0 iff 0 <= u < width and 0 <= v < height, else 0; a non-finite a or b gives 0 (decided as
+ *   a > -1 && a < width && b > -1 && b < height, false for NaN, before the cast).
+ * A sweep whose layer_index is outside [0, n_layers) gives 0 for all its rows.  A row that belongs to no sweep gets 0 and adds 1 to
+ * *stray (DEVICE i64, ACCUMULATED: the caller zeroes it and decides when to read it).
+ *
+ * rv_roi_points -- xyz (n, 3) f32 or f64 (xyz_is_f64), sweep_offsets (n_sweeps + 1) i64 DEVICE (CSR: sweep b owns the rows
+ * [offsets[b], offsets[b + 1]); rows before offsets[0] or from offsets[n_sweeps] on are stray) -> within_roi (n) u8.  One launch, one
+ * thread per point (grid-stride), the sweep by binary search.
+ * rv_roi_boxes -- boxes (n, 10) f32 [tx_m, ty_m, tz_m, length_m, width_m, height_m, qw, qx, qy, qz], batch_index (n) i64 (outside
+ * [0, n_sweeps): stray) -> within_roi (n) u8: 1 iff ANY of the 8 vertices is inside (av2's compute_objects_in_roi_mask looks at vertices
+ * only: a box across a thin strip with all vertices outside is out).  Vertices, in fp64 from the fp32 row:
+ *   R = [[1 - 2*(qy*qy + qz*qz), 2*(qx*qy - qz*qw), 2*(qx*qz + qy*qw)], [2*(qx*qy + qz*qw), 1 - 2*(qx*qx + qz*qz), 2*(qy*qz - qx*qw)],
+ *        [2*(qx*qz - qy*qw), 2*(qy*qz + qx*qw), 1 - 2*(qx*qx + qy*qy)]] -- the full quaternion AS GIVEN (not normalised, not yaw only);
+ *   d = (+-0.5*length, +-0.5*width, +-0.5*height);  vertex_i = c_i + ((R[i][0]*d0 + R[i][1]*d1) + R[i][2]*d2), then the lookup above.
+ * One launch, one thread per box.
+ *
+ * rv_roi_rasterize -- builds one layer from drivable-area polygons (the reference ships no builder).  vertices (n_vertices, 2) f64 city
+ * frame, polygon_offsets (n_polygons + 1) i64, both DEVICE (offsets clamped to the vertex count); polygon p is the closed ring of its
+ * vertices, the last joined to the first.  r = dilation radius in PIXELS (fp64, finite, >= 0).  height * width < 2^31.
+ *   1. fill: vertices map to ((x + tx) * s, (y + ty) * s).  Pixel (v, u) is drivable iff its centre (cx, cy) = (u + 0.5, v + 0.5) is
+ *      inside ANY polygon by the even-odd rule, where an edge a -> b counts iff (a.y <= cy) != (b.y <= cy) and
+ *      a.x + (cy - a.y) * (b.x - a.x) / (b.y - a.y) > cx (fp64, that order).  Vertices are expected to be finite.
+ *   2. dilate: a pixel is ROI iff some drivable pixel lies at an integer offset (du, dv) with (double)(du*du + dv*dv) <= r*r; pixels
+ *      outside the image are not drivable.  Computed separably (per pixel the horizontal distance to the nearest drivable pixel of its
+ *      row, clamped; then dx(dv)^2 + dv^2 over the column), which is the same set.  Integers and booleans only: exact.
+ * -> drivable (height, width) u8 and roi (height, width) u8 (r = 0: equal).  Four launches (polygon boxes; fill, one thread per pixel,
+ * edges through LDS in chunks, polygons whose box misses the workgroup's tile skipped; rows; columns), asynchronous.  workspace:
+ * rv_roi_rasterize_workspace_bytes, 8-byte aligned, need not be initialised.
+ *
+ * rv_eval_match_roi -- rv_eval_match with the detections' ROI flags dt_roi (n_dt) u8 (NULL: exactly rv_eval_match; both entry points
+ * launch one kernel).  Declared order (av2 ANDs the cap mask and the ROI mask): a row IN RANGE counts towards max_num_dts whatever its
+ * flag, and evaluated = in range && rank < max_num_dts && dt_roi[row] != 0.  A row with flag 0 gets the outputs of a row that was not
+ * evaluated.  For the ground truth the caller ANDs the flag into gt_valid. */
+typedef struct rvRoiLayer {
+    int64_t offset;
+    int32_t height, width;
+    double s, tx, ty;
+} rvRoiLayer;
+int rv_roi_atlas_check(const rvRoiLayer* host_layers, int32_t n_layers, int64_t raster_bytes);
+int rv_roi_points(const void* xyz, int32_t xyz_is_f64, int64_t n, const int64_t* sweep_offsets, int32_t n_sweeps,
+                  const int32_t* layer_index, const double* city_SE3_ego, const uint8_t* raster, int64_t raster_bytes,
+                  const rvRoiLayer* layers, int32_t n_layers, uint8_t* within_roi, int64_t* stray, rvStream stream);
+int rv_roi_boxes(const float* boxes, const int64_t* batch_index, int64_t n, int32_t n_sweeps, const int32_t* layer_index,
+                 const double* city_SE3_ego, const uint8_t* raster, int64_t raster_bytes, const rvRoiLayer* layers, int32_t n_layers,
+                 uint8_t* within_roi, int64_t* stray, rvStream stream);
+int64_t rv_roi_rasterize_workspace_bytes(int32_t n_polygons, int32_t height, int32_t width);
+int rv_roi_rasterize(const double* vertices, const int64_t* polygon_offsets, int64_t n_vertices, int32_t n_polygons, double s, double tx,
+                     double ty, int32_t height, int32_t width, double r, void* workspace, uint8_t* drivable, uint8_t* roi, rvStream stream);
+int rv_eval_match_roi(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
+                      const uint8_t* gt_valid, const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments,
+                      const double* host_thresholds_m, int32_t n_thresholds, double tp_threshold_m, double max_range_m, int32_t max_num_dts,
+                      const uint8_t* dt_roi, uint8_t* dt_evaluated, uint8_t* tp, float* err, int32_t* matched_gt, uint8_t* gt_evaluated,
+                      rvStream stream);
+
+/* ---------------------------------------------------------------------------------------
  * Detection evaluation with the Waymo Open Dataset metric definitions: rotated BEV / 3-D IoU, maximum-weight ("Hungarian") matching,
  * AP and APH per object type, range and difficulty level (csrc/evaluate_waymo.hip).  The reference hands its detections to
  * waymo_open_dataset's evaluator (evaluation/evaluate.py:367-466); that library (and TensorFlow) is not part of the reference tree,

@@ -95,6 +95,13 @@ class LossParams(ctypes.Structure):
                [("azimuth_invariant", ctypes.c_int32)]
 
 
+class RoiLayer(ctypes.Structure):
+    """``rvRoiLayer``: one raster of the ROI atlas (``converters/av2/roi.py``)."""
+
+    _fields_ = [("offset", ctypes.c_int64), ("height", ctypes.c_int32), ("width", ctypes.c_int32), ("s", ctypes.c_double), ("tx", ctypes.c_double),
+                ("ty", ctypes.c_double)]
+
+
 ML_MAX_LEVELS, ML_MAX_ENTRIES = 8, 16  # RV_ML_MAX_LEVELS / RV_ML_MAX_ENTRIES
 AFFINITY_GAUSSIAN, AFFINITY_BEV = 0, 1  # RV_AFFINITY_* (rv_soft_assign)
 EVAL_MAX_THRESHOLDS, EVAL_MAX_DTS = 8, 1024  # RV_EVAL_MAX_* (rv_eval_match)
@@ -179,7 +186,7 @@ def _dlopen(path: str) -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     lib.rv_last_error.restype = ctypes.c_char_p
     for name in ("rv_packed_weight_bytes", "rv_decode_num_candidates", "rv_wnms_workspace_bytes", "rv_tap_wgrad_workspace_bytes", "rv_bn_bwd_smallk_workspace_bytes", "rv_smallk_forward_workspace_bytes", "rv_nms_sweeps_workspace_bytes", "rv_nms_rotated_workspace_bytes", "rv_pack_batch_entry_bytes", "rv_soft_assign_workspace_bytes", "rv_db_paste_workspace_bytes",
-                 "rv_eval_summarize_workspace_bytes", "rv_waymo_match_workspace_bytes"):
+                 "rv_eval_summarize_workspace_bytes", "rv_waymo_match_workspace_bytes", "rv_roi_rasterize_workspace_bytes"):
         if hasattr(lib, name):
             getattr(lib, name).restype = ctypes.c_int64
     return lib

@@ -9,6 +9,11 @@ here the same steps are device kernels, so a sweep can be projected online, righ
   data and are passed in, not shipped;
 * :func:`build_range_view`      (``utils.py:32-105``)   ``rv_se3_inverse_apply`` + ``rv_project_indices`` + ``rv_z_buffer``.
 
+The ``is_within_roi`` column that :func:`build_range_view` takes as ``features[:, 5]`` is the converter's map lookup
+(``converters/av2/export.py:91-97``: ``city_SE3_egovehicle.transform_from`` + ``get_raster_layer_points_boolean(city_xyz, ROI)``);
+``converters.av2.roi.roi_points(xyz, sweep_offsets, layer_index, city_SE3_ego, atlas)`` yields it on the device for a whole batch of
+sweeps, from the ego-frame ``xyz`` the sweep file holds (``rv_roi_points``).
+
 Dropped points (outside the pose track's time span) are not compacted away: they keep their place (the z-buffer's tie rule
 depends on the point order) and get range 0, which the z-buffer skips.  No CPU fallback.
 """

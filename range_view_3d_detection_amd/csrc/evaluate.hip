@@ -7,6 +7,8 @@
 //                      for the rows outside every segment.
 //                        A  walk the segment in score order: range filter, running count (ballot scan carried over tiles), the first
 //                           `cap` rows in range are the evaluated detections and go to an LDS list; every other row gets its defaults;
+//                           rv_eval_match_roi (the same kernel, dt_roi given): a row in range holds its place among the `cap` whatever
+//                           its flag, and only the flagged ones of them are evaluated (a second ballot scan packs the list);
 //                        B  every thread owns evaluated detections (rank = k * 256 + thread) and keeps (min d2, argmin) in registers
 //                           while the segment's ground truth passes through LDS in chunks of GT_CHUNK (no bound on their number);
 //                        C  per chunk: LDS atomicMin of the detection's rank on its nearest ground truth; the detection that finds its
@@ -35,6 +37,7 @@ struct EvalMatchArgs {
     const int64_t* dt_off;    // (n_seg + 1)
     const float* gts;         // (n_gt, 10)
     const uint8_t* gt_valid;  // (n_gt) or null
+    const uint8_t* dt_roi;    // (n_dt) or null: rv_eval_match_roi
     const int64_t* gt_order;  // (n_gt)
     const int64_t* gt_off;    // (n_seg + 1)
     int64_t n_dt, n_gt;
@@ -89,6 +92,7 @@ __global__ __launch_bounds__(THREADS) void eval_match_kernel(const EvalMatchArgs
     __shared__ float gt_xyz[GT_CHUNK * 3];
     __shared__ int claim[GT_CHUNK];
     __shared__ int wave_count[THREADS / 64];
+    __shared__ int wave_kept[THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int seg = blockIdx.x;
     if (seg == a.n_seg) {
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(THREADS) void eval_match_kernel(const EvalMatchArgs
     const int64_t g0 = clamp64(a.gt_off[seg], 0, a.n_gt), g1 = clamp64(a.gt_off[seg + 1], g0, a.n_gt);
 
     // A: the first `cap` rows in range, in score order
-    int n_eval = 0;
+    int n_eval = 0, n_kept = 0;  // rows in range so far; with dt_roi: the evaluated ones among them
     for (int64_t base = d0; base < d1; base += THREADS) {
         const int64_t i = base + tid;
         const int64_t row = i < d1 ? row_at(a.dt_order, i, a.n_dt) : -1;
@@ -114,13 +118,26 @@ __global__ __launch_bounds__(THREADS) void eval_match_kernel(const EvalMatchArgs
             if (w < wave) rank += wave_count[w];
             total += wave_count[w];
         }
-        const bool evaluated = in_range && rank < a.cap;
-        if (evaluated) ev_row[rank] = row;
+        bool evaluated = in_range && rank < a.cap;
+        int slot = rank;
+        if (a.dt_roi) {  // (the same for the whole grid) cap first, then the ROI flag: the evaluated rows are packed by a second scan
+            evaluated = evaluated && a.dt_roi[row] != 0;
+            const unsigned long long kept = __ballot(evaluated);
+            if (lane == 0) wave_kept[wave] = __popcll(kept);
+            __syncthreads();
+            slot = n_kept + __popcll(kept & ((1ull << lane) - 1ull));
+            for (int w = 0; w < THREADS / 64; ++w) {
+                if (w < wave) slot += wave_kept[w];
+                n_kept += wave_kept[w];
+            }
+        }
+        if (evaluated) ev_row[slot] = row;
         else if (row >= 0) write_unmatched(a, row, false);
         n_eval += total;
         __syncthreads();
     }
     if (n_eval > a.cap) n_eval = a.cap;
+    if (a.dt_roi) n_eval = n_kept;
 
     // B: nearest evaluated ground truth of every evaluated detection (ties: the lowest index, `<` below)
     const int n_pass = n_eval > 0 ? (n_eval + THREADS - 1) / THREADS : 1;  // (one pass with no detections still flags the ground truth)
@@ -363,11 +380,12 @@ int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
 
 }  // namespace
 
-extern "C" int rv_eval_match(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
-                             const uint8_t* gt_valid, const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments,
-                             const double* host_thresholds_m, int32_t n_thresholds, double tp_threshold_m, double max_range_m,
-                             int32_t max_num_dts, uint8_t* dt_evaluated, uint8_t* tp, float* err, int32_t* matched_gt, uint8_t* gt_evaluated,
-                             rvStream stream) {
+namespace {
+
+int eval_match(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts, const uint8_t* gt_valid,
+               const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments, const double* host_thresholds_m,
+               int32_t n_thresholds, double tp_threshold_m, double max_range_m, int32_t max_num_dts, const uint8_t* dt_roi, uint8_t* dt_evaluated,
+               uint8_t* tp, float* err, int32_t* matched_gt, uint8_t* gt_evaluated, rvStream stream) {
     RV_REQUIRE(n_dt >= 0 && n_gt >= 0 && n_gt <= 0x7fffffff, "rv_eval_match: n_dt = %lld, n_gt = %lld", (long long)n_dt, (long long)n_gt);
     RV_REQUIRE(n_segments >= 1, "rv_eval_match: %d segments", n_segments);
     RV_REQUIRE(host_thresholds_m && n_thresholds >= 1 && n_thresholds <= RV_EVAL_MAX_THRESHOLDS, "rv_eval_match: %d thresholds (1 .. %d)",
@@ -380,7 +398,7 @@ extern "C" int rv_eval_match(const float* dts, const int64_t* dt_order, const in
     EvalMatchArgs a;
     memset(&a, 0, sizeof(a));
     a.dts = dts, a.dt_order = dt_order, a.dt_off = dt_offsets, a.n_dt = n_dt;
-    a.gts = gts, a.gt_valid = gt_valid, a.gt_order = gt_order, a.gt_off = gt_offsets, a.n_gt = n_gt;
+    a.gts = gts, a.gt_valid = gt_valid, a.dt_roi = n_dt > 0 ? dt_roi : nullptr, a.gt_order = gt_order, a.gt_off = gt_offsets, a.n_gt = n_gt;
     a.n_seg = n_segments, a.n_thr = n_thresholds, a.cap = max_num_dts;
     a.range2 = max_range_m * max_range_m;
     a.tp_thr2 = tp_threshold_m * tp_threshold_m;
@@ -392,6 +410,27 @@ extern "C" int rv_eval_match(const float* dts, const int64_t* dt_order, const in
     hipLaunchKernelGGL(eval_match_kernel, dim3((unsigned)n_segments + 1), dim3(THREADS), 0, (hipStream_t)stream, a);
     RV_CHECK_LAUNCH("eval_match_kernel");
     return 0;
+}
+
+}  // namespace
+
+extern "C" int rv_eval_match(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
+                             const uint8_t* gt_valid, const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments,
+                             const double* host_thresholds_m, int32_t n_thresholds, double tp_threshold_m, double max_range_m,
+                             int32_t max_num_dts, uint8_t* dt_evaluated, uint8_t* tp, float* err, int32_t* matched_gt, uint8_t* gt_evaluated,
+                             rvStream stream) {
+    return eval_match(dts, dt_order, dt_offsets, n_dt, gts, gt_valid, gt_order, gt_offsets, n_gt, n_segments, host_thresholds_m, n_thresholds,
+                      tp_threshold_m, max_range_m, max_num_dts, nullptr, dt_evaluated, tp, err, matched_gt, gt_evaluated, stream);
+}
+
+// the same kernel with the detections' ROI flags (include/rv3d.h: cap first, then the flag); dt_roi == NULL is rv_eval_match
+extern "C" int rv_eval_match_roi(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
+                                 const uint8_t* gt_valid, const int64_t* gt_order, const int64_t* gt_offsets, int64_t n_gt, int32_t n_segments,
+                                 const double* host_thresholds_m, int32_t n_thresholds, double tp_threshold_m, double max_range_m,
+                                 int32_t max_num_dts, const uint8_t* dt_roi, uint8_t* dt_evaluated, uint8_t* tp, float* err, int32_t* matched_gt,
+                                 uint8_t* gt_evaluated, rvStream stream) {
+    return eval_match(dts, dt_order, dt_offsets, n_dt, gts, gt_valid, gt_order, gt_offsets, n_gt, n_segments, host_thresholds_m, n_thresholds,
+                      tp_threshold_m, max_range_m, max_num_dts, dt_roi, dt_evaluated, tp, err, matched_gt, gt_evaluated, stream);
 }
 
 extern "C" int64_t rv_eval_summarize_workspace_bytes(int64_t n_rows, int32_t n_categories, int32_t n_thresholds) {
