@@ -250,7 +250,9 @@ int rv_ew_combine(int64_t pixels, int32_t c, const void* a, int32_t ld_a, const 
  *                    coef[0][c] = gamma*invstd, coef[1][c] = mean(g), coef[2][c] = mean(g*xhat)
  *   pass 2 (apply) : dY = coef0 * (g - coef1 - xhat*coef2)  (bf16), and optionally
  *                    dRes (+)= g  (identity residual branch).
- * Replaces cuDNN BatchNorm backward + ReLU backward + the add's gradient fan-out. */
+ * Replaces cuDNN BatchNorm backward + ReLU backward + the add's gradient fan-out.
+ * Every pass here, rv_ew_combine and rv_ew_mask_grad reject, before any launch: pixels <= 0, c <= 0, c % 8, a row pitch that is
+ * no multiple of 8 or below c (of a tensor that is given); the BatchNorm passes also c > 2048. */
 #define RV_BNB_RELU_Z 1
 #define RV_BNB_RES_ACCUM 2
 #define RV_BNB_Y_FROM_INPUT 4 /* rv_bn_bwd_smallk*: y (may be NULL) is recomputed as W v from the conv input and w_packed */
@@ -338,6 +340,42 @@ int rv_smallk_forward(const void* v, int32_t ld_v, int64_t pixels, int32_t cin, 
 /* gradient of rv_ew_combine's plain (non-BN) inputs: d (+)= dOut * [OUT > 0 if out != NULL] */
 int rv_ew_mask_grad(int64_t pixels, int32_t c, const void* dout, int32_t ld_dout, const void* out, int32_t ld_out,
                     void* d, int32_t ld_d, int32_t accumulate, rvStream stream);
+
+/* Which kernel form a bandwidth-bound BatchNorm / element-wise pass launches for a shape (tests / bench labels; launches nothing).
+ * The entry points launch from the very plan this reports.  pixels_or_rows: pixels, or the partial rows of a finalize pass;
+ * ld: the row pitches (elements) as the entry point receives them, those of absent optional tensors included, in its argument order --
+ * RV_EW_PASS_BWD_REDUCE {dout, out, y}, _REDUCE_PAIR {dout, out, ya, yb}, _BWD_APPLY {dout, out, y, dy, dres}; the other passes
+ * do not read it; NULL = every pitch equals c;
+ * has_out: the ReLU mask tensor `out` (RV_EW_PASS_COMBINE: the operand b) is given; has_dres: RV_EW_PASS_BWD_APPLY writes dres;
+ * flags: RV_BNB_* of RV_EW_PASS_BWD_APPLY; finalize passes: non-zero = device-side count (count < 0).
+ *   host_info[0] = form: RV_EW_FORM_COMB   grid-stride comb over channel octets (ew_combine_kernel, ew_mask_grad_kernel)
+ *                        RV_EW_FORM_ROWS   one contiguous pixel range per workgroup (ew_combine_rows_kernel)
+ *                        RV_EW_FORM_OCTET  thread = (pixel lane, channel octet), 64-bit addresses (bn_bwd_reduce_kernel, _reduce2_kernel,
+ *                                          bn_bwd_apply_kernel, bn_bwd_apply2_kernel): c > 1024 or byte offsets of 2^32 and more
+ *                        RV_EW_FORM_LEAN   thread = (pixel lane, channel quad), 32-bit byte offsets (bn_bwd_*_lean_kernel)
+ *                        RV_EW_FORM_FUSED_FINALIZE  one launch sums the partial rows and finalises (at most 2048 rows)
+ *                        RV_EW_FORM_TWO_STAGE       col_reduce_kernel into 64 fp64 group rows, then the finalize kernel
+ *   host_info[1] = 1: non-temporal loads and stores (pixels * c * 2 bytes reach 256 MiB)
+ *   host_info[2] = workgroups (of the second launch for RV_EW_FORM_TWO_STAGE)
+ *   host_info[3] = template argument of the instantiation: RV_EW_PASS_BWD_APPLY lean: F of bn_bwd_apply_lean_kernel<F> (1 non-temporal
+ *                  | 2 out | 4 dres | 8 RV_BNB_RES_ACCUM), octet and RV_EW_PASS_BWD_APPLY_PAIR: MODE; RV_EW_PASS_BWD_REDUCE lean: OUT;
+ *                  RV_EW_PASS_COMBINE rows: HAS_B; finalize passes: 1 = device-side count; 0 otherwise. */
+#define RV_EW_PASS_COMBINE 0
+#define RV_EW_PASS_MASK_GRAD 1
+#define RV_EW_PASS_BN_FINALIZE 2
+#define RV_EW_PASS_BWD_REDUCE 3
+#define RV_EW_PASS_BWD_REDUCE_PAIR 4
+#define RV_EW_PASS_BWD_FINALIZE 5
+#define RV_EW_PASS_BWD_APPLY 6
+#define RV_EW_PASS_BWD_APPLY_PAIR 7
+#define RV_EW_FORM_COMB 1
+#define RV_EW_FORM_ROWS 2
+#define RV_EW_FORM_OCTET 3
+#define RV_EW_FORM_LEAN 4
+#define RV_EW_FORM_FUSED_FINALIZE 5
+#define RV_EW_FORM_TWO_STAGE 6
+int rv_ew_pass_info(int32_t pass, int64_t pixels_or_rows, int32_t c, const int32_t* ld, int32_t has_out, int32_t has_dres,
+                    int32_t flags, int32_t* host_info);
 
 /* RangePartition stem (nn/stems/__init__.py:88-135, the stem RangeNet builds for stem_type RANGE_PARTITION, nn/backbones/dla.py:164-171):
  * `features = (partitions[:, :, None] * features[:, None]).flatten(1, 2) * mask` with partitions = (||cart|| >= lower) & (||cart|| <= upper)

@@ -30,6 +30,9 @@ SEL_SMALL_GRIDS, SEL_SMALL_GRIDS6, SEL_NO_GEN6, SEL_NO_GEN5, SEL_NO_POINTWISE, S
 SELECT = 0
 EW_RELU_A, EW_RELU_B, EW_RELU_OUT = 1, 2, 4
 BNB_RELU_Z, BNB_RES_ACCUM, BNB_Y_FROM_INPUT = 1, 2, 4
+# rv_ew_pass_info: passes and kernel forms (RV_EW_PASS_* / RV_EW_FORM_*)
+EW_PASS_COMBINE, EW_PASS_MASK_GRAD, EW_PASS_BN_FINALIZE, EW_PASS_BWD_REDUCE, EW_PASS_BWD_REDUCE_PAIR, EW_PASS_BWD_FINALIZE, EW_PASS_BWD_APPLY, EW_PASS_BWD_APPLY_PAIR = range(8)
+EW_FORM_COMB, EW_FORM_ROWS, EW_FORM_OCTET, EW_FORM_LEAN, EW_FORM_FUSED_FINALIZE, EW_FORM_TWO_STAGE = range(1, 7)
 STATS_SCRATCH_ROWS = 128
 
 
@@ -269,6 +272,19 @@ def tap_launch_info(geom: TapGeom, shape: TapShape, scatter: bool):
     info = (ctypes.c_int32 * 4)()
     if load().rv_tap_launch_info(ctypes.byref(geom), ctypes.byref(shape), 1 if scatter else 0, info) != 0:
         return None
+    return tuple(info)
+
+
+def ew_pass_info(pass_id: int, pixels_or_rows: int, c: int, ld=None, has_out: bool = False, has_dres: bool = False, flags: int = 0):
+    """``rv_ew_pass_info``: (form, non-temporal, grid, template index) of the launch the library plans for a BatchNorm / element-wise
+    pass at this shape -- the plan the entry point itself launches from.  ``ld``: the row pitches in the entry point's argument order
+    (reduce: dout, out, y; reduce_pair: dout, out, ya, yb; apply: dout, out, y, dy, dres), ``None`` = all ``c``.  Launches nothing;
+    raises ``RvError`` on a shape the library rejects."""
+    info = (ctypes.c_int32 * 4)()
+    lds = (ctypes.c_int32 * 5)(*(list(ld) + [0] * (5 - len(ld)))) if ld is not None else None
+    if load().rv_ew_pass_info(i32(pass_id), i64(pixels_or_rows), i32(c), lds, i32(1 if has_out else 0), i32(1 if has_dres else 0),
+                              i32(flags), info) != 0:
+        raise RvError(f"rv_ew_pass_info failed: {load().rv_last_error().decode()}")
     return tuple(info)
 
 

@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "ewpass.h"
 
 int rv_col_reduce(const float* partial, int rows, int cols, double* scratch, int* groups, hipStream_t st);
 
@@ -958,15 +959,6 @@ __global__ void sum_rows_f64_kernel(const double* rows, int n_rows, int cols, do
     }
 }
 
-// the lean (quad layout, <= 96 VGPRs) forms of the four BatchNorm-backward passes are what runs; the octet forms take tensors whose byte
-// offsets do not fit 32 bits (A/B of the two and of a one-workgroup-per-CU launch: profiles/r04_ab_notes.md)
-constexpr int bnb_lean() { return 2; }
-
-int grid_for(int64_t work) {
-    int64_t b = (work + 255) / 256;
-    return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
-
 int fill(BnbArgs* a, int64_t pixels, int32_t c, const void* dout, int32_t ld_dout, const void* out, int32_t ld_out,
          const void* y, int32_t ld_y, const float* scale, const float* shift, const float* mean, const float* invstd,
          int32_t flags) {
@@ -990,6 +982,13 @@ int fill(BnbArgs* a, int64_t pixels, int32_t c, const void* dout, int32_t ld_dou
     return 0;
 }
 
+// the rule of the _pair entry points for rv_bn_bwd_reduce / _apply (fill() also serves the small-K passes, whose y may be NULL)
+int check_extent(const char* who, int64_t pixels, int32_t c, int32_t ld_dout, const void* out, int32_t ld_out, const void* y, int32_t ld_y) {
+    RV_REQUIRE(pixels > 0 && c > 0 && ld_dout >= c && (!y || ld_y >= c) && (!out || ld_out >= c),
+               "%s: empty tensor, or a row pitch below the channel count", who);
+    return 0;
+}
+
 }  // namespace
 
 extern "C" int32_t rv_bn_bwd_rows(int64_t pixels) { return (int32_t)((pixels + kPixPerBlock - 1) / kPixPerBlock); }
@@ -1000,14 +999,16 @@ extern "C" int rv_bn_bwd_reduce(int64_t pixels, int32_t c, const void* dout, int
     BnbArgs a;
     if (fill(&a, pixels, c, dout, ld_dout, out, ld_out, y, ld_y, scale, shift, mean, invstd, flags)) return 1;
     RV_REQUIRE(partial, "rv_bn_bwd_reduce: null partial buffer");
+    if (check_extent("rv_bn_bwd_reduce", pixels, c, ld_dout, out, ld_out, y, ld_y)) return 1;
     a.partial = partial;
-    if (bnb_lean() && c <= 1024 && pixels * std::max(std::max((int64_t)ld_dout, (int64_t)ld_y), (int64_t)ld_out) * 2 < ((int64_t)1 << 32)) {
-        if (out) hipLaunchKernelGGL(bn_bwd_reduce_lean_kernel<true>, dim3(rv_bn_bwd_rows(pixels)), dim3(256), 0, (hipStream_t)stream, a);
-        else hipLaunchKernelGGL(bn_bwd_reduce_lean_kernel<false>, dim3(rv_bn_bwd_rows(pixels)), dim3(256), 0, (hipStream_t)stream, a);
+    const RvEwPlan plan = rv_plan_bnb_reduce(pixels, c, ld_dout, ld_out, ld_y, out != nullptr);
+    if (plan.form == RV_EW_FORM_LEAN) {
+        if (out) hipLaunchKernelGGL(bn_bwd_reduce_lean_kernel<true>, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
+        else hipLaunchKernelGGL(bn_bwd_reduce_lean_kernel<false>, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
         RV_CHECK_LAUNCH("bn_bwd_reduce_lean_kernel");
         return 0;
     }
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(rv_bn_bwd_rows(pixels)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(bn_bwd_reduce_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
     RV_CHECK_LAUNCH("bn_bwd_reduce_kernel");
     return 0;
 }
@@ -1024,12 +1025,13 @@ extern "C" int rv_bn_bwd_reduce_pair(int64_t pixels, int32_t c, const void* dout
     a.mean_a = mean_a, a.invstd_a = invstd_a, a.mean_b = mean_b, a.invstd_b = invstd_b;
     a.pixels = pixels, a.c = c, a.c8 = c / 8, a.ld_dout = ld_dout, a.ld_out = ld_out, a.ld_ya = ld_ya, a.ld_yb = ld_yb;
     a.partial_a = partial_a, a.partial_b = partial_b;
-    if (bnb_lean() && c <= 1024 && pixels * std::max(std::max((int64_t)ld_dout, (int64_t)ld_out), std::max((int64_t)ld_ya, (int64_t)ld_yb)) * 2 < ((int64_t)1 << 32)) {
-        hipLaunchKernelGGL(bn_bwd_reduce2_lean_kernel, dim3(rv_bn_bwd_rows(pixels)), dim3(256), 0, (hipStream_t)stream, a);
+    const RvEwPlan plan = rv_plan_bnb_reduce_pair(pixels, c, ld_dout, ld_out, ld_ya, ld_yb);
+    if (plan.form == RV_EW_FORM_LEAN) {
+        hipLaunchKernelGGL(bn_bwd_reduce2_lean_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
         RV_CHECK_LAUNCH("bn_bwd_reduce2_lean_kernel");
         return 0;
     }
-    hipLaunchKernelGGL(bn_bwd_reduce2_kernel, dim3(rv_bn_bwd_rows(pixels)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(bn_bwd_reduce2_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
     RV_CHECK_LAUNCH("bn_bwd_reduce2_kernel");
     return 0;
 }
@@ -1040,8 +1042,9 @@ extern "C" int rv_bn_bwd_finalize(const float* partial, int32_t rows, int32_t c,
     RV_REQUIRE(partial && gamma && invstd && coef, "rv_bn_bwd_finalize: null argument");
     RV_REQUIRE(count > 0 || (count < 0 && rows == 1), "rv_bn_bwd_finalize: a device-side count (count < 0) needs the single row of all-reduced totals");
     const float* count_dev = count < 0 ? partial + 2 * c : nullptr;
-    if (rows <= 2048) {
-        hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(rv_ceil_div(c, 16)), dim3(256), 0, (hipStream_t)stream, partial, rows, c,
+    const RvEwPlan plan = rv_plan_bn_finalize(rows, c);
+    if (plan.form == RV_EW_FORM_FUSED_FINALIZE) {
+        hipLaunchKernelGGL(bn_bwd_reduce_finalize_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, partial, rows, c,
                            1.0 / (double)count, gamma, invstd, dgamma, dbeta, accumulate, coef, count_dev);
         RV_CHECK_LAUNCH("bn_bwd_reduce_finalize_kernel");
         return 0;
@@ -1050,7 +1053,7 @@ extern "C" int rv_bn_bwd_finalize(const float* partial, int32_t rows, int32_t c,
     double* scratch = (double*)(partial + (int64_t)rows * 2 * c);
     int groups;
     if (rv_col_reduce(partial, rows, 2 * c, scratch, &groups, (hipStream_t)stream)) return 1;
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(rv_ceil_div(c, 64)), dim3(256), 0, (hipStream_t)stream, scratch, groups, c,
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, scratch, groups, c,
                        1.0 / (double)count, gamma, invstd, dgamma, dbeta, accumulate, coef);
     RV_CHECK_LAUNCH("bn_bwd_finalize_kernel");
     return 0;
@@ -1063,6 +1066,8 @@ extern "C" int rv_bn_bwd_apply(int64_t pixels, int32_t c, const void* dout, int3
     BnbArgs a;
     if (fill(&a, pixels, c, dout, ld_dout, out, ld_out, y, ld_y, scale, shift, mean, invstd, flags)) return 1;
     RV_REQUIRE(coef && dy && ld_dy % 8 == 0 && (!dres || ld_dres % 8 == 0), "rv_bn_bwd_apply: bad outputs");
+    if (check_extent("rv_bn_bwd_apply", pixels, c, ld_dout, out, ld_out, y, ld_y)) return 1;
+    RV_REQUIRE(ld_dy >= c && (!dres || ld_dres >= c), "rv_bn_bwd_apply: a row pitch below the channel count");
     a.coef = coef;
     a.dy = (bf16_t*)dy;
     a.ld_dy = ld_dy;
@@ -1070,30 +1075,21 @@ extern "C" int rv_bn_bwd_apply(int64_t pixels, int32_t c, const void* dout, int3
     a.ld_dres = ld_dres;
     // lean form: alone it takes the same time (96.7 against 96.5-96.9 ms
     // per rv-av2 step), beside a weight gradient on the side stream (engine.py RV3D_OVERLAP=chain) it is what fits on the CU
-    const int lean = bnb_lean();
-    const int64_t ld_max = std::max(std::max((int64_t)ld_dout, (int64_t)ld_y), std::max(std::max((int64_t)ld_out, (int64_t)ld_dy), (int64_t)ld_dres));
-    if (lean && c <= 1024 && pixels * ld_max * 2 < ((int64_t)1 << 32)) {  // (32-bit byte offsets)
-        const int lanes4 = 256 / (2 * a.c8);
-        int64_t blocks4 = (pixels + lanes4 - 1) / lanes4;
-        if (blocks4 > 4096) blocks4 = 4096;
-        const int f = ((int64_t)pixels * c * 2 >= ((int64_t)256 << 20) ? 1 : 0) | (out ? 2 : 0) | (dres ? 4 : 0) |
-                      (dres && (flags & RV_BNB_RES_ACCUM) ? 8 : 0);
+    const RvEwPlan plan = rv_plan_bnb_apply(pixels, c, ld_dout, ld_out, ld_y, ld_dy, ld_dres, out != nullptr, dres != nullptr, flags);
+    if (plan.form == RV_EW_FORM_LEAN) {  // (32-bit byte offsets)
         using K = void (*)(const BnbArgs);
         static const K table[16] = {bn_bwd_apply_lean_kernel<0>,  bn_bwd_apply_lean_kernel<1>,  bn_bwd_apply_lean_kernel<2>,  bn_bwd_apply_lean_kernel<3>,
                                     bn_bwd_apply_lean_kernel<4>,  bn_bwd_apply_lean_kernel<5>,  bn_bwd_apply_lean_kernel<6>,  bn_bwd_apply_lean_kernel<7>,
                                     bn_bwd_apply_lean_kernel<4>,  bn_bwd_apply_lean_kernel<5>,  bn_bwd_apply_lean_kernel<6>,  bn_bwd_apply_lean_kernel<7>,
                                     bn_bwd_apply_lean_kernel<12>, bn_bwd_apply_lean_kernel<13>, bn_bwd_apply_lean_kernel<14>, bn_bwd_apply_lean_kernel<15>};
-        hipLaunchKernelGGL(table[f], dim3((int)blocks4), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(table[plan.index], dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
         RV_CHECK_LAUNCH("bn_bwd_apply_lean_kernel");
         return 0;
     }
-    const int lanes_px = 256 / a.c8;
-    int64_t blocks = (pixels + lanes_px - 1) / lanes_px;
-    if (blocks > 4096) blocks = 4096;
-    if ((int64_t)pixels * c * 2 >= ((int64_t)256 << 20))
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    if (plan.nontemporal)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel<0>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<0>, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
     RV_CHECK_LAUNCH("bn_bwd_apply_kernel");
     return 0;
 }
@@ -1114,13 +1110,11 @@ extern "C" int rv_bn_bwd_apply_pair(int64_t pixels, int32_t c, const void* dout,
     a.ld_dout = ld_dout, a.ld_out = ld_out, a.ld_ya = ld_ya, a.ld_yb = ld_yb, a.ld_dya = ld_dya, a.ld_dyb = ld_dyb;
     // (no lean form of this one: ten constants per channel -- 40 registers at four channels per thread -- leave no room for loads in
     //  flight within 96 registers; it runs beside a weight gradient only where that one leaves more)
-    const int lanes_px = 256 / a.c8;
-    int64_t blocks = (pixels + lanes_px - 1) / lanes_px;
-    if (blocks > 4096) blocks = 4096;
-    if ((int64_t)pixels * c * 2 >= ((int64_t)256 << 20))
-        hipLaunchKernelGGL(bn_bwd_apply2_kernel<1>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, a);
+    const RvEwPlan plan = rv_plan_bnb_apply_pair(pixels, c);
+    if (plan.nontemporal)
+        hipLaunchKernelGGL(bn_bwd_apply2_kernel<1>, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
     else
-        hipLaunchKernelGGL(bn_bwd_apply2_kernel<0>, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, a);
+        hipLaunchKernelGGL(bn_bwd_apply2_kernel<0>, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, a);
     RV_CHECK_LAUNCH("bn_bwd_apply2_kernel");
     return 0;
 }
@@ -1129,9 +1123,43 @@ extern "C" int rv_ew_mask_grad(int64_t pixels, int32_t c, const void* dout, int3
                                int32_t ld_out, void* d, int32_t ld_d, int32_t accumulate, rvStream stream) {
     RV_REQUIRE(dout && d, "rv_ew_mask_grad: null argument");
     RV_REQUIRE(c % 8 == 0 && ld_dout % 8 == 0 && ld_d % 8 == 0 && (!out || ld_out % 8 == 0), "rv_ew_mask_grad: channels / strides must be multiples of 8");
-    hipLaunchKernelGGL(ew_mask_grad_kernel, dim3(grid_for(pixels * (c / 8))), dim3(256), 0, (hipStream_t)stream, pixels,
+    RV_REQUIRE(pixels > 0 && c > 0 && ld_dout >= c && ld_d >= c && (!out || ld_out >= c), "rv_ew_mask_grad: empty tensor, or a row pitch below the channel count");
+    hipLaunchKernelGGL(ew_mask_grad_kernel, dim3(rv_plan_ew_mask_grad(pixels, c).grid), dim3(256), 0, (hipStream_t)stream, pixels,
                        c / 8, (const bf16_t*)dout, ld_dout, (const bf16_t*)out, ld_out, (bf16_t*)d, ld_d, accumulate);
     RV_CHECK_LAUNCH("ew_mask_grad_kernel");
+    return 0;
+}
+
+extern "C" int rv_ew_pass_info(int32_t pass, int64_t pixels_or_rows, int32_t c, const int32_t* ld, int32_t has_out, int32_t has_dres,
+                               int32_t flags, int32_t* host_info) {
+    RV_REQUIRE(host_info, "rv_ew_pass_info: null argument");
+    RV_REQUIRE(pixels_or_rows > 0 && c > 0, "rv_ew_pass_info: empty tensor");
+    const bool finalize = pass == RV_EW_PASS_BN_FINALIZE || pass == RV_EW_PASS_BWD_FINALIZE;
+    RvEwPlan plan;
+    if (finalize) {
+        RV_REQUIRE(pixels_or_rows <= INT32_MAX, "rv_ew_pass_info: too many partial rows");
+        RV_REQUIRE(!flags || pixels_or_rows == 1, "rv_ew_pass_info: a device-side count needs the single row of all-reduced totals");
+        plan = rv_plan_bn_finalize((int)pixels_or_rows, c);
+        plan.index = flags ? 1 : 0;
+    } else {
+        RV_REQUIRE(c % 8 == 0, "rv_ew_pass_info: channels must be a multiple of 8");
+        const int32_t dense[5] = {c, c, c, c, c};
+        if (!ld) ld = dense;
+        RV_REQUIRE(c <= 2048 || pass == RV_EW_PASS_COMBINE || pass == RV_EW_PASS_MASK_GRAD, "rv_ew_pass_info: at most 2048 channels");
+        switch (pass) {
+            case RV_EW_PASS_COMBINE: plan = rv_plan_ew_combine(pixels_or_rows, c, has_out != 0); break;
+            case RV_EW_PASS_MASK_GRAD: plan = rv_plan_ew_mask_grad(pixels_or_rows, c); break;
+            case RV_EW_PASS_BWD_REDUCE: plan = rv_plan_bnb_reduce(pixels_or_rows, c, ld[0], ld[1], ld[2], has_out != 0); break;
+            case RV_EW_PASS_BWD_REDUCE_PAIR: plan = rv_plan_bnb_reduce_pair(pixels_or_rows, c, ld[0], ld[1], ld[2], ld[3]); break;
+            case RV_EW_PASS_BWD_APPLY: plan = rv_plan_bnb_apply(pixels_or_rows, c, ld[0], ld[1], ld[2], ld[3], ld[4], has_out != 0, has_dres != 0, flags); break;
+            case RV_EW_PASS_BWD_APPLY_PAIR: plan = rv_plan_bnb_apply_pair(pixels_or_rows, c); break;
+            default: RV_FAIL("rv_ew_pass_info: unknown pass %d", pass);
+        }
+    }
+    host_info[0] = plan.form;
+    host_info[1] = plan.nontemporal;
+    host_info[2] = plan.grid;
+    host_info[3] = plan.index;
     return 0;
 }
 

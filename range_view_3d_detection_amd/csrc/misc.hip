@@ -5,6 +5,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "ewpass.h"
 #include "tapconv.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -516,10 +517,9 @@ extern "C" int rv_bn_finalize(const float* partial, int32_t rows, int32_t c, int
     RV_REQUIRE(count > 0 || rows == 1, "rv_bn_finalize: a device-side count (count < 0) needs the single row of all-reduced totals");
     const float* count_dev = count < 0 ? partial + 2 * c : nullptr;  // the slot right behind the (2, c) totals
     const double unbias = count > 1 ? (double)count / (double)(count - 1) : 1.0;
-    // few partial rows: one launch reduces and finalises; many (4096 rows behind a 512-channel tapconv4 launch): the
-    // 64-group column reduction spreads them over the chip first (29 us vs 14 us measured for the single launch)
-    if (rows <= 2048) {
-        hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3(rv_ceil_div(c, 16)), dim3(256), 0, (hipStream_t)stream, partial, rows, c,
+    const RvEwPlan plan = rv_plan_bn_finalize(rows, c);  // (one launch, or the 64-group column reduction first: ewpass.h)
+    if (plan.form == RV_EW_FORM_FUSED_FINALIZE) {
+        hipLaunchKernelGGL(bn_reduce_finalize_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, partial, rows, c,
                            1.0 / (double)count, unbias, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, mean, invstd,
                            count_dev);
         RV_CHECK_LAUNCH("bn_reduce_finalize_kernel");
@@ -529,7 +529,7 @@ extern "C" int rv_bn_finalize(const float* partial, int32_t rows, int32_t c, int
     double* scratch = (double*)(partial + (int64_t)rows * 2 * c);
     int groups;
     if (rv_col_reduce(partial, rows, 2 * c, scratch, &groups, (hipStream_t)stream)) return 1;
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3(rv_ceil_div(c, 64)), dim3(256), 0, (hipStream_t)stream, scratch, groups, c,
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, scratch, groups, c,
                        1.0 / (double)count, unbias, gamma, beta, eps, momentum, running_mean, running_var, scale, shift,
                        mean, invstd);
     RV_CHECK_LAUNCH("bn_finalize_kernel");
@@ -697,18 +697,15 @@ extern "C" int rv_ew_combine(int64_t pixels, int32_t c, const void* a, int32_t l
                              const float* b_shift, void* out, int32_t ld_out, int32_t flags, rvStream stream) {
     RV_REQUIRE(a && out, "rv_ew_combine: null argument");
     RV_REQUIRE(c % 8 == 0 && ld_a % 8 == 0 && ld_out % 8 == 0 && (!b || ld_b % 8 == 0), "rv_ew_combine: channels / strides must be multiples of 8");
+    RV_REQUIRE(pixels > 0 && c > 0 && ld_a >= c && ld_out >= c && (!b || ld_b >= c), "rv_ew_combine: empty tensor, or a row pitch below the channel count");
     RV_REQUIRE((a_scale == nullptr) == (a_shift == nullptr) && (b_scale == nullptr) == (b_shift == nullptr), "rv_ew_combine: scale and shift go together");
     EwArgs e{(const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, a_scale, a_shift, b_scale, b_shift, pixels, c / 8, ld_a, ld_b, ld_out, flags};
-    // (measured, profiles/r02_hbm_kernels.md: the row-range kernel wins on tensors beyond the Infinity Cache, 4.9-5.2 vs 4.7-4.8 TB/s;
-    //  on small ones its per-thread constant prologue costs more than the comb's address arithmetic, 2.9 vs 6.2 TB/s)
-    if (e.c8 <= 256 && pixels * c * 2 >= ((int64_t)256 << 20)) {
-        const int lanes_px = 256 / e.c8;
-        int64_t blocks = (pixels + lanes_px - 1) / lanes_px;
-        if (blocks > 4096) blocks = 4096;
-        if (e.b) hipLaunchKernelGGL((ew_combine_rows_kernel<true, true>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, e);  // <non-temporal, two operands>
-        else hipLaunchKernelGGL((ew_combine_rows_kernel<true, false>), dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, e);
+    const RvEwPlan plan = rv_plan_ew_combine(pixels, c, b != nullptr);  // (row-range kernel beyond the Infinity Cache, comb below: ewpass.h)
+    if (plan.form == RV_EW_FORM_ROWS) {
+        if (e.b) hipLaunchKernelGGL((ew_combine_rows_kernel<true, true>), dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, e);  // <non-temporal, two operands>
+        else hipLaunchKernelGGL((ew_combine_rows_kernel<true, false>), dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, e);
     } else {
-        hipLaunchKernelGGL(ew_combine_kernel, dim3(ew_grid(pixels * (c / 8))), dim3(256), 0, (hipStream_t)stream, e);
+        hipLaunchKernelGGL(ew_combine_kernel, dim3(plan.grid), dim3(256), 0, (hipStream_t)stream, e);
     }
     RV_CHECK_LAUNCH("ew_combine_kernel");
     return 0;
