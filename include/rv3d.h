@@ -303,7 +303,13 @@ int rv_head_final_bwd_apply(int64_t pixels, int32_t c, const void* y, int32_t ld
 /* Small-K layers whose input needs no gradient (1x1 conv with cin <= 8 followed by BatchNorm: the stem's 3 -> C positional
  * conv, the 5/6 -> C feature projections): BatchNorm backward AND the conv's weight gradient from one pass over
  * (dOut, y, v) -- dy is never written.  v = the conv input (bf16 NHWC, >= 8 stored channels), w_packed = the layer's packed
- * gather image (bf16 [c][ld_w]); dW is fp32 [c][cin].  Replaces cuDNN BatchNorm backward + conv2d backward-weight. */
+ * gather image (bf16 [c][ld_w]); dW is fp32 [c][cin].  Replaces cuDNN BatchNorm backward + conv2d backward-weight.
+ * Precondition (cin_pad = 4 for cin <= 4, else 8): the per-pixel passes -- rv_bn_bwd_smallk / _sums with RV_BNB_Y_FROM_INPUT and
+ * rv_smallk_forward's apply pass -- multiply ALL cin_pad columns of w_packed with the stored channels of v, so ld_w >= cin_pad,
+ * the columns cin..cin_pad-1 of w_packed are zero (rv_pack_weight pads with zeros) and the channels cin..cin_pad-1 of v are finite
+ * (any finite value; they also reach moms / moments and the planes R[d >= cin], which nothing reads).  The statistics pass of
+ * rv_smallk_forward and rv_bn_bwd_smallk_from_sums read the columns below cin only, and the statistics pass the moments of the
+ * channels below cin only. */
 int64_t rv_bn_bwd_smallk_workspace_bytes(int64_t pixels, int32_t c, int32_t cin);
 int rv_bn_bwd_smallk(int64_t pixels, int32_t c, const void* dout, int32_t ld_dout, const void* out, int32_t ld_out,
                      const void* y, int32_t ld_y, const float* scale, const float* shift, const float* mean,

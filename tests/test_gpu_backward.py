@@ -373,7 +373,7 @@ def test_meta_modulate_backward_fused_kernels_vs_fp32(N, H, W, C):
     coef = torch.stack([0.5 + torch.rand(C, generator=gen), 0.1 * torch.randn(C, generator=gen), 0.1 * torch.randn(C, generator=gen)]).to(DEV)
     lib = L.load()
     rows = lib.rv_meta_bwd_rows(L.i32(N), L.i32(H), L.i32(W))
-    partial = torch.zeros((rows + L.STATS_SCRATCH_ROWS, 2, C), dtype=torch.float32, device=DEV)
+    partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, C), float("nan"), dtype=torch.float32, device=DEV)
     dfeat = torch.empty_like(feat)
     dy = torch.empty_like(y)
     L.call("rv_meta_modulate_bwd_sums", L.ptr(dgeo), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.ptr(feat), L.i32(C),

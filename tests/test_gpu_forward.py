@@ -619,7 +619,7 @@ def test_pos_forward_kernel_vs_fp32(P, C):
     h1 = torch.full((P, C), float("nan"), dtype=torch.bfloat16, device=DEV)
     y2 = torch.full((P, C), float("nan"), dtype=torch.bfloat16, device=DEV)
     rows = L.load().rv_pos_forward_rows(L.i64(P))
-    partial = torch.zeros((rows + L.STATS_SCRATCH_ROWS, 2, C), dtype=torch.float32, device=DEV)
+    partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, C), float("nan"), dtype=torch.float32, device=DEV)
     L.call("rv_pos_forward", L.ptr(rel), L.i32(32), L.i32(3), L.i64(P), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1), L.ptr(w2), L.i32(C),
            L.ptr(h1), L.ptr(y2), L.ptr(partial), L.stream_ptr())
     torch.cuda.synchronize()
