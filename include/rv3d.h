@@ -719,7 +719,11 @@ int rv_assign_targets(const double* cuboids, int32_t m, const int32_t* box_offse
  *           background, coordinate, dimension, rotation, regression loss; optional soft targets (B,n_cls,H,W) and foreground map.
  * backward: d loss / d logits, d loss / d regressands (same NHWC strides), scaled by grad_scale * sums[15] -- the caller may copy
  *           the incoming gradient of the loss (a device scalar) into sums[15] instead of multiplying both tensors afterwards;
- *           reads sums[12], sums[13], sums[15] on device (no host round trip).  Padding channels of the gradient buffers are not written. */
+ *           reads sums[12], sums[13], sums[15] on device (no host round trip).  Padding channels: columns 8 .. ld_reg-1 of d_regressands
+ *           are never written.  Columns n_cls .. ld_logits-1 of d_logits are not written either, EXCEPT with ld_logits == 32 (the rows
+ *           the head kernels write: eight 16-byte stores per pixel), where the whole row is stored and these columns are all zero.
+ *           Padding columns of the inputs are never used: their values cannot reach any output (32-float logits rows are
+ *           loaded whole, so they may be read). */
 int rv_detection_loss_forward(const float* logits, int32_t ld_logits, const float* regressands, int32_t ld_reg,
                               const float* cart, const uint8_t* mask, const int64_t* labels, const int64_t* panoptics,
                               const float* reg_targets, const int64_t* points_per_obj, const int32_t* num_objects,
@@ -805,8 +809,10 @@ typedef struct {
  *   row n_entries = each of [16..23] summed over the entries ([16] is the loss), [12] / [13] = n_entries x the global numbers (the
  *   reference sums its collated list, :438-439), [15] = 1 (the backward pass's device-side factor, as sums[15] above).
  * backward, ONE launch: gradients of row n_entries [16] for every entry, scaled by grad_scale * sums[n_entries][15]; reads the
- *   normalisers from the rows on the device.  With one entry every tensor and row 0 equal the one-level entry points' results
- *   (the atomically accumulated [0..11] up to the order of the workgroups' additions). */
+ *   normalisers from the rows on the device.  Padding channels of every entry's gradient buffers as in rv_detection_loss_backward:
+ *   d_regressands columns 8 .. ld_reg-1 and d_logits columns n_cls .. ld_logits-1 are not written, except that an entry with
+ *   ld_logits == 32 gets its whole d_logits row stored, zeros in the padding columns.  With one entry every tensor and row 0 equal
+ *   the one-level entry points' results (the atomically accumulated [0..11] up to the order of the workgroups' additions). */
 int rv_detection_loss_multilevel_forward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
                                          double* sums, rvStream stream);
 int rv_detection_loss_multilevel_backward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
