@@ -860,6 +860,51 @@ int rv_detection_loss_multilevel_backward_aff(const rvLossEntry* host_entries, i
                                               rvStream stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Loss kinds: every classification and regression loss the configuration can name (nn/losses/classification.py:14-119,
+ * nn/functional/__init__.py:8-49; `_regression_loss` is any of four torch.nn losses).  Per class logit x with soft target t (the fp32
+ * value, detached): p = sigmoid(x), sp = softplus(x), bce = sp - x t; alpha / gamma are the rvLossParams fields.
+ *   RV_CLS_VARIFOCAL        t > 0 ? t bce : alpha p^gamma bce -- what the entry points above compute.
+ *   RV_CLS_FOCAL            alpha_t q^gamma bce with q = p (1 - t) + (1 - p) t and alpha_t = alpha t + (1 - alpha)(1 - t); alpha < 0: no
+ *                           alpha_t factor.  Its semantics are DECLARED here: the reference's FocalLoss calls torchvision's
+ *                           sigmoid_focal_loss, and torchvision is outside the reference tree (as with rv_wnms); this is the published
+ *                           definition, soft t included.  (The reference passes neither alpha nor gamma on, classification.py:83; that
+ *                           quirk is the Python class's business, the kernel takes any values.)
+ *                           d/dx = alpha_t [gamma q^(gamma-1) p (1-p) (1-2t) bce + q^gamma (p - t)].
+ *   RV_CLS_PENALTY_REDUCED  [t == 1] (1-p)^gamma bce + alpha (1-t)^4 p^gamma bce (functional/__init__.py:30-49); the second term runs
+ *                           over every element, t == 1 included, where it is 0.
+ *                           d/dx = [t == 1] (-(1-p)^gamma (gamma p (sp - x) + (1-p))) + alpha (1-t)^4 p^gamma (gamma (1-p) bce + (p - t)).
+ * 1 - p is formed as sigmoid(-x), never by subtraction; gamma 0, 1, 2, 3 are products, any other value goes through powf.
+ * Per regressand, on d = r - t, with reg_param = beta (SMOOTH_L1) or delta (HUBER), ignored by the other two:
+ *   RV_REG_L1         |d| -- what the entry points above compute
+ *   RV_REG_SMOOTH_L1  |d| < beta ? 0.5 d^2 / beta : |d| - 0.5 beta      (beta == 0 is L1, as torch defines it)
+ *   RV_REG_HUBER      |d| <= delta ? 0.5 d^2 : delta (|d| - 0.5 delta)
+ *   RV_REG_MSE        d^2
+ * The element-wise loss and its product with reg_weight are fp32 values, as for L1; the chain 1 / (points_per_obj + smoothing) * mask *
+ * coding_weights[j] / 8 is fp64.  Foreground (affinity != 0), background, the normalisers, the sums layout, phase two and
+ * grad_scale * sums[n_entries][15] do not depend on the kinds.
+ *
+ * rv_detection_loss_table_forward / _backward: rv_detection_loss_multilevel_forward / _backward (host_affinity_maps == NULL) and the
+ * _aff pair (host_affinity_maps != NULL: one device pointer per entry) with the kinds of *host_kinds.  With kinds {0, 0, any} every
+ * tensor equals the existing pairs' bit for bit and the rows up to the order of the atomic additions.  Refused (rv_last_error): NULL
+ * kinds, an unknown kind, SMOOTH_L1 with beta < 0, HUBER with delta <= 0, either with a reg_param that is not finite. */
+#define RV_CLS_VARIFOCAL 0
+#define RV_CLS_FOCAL 1
+#define RV_CLS_PENALTY_REDUCED 2
+#define RV_REG_L1 0
+#define RV_REG_SMOOTH_L1 1
+#define RV_REG_HUBER 2
+#define RV_REG_MSE 3
+typedef struct {
+    int32_t cls_kind, reg_kind;
+    float reg_param;
+} rvLossKinds;
+int rv_detection_loss_table_forward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                    const rvLossKinds* host_kinds, const float* const* host_affinity_maps, double* sums, rvStream stream);
+int rv_detection_loss_table_backward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                     const rvLossKinds* host_kinds, const float* const* host_affinity_maps, const double* sums,
+                                     float grad_scale, rvStream stream);
+
+/* ---------------------------------------------------------------------------------------
  * Detection evaluation: matching, AP, ATE / ASE / AOE, CDS with the AV2 sensor-dataset metric definitions (csrc/evaluate.hip).
  * The reference calls av2's CPU evaluator (nn/arch/detector.py:457-479); av2 is not part of the reference tree, so -- as for rv_wnms --
  * the semantics are DECLARED here: they restate the published AV2 detection metric and are not pinned against av2's binaries.

@@ -98,6 +98,12 @@ class LossParams(ctypes.Structure):
                [("azimuth_invariant", ctypes.c_int32)]
 
 
+class LossKinds(ctypes.Structure):
+    """``rvLossKinds``: the classification / regression loss of the ``rv_detection_loss_table_*`` pair (``CLS_*`` / ``REG_*``)."""
+
+    _fields_ = [("cls_kind", ctypes.c_int32), ("reg_kind", ctypes.c_int32), ("reg_param", ctypes.c_float)]
+
+
 class RoiLayer(ctypes.Structure):
     """``rvRoiLayer``: one raster of the ROI atlas (``converters/av2/roi.py``)."""
 
@@ -107,6 +113,8 @@ class RoiLayer(ctypes.Structure):
 
 ML_MAX_LEVELS, ML_MAX_ENTRIES = 8, 16  # RV_ML_MAX_LEVELS / RV_ML_MAX_ENTRIES
 AFFINITY_GAUSSIAN, AFFINITY_BEV = 0, 1  # RV_AFFINITY_* (rv_soft_assign)
+CLS_VARIFOCAL, CLS_FOCAL, CLS_PENALTY_REDUCED = 0, 1, 2  # RV_CLS_* (rvLossKinds.cls_kind)
+REG_L1, REG_SMOOTH_L1, REG_HUBER, REG_MSE = 0, 1, 2, 3  # RV_REG_* (rvLossKinds.reg_kind; reg_param = beta / delta)
 EVAL_MAX_THRESHOLDS, EVAL_MAX_DTS = 8, 1024  # RV_EVAL_MAX_* (rv_eval_match)
 WAYMO_MAX_DTS, WAYMO_MAX_GTS, WAYMO_MAX_SWEEPS = 1024, 1024, 65536  # RV_WAYMO_MAX_* (rv_waymo_match: per sweep and object type)
 WAYMO_NUM_CUTOFFS, WAYMO_NUM_BREAKDOWN_ROWS, WAYMO_NUM_RESULT_ROWS = 101, 16, 32  # RV_WAYMO_NUM_*

@@ -56,13 +56,75 @@ __device__ __forceinline__ void decode_centre(const float* r, float px, float py
 
 __device__ __forceinline__ float softplus(float x) { return fmaxf(x, 0.f) + log1pf(expf(-fabsf(x))); }
 
+// ---- loss kinds (rvLossKinds, include/rv3d.h): the per-element terms of the table pair.  alpha / gamma / the kinds are wave-uniform. ----
+// b^gamma without powf for the small integers
+__device__ __forceinline__ float pow_gamma(float b, float g) {
+    return g == 2.f ? b * b : (g == 1.f ? b : (g == 3.f ? b * b * b : (g == 0.f ? 1.f : powf(b, g))));
+}
+// gamma * b^(gamma - 1): the factor of d/dx b^gamma (gamma == 0: exactly 0, also at b == 0)
+__device__ __forceinline__ float dpow_gamma(float b, float g) {
+    return g == 2.f ? 2.f * b : (g == 1.f ? 1.f : (g == 3.f ? 3.f * (b * b) : (g == 0.f ? 0.f : g * powf(b, g - 1.f))));
+}
+
+// One class logit x with soft target t: the loss (BACKWARD == false) or d loss / d x.  One exponential serves sigmoid(x), sigmoid(-x) =
+// 1 - p (the other branch of the same select: never a subtraction) and both softplus values.
+template <int CLS, bool BACKWARD>
+__device__ __forceinline__ float cls_term(float x, float t, float alpha, float gamma) {
+    const float e = expf(-fabsf(x));
+    const float p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    const float sp = fmaxf(x, 0.f) + log1pf(e);
+    if (CLS == RV_CLS_VARIFOCAL) {  // (the text of the default path below: the same numbers)
+        const float pg = gamma == 2.f ? p * p : powf(p, gamma);
+        if (!BACKWARD) {
+            const float bce = sp - x * t;
+            return t > 0.f ? t * bce : alpha * pg * bce;
+        }
+        return t > 0.f ? t * (p - t) : alpha * pg * (gamma * (1.f - p) * sp + p);
+    }
+    const float np = x >= 0.f ? e / (1.f + e) : 1.f / (1.f + e);  // 1 - p
+    const float bce = sp - x * t;
+    if (CLS == RV_CLS_FOCAL) {
+        const float q = p * (1.f - t) + np * t;
+        const float at = alpha < 0.f ? 1.f : alpha * t + (1.f - alpha) * (1.f - t);
+        if (!BACKWARD) return at * pow_gamma(q, gamma) * bce;
+        return at * (dpow_gamma(q, gamma) * (p * np) * (1.f - 2.f * t) * bce + pow_gamma(q, gamma) * (p - t));
+    }
+    // RV_CLS_PENALTY_REDUCED: at t == 1 bce = softplus(x) - x = softplus(-x), formed without the cancellation
+    const float spn = fmaxf(-x, 0.f) + log1pf(e);
+    const float w = 1.f - t, w2 = w * w, w4 = w2 * w2;
+    const float pg = pow_gamma(p, gamma), npg = pow_gamma(np, gamma);
+    if (!BACKWARD) return (t == 1.f ? npg * spn : 0.f) + alpha * w4 * pg * bce;
+    return (t == 1.f ? -(npg * (gamma * p * spn + np)) : 0.f) + alpha * w4 * pg * (gamma * np * bce + (p - t));
+}
+
+// One regressand residual d = r - t: the element-wise loss, or its derivative (both before reg_weight).
+template <bool BACKWARD>
+__device__ __forceinline__ float reg_term(int kind, float param, float d) {
+    const float ad = fabsf(d);
+    const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    switch (kind) {
+        case RV_REG_SMOOTH_L1:  // (beta == 0: the comparison is never true -> L1, as torch defines it)
+            if (!BACKWARD) return ad < param ? 0.5f * d * d / param : ad - 0.5f * param;
+            return ad < param ? d / param : sgn;
+        case RV_REG_HUBER:
+            if (!BACKWARD) return ad <= param ? 0.5f * d * d : param * (ad - 0.5f * param);
+            return ad <= param ? d : param * sgn;
+        case RV_REG_MSE:
+            return BACKWARD ? 2.f * d : d * d;
+        default:
+            return BACKWARD ? sgn : ad;
+    }
+}
+
 // The work of workgroup `block` of `n_blocks` on one (level, task): shared by the one-level kernel and the entry-table kernel, which
 // differ only in where a workgroup finds its tensors.  total_fg / total_obj / gscale are read by the caller (BACKWARD only).
 // AFF_MAP: the pixel's affinity is read from `aff_map` (B,H,W), which rv_soft_assign filled (softassign.hip: BEV affinity,
 // normalize_affinities, finite k), instead of being the per-pixel exponential below.
-template <bool BACKWARD, bool AFF_MAP = false>
+// CLS: -1 = the default recipe (varifocal + L1, the text below as it always was); RV_CLS_* = the loss kinds of the table pair:
+// cls_term per class, reg_term(reg_kind, reg_param: beta / delta) per regressand.  Everything else -- affinity, foreground, normalisers, reductions -- is shared.
+template <bool BACKWARD, bool AFF_MAP = false, int CLS = -1>
 __device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int64_t n_blocks, double total_fg, double total_obj, float gscale,
-                                          const float* aff_map = nullptr) {
+                                          const float* aff_map = nullptr, int reg_kind = RV_REG_L1, float reg_param = 0.f) {
     const int64_t hw = (int64_t)a.H * a.W, total = (int64_t)a.B * hw;
     double acc[12];
 #pragma unroll
@@ -119,6 +181,14 @@ __device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int6
             const float x = lv[c >> 2][c & 3];
             const float t = (label == c) ? aff : 0.f;
             if (!BACKWARD && a.soft) a.soft[(b * a.n_cls + c) * hw + pix] = t;
+            if (CLS >= 0) {
+                const float v = cls_term<(CLS < 0 ? 0 : CLS), BACKWARD>(x, t, a.alpha, a.gamma);
+                if (!BACKWARD)
+                    cls_sum += v;
+                else
+                    gv[c >> 2][c & 3] = (float)((double)(v * a.cls_w * m) / total_fg) * gscale;
+                continue;
+            }
             const float e = expf(-fabsf(x));
             const float p = x >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
             const float sp = fmaxf(x, 0.f) + log1pf(e);
@@ -139,6 +209,14 @@ __device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int6
             const float x = a.logits[i * a.ld_logits + c];
             const float t = (label == c) ? aff : 0.f;
             if (!BACKWARD && a.soft) a.soft[(b * a.n_cls + c) * hw + pix] = t;
+            if (CLS >= 0) {
+                const float v = cls_term<(CLS < 0 ? 0 : CLS), BACKWARD>(x, t, a.alpha, a.gamma);
+                if (!BACKWARD)
+                    cls_sum += v;
+                else
+                    a.d_logits[i * a.ld_logits + c] = (float)((double)(v * a.cls_w * m) / total_fg) * gscale;
+                continue;
+            }
             // one exponential per class serves the sigmoid and the softplus; p^gamma is a product for the recipe's gamma = 2
             // (the transcendental functions, not the 34 floats per pixel, are what this kernel's time goes to)
             const float e = expf(-fabsf(x));
@@ -158,7 +236,7 @@ __device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int6
                 a.d_logits[i * a.ld_logits + c] = (float)((double)(g * a.cls_w * m) / total_fg) * gscale;
             }
         }
-        // ---- regression: L1 with the per-object normaliser in fp64 ----
+        // ---- regression: L1 (or reg_term of the configured kind) with the per-object normaliser in fp64 ----
         const bool reg_on = label < a.n_cls;
         const double norm = 1.0 / ((double)a.ppo[i] + (double)a.smoothing);
         if (!BACKWARD) {
@@ -169,13 +247,16 @@ __device__ __forceinline__ void loss_tile(const LossArgs& a, int64_t block, int6
             if (fg) acc[3] += 1.0;
 #pragma unroll
             for (int j = 0; j < 8; ++j)
-                if (reg_on) acc[4 + j] += (double)(fabsf(r[j] - tg[j]) * a.reg_w) * norm * (double)m * (double)a.coding[j] / 8.0;
+                if (reg_on) {
+                    const float l = CLS >= 0 ? reg_term<false>(reg_kind, reg_param, r[j] - tg[j]) : fabsf(r[j] - tg[j]);
+                    acc[4 + j] += (double)(l * a.reg_w) * norm * (double)m * (double)a.coding[j] / 8.0;
+                }
         } else {
             float dr[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float d = r[j] - tg[j];
-                const float sgn = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+                const float sgn = CLS >= 0 ? reg_term<true>(reg_kind, reg_param, d) : (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
                 const double g = reg_on ? (double)(sgn * a.reg_w) * norm * (double)m * (double)a.coding[j] / 8.0 / total_obj : 0.0;
                 dr[j] = (float)g * gscale;
             }
@@ -313,6 +394,20 @@ __global__ __launch_bounds__(256) void loss_table_aff_kernel(const LossTable t, 
     const double total_obj = BACKWARD ? a.sums[12] : 1.0;
     const float gscale = BACKWARD ? t.grad_scale * (float)t.sums[(int64_t)t.n * RV_LOSS_SUMS_LEN + 15] : 1.f;
     loss_tile<BACKWARD, true>(a, (int)blockIdx.x - t.block_begin[k], t.block_begin[k + 1] - t.block_begin[k], total_fg, total_obj, gscale, maps.map[k]);
+}
+
+// the table pair with loss kinds (rv_detection_loss_table_*): one instantiation per classification kind, the regression kind a uniform
+// run-time switch; AFF_MAP as above.  The default recipe never launches these.
+template <bool BACKWARD, bool AFF_MAP, int CLS>
+__global__ __launch_bounds__(256) void loss_table_kinds_kernel(const LossTable t, const AffMaps maps, const int reg_kind, const float reg_param) {
+    int k = 0;
+    while (k + 1 < t.n && (int)blockIdx.x >= t.block_begin[k + 1]) ++k;
+    const LossArgs a = table_args(t, k);
+    const double total_fg = BACKWARD ? a.sums[13] : 1.0;
+    const double total_obj = BACKWARD ? a.sums[12] : 1.0;
+    const float gscale = BACKWARD ? t.grad_scale * (float)t.sums[(int64_t)t.n * RV_LOSS_SUMS_LEN + 15] : 1.f;
+    loss_tile<BACKWARD, AFF_MAP, CLS>(a, (int)blockIdx.x - t.block_begin[k], t.block_begin[k + 1] - t.block_begin[k], total_fg, total_obj, gscale,
+                                      AFF_MAP ? maps.map[k] : nullptr, reg_kind, reg_param);
 }
 
 // phase two (reduce_multiscale_loss, detection_head.py:379-449): the global normalisers, every entry's scalars, and their sums over
@@ -560,5 +655,74 @@ extern "C" int rv_detection_loss_multilevel_backward_aff(const rvLossEntry* host
     t.grad_scale = grad_scale;
     hipLaunchKernelGGL(loss_table_aff_kernel<true>, dim3(t.block_begin[n_entries]), dim3(256), 0, (hipStream_t)stream, t, maps);
     RV_CHECK_LAUNCH("multi-level loss backward kernel (affinity maps)");
+    return 0;
+}
+
+namespace {
+
+int check_kinds(const rvLossKinds* kinds) {
+    RV_REQUIRE(kinds, "rv_detection_loss_table: null kinds");
+    RV_REQUIRE(kinds->cls_kind >= RV_CLS_VARIFOCAL && kinds->cls_kind <= RV_CLS_PENALTY_REDUCED, "rv_detection_loss_table: unknown classification kind %d",
+               kinds->cls_kind);
+    RV_REQUIRE(kinds->reg_kind >= RV_REG_L1 && kinds->reg_kind <= RV_REG_MSE, "rv_detection_loss_table: unknown regression kind %d", kinds->reg_kind);
+    if (kinds->reg_kind == RV_REG_SMOOTH_L1 || kinds->reg_kind == RV_REG_HUBER) {
+        RV_REQUIRE(std::isfinite(kinds->reg_param), "rv_detection_loss_table: reg_param is not finite");
+        RV_REQUIRE(kinds->reg_kind != RV_REG_SMOOTH_L1 || kinds->reg_param >= 0.f, "rv_detection_loss_table: SMOOTH_L1 needs beta >= 0, not %g",
+                   (double)kinds->reg_param);
+        RV_REQUIRE(kinds->reg_kind != RV_REG_HUBER || kinds->reg_param > 0.f, "rv_detection_loss_table: HUBER needs delta > 0, not %g", (double)kinds->reg_param);
+    }
+    return 0;
+}
+
+template <bool BACKWARD, bool AFF_MAP>
+void launch_kinds(const LossTable& t, const AffMaps& maps, const rvLossKinds& k, hipStream_t st) {
+    const dim3 grid(t.block_begin[t.n]), block(256);
+    switch (k.cls_kind) {
+        case RV_CLS_FOCAL:
+            hipLaunchKernelGGL((loss_table_kinds_kernel<BACKWARD, AFF_MAP, RV_CLS_FOCAL>), grid, block, 0, st, t, maps, k.reg_kind, k.reg_param);
+            break;
+        case RV_CLS_PENALTY_REDUCED:
+            hipLaunchKernelGGL((loss_table_kinds_kernel<BACKWARD, AFF_MAP, RV_CLS_PENALTY_REDUCED>), grid, block, 0, st, t, maps, k.reg_kind, k.reg_param);
+            break;
+        default:
+            hipLaunchKernelGGL((loss_table_kinds_kernel<BACKWARD, AFF_MAP, RV_CLS_VARIFOCAL>), grid, block, 0, st, t, maps, k.reg_kind, k.reg_param);
+    }
+}
+
+}  // namespace
+
+extern "C" int rv_detection_loss_table_forward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                               const rvLossKinds* host_kinds, const float* const* host_affinity_maps, double* sums, rvStream stream) {
+    LossTable t;
+    AffMaps maps;
+    memset(&maps, 0, sizeof(maps));
+    if (check_kinds(host_kinds) || fill_table(&t, host_entries, n_entries, host_params, sums, false)) return 1;
+    if (host_affinity_maps && fill_maps(&maps, host_affinity_maps, n_entries)) return 1;
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(sums, 0, (size_t)(n_entries + 1) * RV_LOSS_SUMS_LEN * sizeof(double), st);
+    if (e != hipSuccess) RV_FAIL("rv_detection_loss_table_forward: %s", hipGetErrorString(e));
+    if (host_affinity_maps)
+        launch_kinds<false, true>(t, maps, *host_kinds, st);
+    else
+        launch_kinds<false, false>(t, maps, *host_kinds, st);
+    hipLaunchKernelGGL(loss_table_finish_kernel, dim3(1), dim3(64), 0, st, t);
+    RV_CHECK_LAUNCH("loss table forward kernels");
+    return 0;
+}
+
+extern "C" int rv_detection_loss_table_backward(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params,
+                                                const rvLossKinds* host_kinds, const float* const* host_affinity_maps, const double* sums,
+                                                float grad_scale, rvStream stream) {
+    LossTable t;
+    AffMaps maps;
+    memset(&maps, 0, sizeof(maps));
+    if (check_kinds(host_kinds) || fill_table(&t, host_entries, n_entries, host_params, (double*)sums, true)) return 1;
+    if (host_affinity_maps && fill_maps(&maps, host_affinity_maps, n_entries)) return 1;
+    t.grad_scale = grad_scale;
+    if (host_affinity_maps)
+        launch_kinds<true, true>(t, maps, *host_kinds, (hipStream_t)stream);
+    else
+        launch_kinds<true, false>(t, maps, *host_kinds, (hipStream_t)stream);
+    RV_CHECK_LAUNCH("loss table backward kernel");
     return 0;
 }

@@ -20,6 +20,10 @@ Soft target assignment takes every option of ``targets_config`` (``math/ops/assi
 ``normalize_affinities`` and ``k`` (``.inf`` or an integer).  GAUSSIAN without normalisation and ``k = inf`` (every shipped recipe) is a
 per-pixel map inside the loss kernels, as before; any other combination runs ``rv_soft_assign`` (per-instance minimum / top-k threshold
 on the device, no host synchronisation) inside the loss node and the ``rv_detection_loss_multilevel_*_aff`` pair, see ``soft_options``.
+
+Both loss slots follow the configuration: ``_cls_loss`` VarifocalLoss | FocalLoss | PenaltyReducedFocalLoss, ``_regression_loss``
+``torch.nn.L1Loss`` | ``SmoothL1Loss`` | ``HuberLoss`` | ``MSELoss`` (``reduction: none``).  Varifocal + L1 (every shipped recipe) takes the
+routes above unchanged; any other pair runs the same table node on ``rv_detection_loss_table_*`` (``rvLossKinds``, include/rv3d.h).
 """
 
 from __future__ import annotations
@@ -275,7 +279,10 @@ class _MultiLevelLossFn(torch.autograd.Function):
 
     ``hp["soft"]`` (``soft_options``; absent = the per-pixel GAUSSIAN affinity inside the loss kernel): forward first runs ``rv_soft_assign``
     over the same entry table -- every entry's affinity map, selected per instance on the device -- and the ``_aff`` loss pair reads the
-    maps; backward reuses the maps forward saved (the affinity comes from detached inputs: there is no second selection)."""
+    maps; backward reuses the maps forward saved (the affinity comes from detached inputs: there is no second selection).
+
+    ``hp["kinds"]`` (``(RV_CLS_*, RV_REG_*, beta / delta)``; absent = varifocal + L1 on the pairs above): the same node on the
+    ``rv_detection_loss_table_*`` pair, with the maps when ``hp["soft"]`` asks for them."""
 
     @staticmethod
     def forward(ctx, entries, hp: Dict[str, Any], *tensors: Tensor):
@@ -304,8 +311,12 @@ class _MultiLevelLossFn(torch.autograd.Function):
         params = L.LossParams((ctypes.c_float * 8)(*[float(v) for v in hp["coding_weights"]]), hp["cls_weight"], hp["reg_weight"], hp["smoothing"],
                               hp["sigma"], hp["alpha"], hp["gamma"], 1 if hp["az_inv"] else 0)
         ctx.maps = None
+        ctx.kinds = L.LossKinds(*hp["kinds"]) if hp.get("kinds") is not None else None
         if hp.get("soft") is None:
-            L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), L.ptr(sums), L.stream_ptr())
+            if ctx.kinds is None:
+                L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), L.ptr(sums), L.stream_ptr())
+            else:
+                L.call("rv_detection_loss_table_forward", table, L.i32(n), ctypes.byref(params), ctypes.byref(ctx.kinds), None, L.ptr(sums), L.stream_ptr())
         else:
             fn, normalize, k = hp["soft"]
             off_d, m = hp["box_offsets"], int(hp["box_count"])
@@ -315,7 +326,10 @@ class _MultiLevelLossFn(torch.autograd.Function):
             ws = torch.empty(max(int(L.load().rv_soft_assign_workspace_bytes(L.i32(n), L.i32(m), L.i32(B))), 1), dtype=torch.uint8, device=dev)
             L.call("rv_soft_assign", table, L.i32(n), ctypes.byref(params), L.i32(fn), L.i32(1 if normalize else 0), L.i32(k), L.ptr(off_d),
                    L.i32(m), L.ptr(ws), map_ptrs, L.stream_ptr())
-            L.call("rv_detection_loss_multilevel_forward_aff", table, L.i32(n), ctypes.byref(params), map_ptrs, L.ptr(sums), L.stream_ptr())
+            if ctx.kinds is None:
+                L.call("rv_detection_loss_multilevel_forward_aff", table, L.i32(n), ctypes.byref(params), map_ptrs, L.ptr(sums), L.stream_ptr())
+            else:
+                L.call("rv_detection_loss_table_forward", table, L.i32(n), ctypes.byref(params), ctypes.byref(ctx.kinds), map_ptrs, L.ptr(sums), L.stream_ptr())
             ctx.maps = (map_ptrs, maps)
             for ent, amap in zip(entries, maps):
                 ent["affinity"] = amap
@@ -334,7 +348,10 @@ class _MultiLevelLossFn(torch.autograd.Function):
             ctx.table[e].d_logits, ctx.table[e].d_regressands = d_l.data_ptr(), d_r.data_ptr()
             bufs.append((d_l, d_r))
         ctx.sums[n, 15:16].copy_(g_loss.reshape(1))  # the incoming gradient as the kernel's device-side factor
-        if ctx.maps is None:
+        if ctx.kinds is not None:
+            L.call("rv_detection_loss_table_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), ctypes.byref(ctx.kinds),
+                   None if ctx.maps is None else ctx.maps[0], L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
+        elif ctx.maps is None:
             L.call("rv_detection_loss_multilevel_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
         else:
             L.call("rv_detection_loss_multilevel_backward_aff", ctx.table, L.i32(n), ctypes.byref(ctx.params), ctx.maps[0], L.ptr(ctx.sums), L.f32(1.0),
@@ -354,7 +371,55 @@ def _instantiate(cfg: Any) -> Any:
     if target.startswith("torchbox3d."):
         target = "range_view_3d_detection_amd." + target[len("torchbox3d."):]
     mod, _, name = target.rpartition(".")
-    return getattr(importlib.import_module(mod), name)(**cfg)
+    module = importlib.import_module(mod)
+    if not hasattr(module, name):
+        raise NotImplementedError(f"{target}: {mod} has no {name}")
+    return getattr(module, name)(**cfg)
+
+
+def _classification_kind(cls_loss: Any) -> Tuple[int, float, float]:
+    """``(RV_CLS_* kind, alpha, gamma)`` the fused kernel takes for the instantiated ``_cls_loss`` (``None``: the varifocal defaults).
+    The class decides, not its fields: ``FocalLoss`` hands over 0.25 / 2.0 whatever it was configured with (see its docstring)."""
+    from ..losses.classification import FocalLoss, PenaltyReducedFocalLoss, VarifocalLoss
+
+    if cls_loss is None:
+        return L.CLS_VARIFOCAL, 0.75, 2.0
+    if getattr(cls_loss, "reduction", "none") != "none":
+        raise NotImplementedError(f"_cls_loss reduction {cls_loss.reduction!r}: the fused loss reduces element-wise losses itself (reduction: none)")
+    if type(cls_loss) is VarifocalLoss:
+        return L.CLS_VARIFOCAL, float(cls_loss.alpha), float(cls_loss.gamma)
+    if type(cls_loss) is FocalLoss:
+        return L.CLS_FOCAL, float(cls_loss.kernel_alpha), float(cls_loss.kernel_gamma)
+    if type(cls_loss) is PenaltyReducedFocalLoss:
+        return L.CLS_PENALTY_REDUCED, float(cls_loss.alpha), float(cls_loss.gamma)
+    raise NotImplementedError(f"_cls_loss {type(cls_loss).__module__}.{type(cls_loss).__qualname__}: the fused loss implements VarifocalLoss, "
+                              "FocalLoss and PenaltyReducedFocalLoss")
+
+
+# `_regression_loss._target_` by its exact class name -> (RV_REG_* kind, the keyword of its parameter, torch's default)
+_REGRESSION_KINDS = {"L1Loss": (L.REG_L1, None, 0.0), "SmoothL1Loss": (L.REG_SMOOTH_L1, "beta", 1.0), "HuberLoss": (L.REG_HUBER, "delta", 1.0),
+                     "MSELoss": (L.REG_MSE, None, 0.0)}
+
+
+def _regression_kind(cfg: Any) -> Tuple[int, float, nn.Module]:
+    """``(RV_REG_* kind, beta / delta, the instantiated torch module)`` of ``_regression_loss`` (``None``: ``torch.nn.L1Loss``).  The target
+    is matched by its exact class name under ``torch.nn`` or ``torch.nn.modules.loss`` (a test by suffix once took SmoothL1Loss for L1Loss)."""
+    if cfg is None or isinstance(cfg, str):
+        return L.REG_L1, 0.0, nn.L1Loss(reduction="none")
+    cfg = dict(cfg)
+    target = str(cfg.pop("_target_", "torch.nn.L1Loss"))
+    cfg.pop("_recursive_", None)
+    mod, _, name = target.rpartition(".")
+    if mod not in ("torch.nn", "torch.nn.modules.loss") or name not in _REGRESSION_KINDS:
+        raise NotImplementedError(f"_regression_loss {target}: the fused loss implements torch.nn.L1Loss, SmoothL1Loss, HuberLoss and MSELoss")
+    module = getattr(nn, name)(**cfg)
+    if module.reduction != "none":
+        raise NotImplementedError(f"_regression_loss reduction {module.reduction!r}: the fused loss reduces element-wise losses itself (reduction: none)")
+    kind, key, _ = _REGRESSION_KINDS[name]
+    param = float(getattr(module, key)) if key else 0.0
+    if (kind == L.REG_SMOOTH_L1 and not param >= 0.0) or (kind == L.REG_HUBER and not param > 0.0) or param == float("inf"):
+        raise ValueError(f"_regression_loss {target}: {key} = {param}")
+    return kind, param, module
 
 
 class DetectionHead(nn.Module):
@@ -387,10 +452,9 @@ class DetectionHead(nn.Module):
                 for k, _ in tasks_cfg.items()})
             for stride, num_channels in fpn.items()})
         self.cls_loss = _instantiate(_cls_loss)
-        reg_target = str(dict(_regression_loss).get("_target_", "torch.nn.L1Loss")) if _regression_loss is not None and not isinstance(_regression_loss, str) else "torch.nn.L1Loss"
-        if not reg_target.endswith("L1Loss"):
-            raise NotImplementedError("the fused HIP loss implements the configured torch.nn.L1Loss regression loss")
-        self.regression_loss = nn.L1Loss(reduction="none")
+        _classification_kind(self.cls_loss)  # (an unknown class or reduction raises here, not in the first step)
+        reg_kind, reg_param, self.regression_loss = _regression_kind(_regression_loss)
+        self._reg_kind = (reg_kind, reg_param)
 
     def forward(self, input: Dict[int, Tensor], data: Dict[Any, Any], return_loss: bool = False):
         multiscale_outputs: Dict[int, Dict[Any, Any]] = {}
@@ -432,12 +496,17 @@ class DetectionHead(nn.Module):
         strides, tasks = [int(s) for s in self.fpn.keys()], list(self.tasks_cfg.keys())
         tc = self.targets_config
         soft = soft_options(tc)
+        cls_kind, alpha, gamma = _classification_kind(self.cls_loss)
         hp = {
             "coding_weights": self.coding_weights, "cls_weight": float(self.classification_weight), "reg_weight": float(self.regression_weight),
             "smoothing": float(self.additive_smoothing), "sigma": float(_cfg_get(tc, "sigma", 0.75)),
-            "alpha": float(getattr(self.cls_loss, "alpha", 0.75)), "gamma": float(getattr(self.cls_loss, "gamma", 2.0)),
+            "alpha": alpha, "gamma": gamma,
             "az_inv": bool(_cfg_get(tc, "enable_azimuth_invariant_targets", True)),
         }
+        if (cls_kind, self._reg_kind[0]) != (L.CLS_VARIFOCAL, L.REG_L1):
+            # any other loss kind: the table node on the rv_detection_loss_table_* pair (one entry is a legal table); the default kinds
+            # keep the three routes below, launch for launch
+            hp["kinds"] = (cls_kind, self._reg_kind[0], self._reg_kind[1])
         if not _soft_is_default(soft):
             # a per-instance affinity (BEV, normalize_affinities, finite k): one entry is a legal table, so the one-level recipe goes
             # through the multi-level node too; the instance table is indexed by the CSR of the annotation table
@@ -449,7 +518,7 @@ class DetectionHead(nn.Module):
                 _, hp["box_offsets"], hp["box_count"] = _stage_annotations(multiscale_data, out0["cart"].shape[0], out0["cart"].device)
             hp["soft"] = soft
             return self._multilevel_loss(multiscale_outputs, multiscale_data, strides, tasks, hp)
-        if strides != [1] or len(tasks) != 1 or _assignment_method(tc) is not None:
+        if "kinds" in hp or strides != [1] or len(tasks) != 1 or _assignment_method(tc) is not None:
             return self._multilevel_loss(multiscale_outputs, multiscale_data, strides, tasks, hp)
         stride, task_id = strides[0], tasks[0]
         out = multiscale_outputs[stride]
