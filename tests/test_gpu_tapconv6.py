@@ -4,7 +4,7 @@ Same method as test_gpu_tapconv4/5.py: small-integer activations and weights mak
 the bf16 output must equal the CPU convolution rounded once to bf16, bit for bit, whatever the summation order.  Every case
 asserts (``rv_tap_launch_info``) that generation 6 runs.  Shapes cover ragged tile rows (H % 16 != 0) and columns
 (W % 32 != 0), one / two / many 32-channel chunks (halo double-buffering, every position of the counted waits), one to four
-channel tiles, bias, batch statistics (four partial rows per tile), the conv-transpose phases (2 x 3 taps), 3 x 2 kernels,
+channel tiles, bias, batch statistics (four partial rows per tile -- also under a persistent grid, exactly), the conv-transpose phases (2 x 3 taps), 3 x 2 kernels,
 the accumulate epilogue, the BatchNorm-backward-sum epilogue and a race screen on random data.
 """
 
@@ -31,6 +31,11 @@ def _small_grids_allowed():
         yield
 
 
+# 2 x 48 x 512 pixels, 32 -> 384 channels (the shape of test_gpu_tap_bnb_epilogue.py's per-tile case); operands in -1..1 keep the sum of
+# squares of a channel below 2^24
+_PER_TILE_ROWS = (32, 384, 2, 48, 512)
+
+
 def _run(module, x, stats=False):
     from range_view_3d_detection_amd import _lib as L
     from range_view_3d_detection_amd import engine as E
@@ -50,21 +55,37 @@ def _run(module, x, stats=False):
                                                  (512, 512, 1, 64, 288, False),   # sixteen chunks, four channel tiles
                                                  (64, 128, 8, 16, 32, False),     # a single tile per image
                                                  (320, 128, 3, 33, 1030, False),  # ten chunks, ragged
-                                                 (128, 384, 1, 16, 96, True)])    # three channel tiles
+                                                 (128, 384, 1, 16, 96, True),     # three channel tiles
+                                                 _PER_TILE_ROWS + (False,)])      # statistics rows per TILE under a persistent grid
 def test_gather_3x3_exact(cin, cout, N, H, W, bias):
+    per_tile = (cin, cout, N, H, W) == _PER_TILE_ROWS
     g = torch.Generator().manual_seed(cin + W)
     m = torch.nn.Conv2d(cin, cout, 3, padding=1, bias=bias)
-    m.weight.data = _ints(m.weight.shape, g, -2, 3)
+    m.weight.data = _ints(m.weight.shape, g, -1, 2) if per_tile else _ints(m.weight.shape, g, -2, 3)
     if bias:
         m.bias.data = _ints(m.bias.shape, g, -8, 9)
-    x = _ints((N, cin, H, W), g)
+    x = _ints((N, cin, H, W), g, -1, 2) if per_tile else _ints((N, cin, H, W), g)
     ref = F.conv2d(x, m.weight.data, m.bias.data if bias else None, padding=1)
+    if per_tile:  # (on the reference, first: every fp32 partial sum of the statistics is an integer below 2^24 -- exact in any order)
+        assert float((ref.double() ** 2).sum(dim=(0, 2, 3)).max()) < 2 ** 24
     out, op = _run(m.to(DEV), x.to(DEV), stats=not bias)
     assert torch.equal(out.cpu(), ref.bfloat16().float())
     if not bias:
         rows = op.partial[: op.rows].double().sum(dim=0).cpu()  # (2, C)
         assert torch.allclose(rows[0, :cout], ref.double().sum(dim=(0, 2, 3)), rtol=1e-6, atol=1e-3)
         assert torch.allclose(rows[1, :cout], (ref.double() ** 2).sum(dim=(0, 2, 3)), rtol=1e-5)
+    if per_tile:
+        from range_view_3d_detection_amd import _lib as L
+        from range_view_3d_detection_amd import engine as E
+
+        cu = E.cu_count(DEV)
+        info = L.tap_launch_info(op.layer.geom, op.shape, False)
+        # 96 pixel tiles x 3 channel tiles on a persistent grid of cu & ~7 workgroups, and 3 does not divide its eighth: a workgroup's
+        # tiles belong to different channel tiles, so the rows are written per tile (four each), not accumulated per workgroup
+        assert info[2] * info[3] > cu and ((cu & ~7) // 8) % info[3] != 0 and op.rows == 4 * info[2], (info, op.rows, cu)
+        part = op.partial[: op.rows + L.STATS_SCRATCH_ROWS].cpu()
+        assert bool(torch.isfinite(part[: op.rows]).all())
+        assert torch.equal(rows[0, :cout], ref.double().sum(dim=(0, 2, 3))) and torch.equal(rows[1, :cout], (ref.double() ** 2).sum(dim=(0, 2, 3)))
 
 
 def test_gather_3x2_exact():
