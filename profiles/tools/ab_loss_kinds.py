@@ -72,11 +72,11 @@ VARIANTS = {  # name -> (params, kinds or None = the existing pair)
 def step(p, kinds):
     st = L.stream_ptr()
     if kinds is None:
-        L.call("rv_detection_loss_multilevel_forward", table, L.i32(1), ctypes.byref(p), L.ptr(sums), st)
-        L.call("rv_detection_loss_multilevel_backward", table, L.i32(1), ctypes.byref(p), L.ptr(sums), L.f32(1.0), st)
+        L.call("rv_detection_loss_multilevel_forward", table, 1, ctypes.byref(p), L.ptr(sums), st)
+        L.call("rv_detection_loss_multilevel_backward", table, 1, ctypes.byref(p), L.ptr(sums), 1.0, st)
     else:
-        L.call("rv_detection_loss_table_forward", table, L.i32(1), ctypes.byref(p), ctypes.byref(kinds), None, L.ptr(sums), st)
-        L.call("rv_detection_loss_table_backward", table, L.i32(1), ctypes.byref(p), ctypes.byref(kinds), None, L.ptr(sums), L.f32(1.0), st)
+        L.call("rv_detection_loss_table_forward", table, 1, ctypes.byref(p), ctypes.byref(kinds), None, L.ptr(sums), st)
+        L.call("rv_detection_loss_table_backward", table, 1, ctypes.byref(p), ctypes.byref(kinds), None, L.ptr(sums), 1.0, st)
 
 
 names = list(VARIANTS)

@@ -15,7 +15,7 @@ for (px, c, two) in [(4*64*2048, 512, False), (4*64*2048, 256, False), (4*64*204
     a = torch.randn(px, c, device=dev).bfloat16(); b = torch.randn(px, c, device=dev).bfloat16() if two else None
     out = torch.empty_like(a)
     sc = torch.rand(c, device=dev) + 0.5; sh = torch.randn(c, device=dev) * 0.1
-    t = bench(lambda: L.call("rv_ew_combine", L.i64(px), L.i32(c), L.ptr(a), L.i32(c), L.ptr(sc), L.ptr(sh), L.ptr(b) if two else None, L.i32(c), L.ptr(sc) if two else None,
-                              L.ptr(sh) if two else None, L.ptr(out), L.i32(c), L.i32(L.EW_RELU_A | (L.EW_RELU_OUT if two else 0)), L.stream_ptr()))
+    t = bench(lambda: L.call("rv_ew_combine", px, c, L.ptr(a), c, L.ptr(sc), L.ptr(sh), L.ptr(b) if two else None, c, L.ptr(sc) if two else None,
+                              L.ptr(sh) if two else None, L.ptr(out), c, L.EW_RELU_A | (L.EW_RELU_OUT if two else 0), L.stream_ptr()))
     nb = (3 if two else 2) * px * c * 2 / 1e9
     print(f"px {px} c {c} operands {2 if two else 1}: {t*1e3:7.1f} us {nb/t:6.2f} TB/s")

@@ -17,12 +17,12 @@ pos, dgeo, feat = bf(N, H, W, 9, C), bf(N, H, W, 9, C), bf(N, H, W, C)
 geo, dy, dfeat = torch.empty_like(pos), torch.empty_like(pos), torch.empty_like(feat)
 sc, sh, mu, isd = torch.rand(C, device=dev) + 0.5, torch.randn(C, device=dev) * 0.1, torch.randn(C, device=dev) * 0.1, torch.rand(C, device=dev) + 0.5
 coef = torch.rand(3, C, device=dev)
-rows = L.load().rv_meta_bwd_rows(L.i32(N), L.i32(H), L.i32(W))
+rows = L.load().rv_meta_bwd_rows(N, H, W)
 partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, C), dtype=torch.float32, device=dev)
 T = pos.numel() * 2 / 1e9
-t = bench(lambda: L.call("rv_meta_modulate", L.ptr(pos), L.ptr(sc), L.ptr(sh), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(geo), L.stream_ptr()))
+t = bench(lambda: L.call("rv_meta_modulate", L.ptr(pos), L.ptr(sc), L.ptr(sh), L.ptr(feat), C, N, H, W, C, L.ptr(geo), L.stream_ptr()))
 print(f"modulate fwd   {t*1e3:7.1f} us  {(2*T + T/9)/t:5.2f} TB/s")
-t = bench(lambda: L.call("rv_meta_modulate_bwd_sums", L.ptr(dgeo), L.ptr(pos), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(dfeat), L.i32(C), L.ptr(partial), L.stream_ptr()))
+t = bench(lambda: L.call("rv_meta_modulate_bwd_sums", L.ptr(dgeo), L.ptr(pos), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd), L.ptr(feat), C, N, H, W, C, L.ptr(dfeat), C, L.ptr(partial), L.stream_ptr()))
 print(f"bwd sums       {t*1e3:7.1f} us  {(2*T + 2*T/9)/t:5.2f} TB/s")
-t = bench(lambda: L.call("rv_meta_modulate_bwd_apply", L.ptr(dgeo), L.ptr(pos), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd), L.ptr(coef), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(dy), L.stream_ptr()))
+t = bench(lambda: L.call("rv_meta_modulate_bwd_apply", L.ptr(dgeo), L.ptr(pos), L.ptr(sc), L.ptr(sh), L.ptr(mu), L.ptr(isd), L.ptr(coef), L.ptr(feat), C, N, H, W, C, L.ptr(dy), L.stream_ptr()))
 print(f"bwd apply      {t*1e3:7.1f} us  {(3*T + T/9)/t:5.2f} TB/s")

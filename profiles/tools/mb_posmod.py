@@ -26,11 +26,11 @@ for tag, dt in (("bf16", torch.bfloat16), ("f16", torch.float16)):
         geo = torch.empty(N * H * W, 9 * C, dtype=dt, device=dev)
         T = P * C * 2 / 1e9
         with L.operand(tag):
-            ta = bench(lambda: L.call("rv_pos_forward", L.ptr(rel), L.i32(32), L.i32(3), L.i64(P), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1), L.ptr(w2), L.i32(C),
+            ta = bench(lambda: L.call("rv_pos_forward", L.ptr(rel), 32, 3, P, L.ptr(w1), 32, L.ptr(s1), L.ptr(t1), L.ptr(w2), C,
                                       L.ptr(h1), L.ptr(y2), None, L.stream_ptr()))
-            tb = bench(lambda: L.call("rv_meta_modulate", L.ptr(y2), L.ptr(s2), L.ptr(t2), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(geo),
+            tb = bench(lambda: L.call("rv_meta_modulate", L.ptr(y2), L.ptr(s2), L.ptr(t2), L.ptr(feat), C, N, H, W, C, L.ptr(geo),
                                       L.stream_ptr()))
-            tc = bench(lambda: L.call("rv_pos_modulate_forward", L.ptr(rel), L.i32(32), L.i32(3), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1), L.ptr(w2), L.i32(C),
-                                      L.ptr(s2), L.ptr(t2), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.ptr(geo), L.stream_ptr()))
+            tc = bench(lambda: L.call("rv_pos_modulate_forward", L.ptr(rel), 32, 3, L.ptr(w1), 32, L.ptr(s1), L.ptr(t1), L.ptr(w2), C,
+                                      L.ptr(s2), L.ptr(t2), L.ptr(feat), C, N, H, W, L.ptr(geo), L.stream_ptr()))
         print(f"{tag} C={C}: pos_forward {ta*1e3:7.1f} us + modulate {tb*1e3:7.1f} us = {(ta+tb)*1e3:7.1f}   fused {tc*1e3:7.1f} us ({T/tc:4.2f} TB/s written, "
               f"{2.0*P*C*C/tc/1e9:5.0f} TFLOP/s)", flush=True)

@@ -17,7 +17,7 @@ for C in (512, 256):
     grad = torch.empty((C, C, 3, 3), dtype=torch.float32, device=dev)
     u = torch.randn(N, H, W, C, device=dev).to(torch.bfloat16)
     v = torch.randn(N, H, W, C, device=dev).to(torch.bfloat16)
-    call = lambda: L.call("rv_tap_wgrad", ctypes.byref(g), ctypes.byref(s), L.ptr(u), L.i32(C), L.ptr(v), L.i32(C), None, None, L.i32(1), L.ptr(grad), L.ptr(ws), L.stream_ptr())
+    call = lambda: L.call("rv_tap_wgrad", ctypes.byref(g), ctypes.byref(s), L.ptr(u), C, L.ptr(v), C, None, None, 1, L.ptr(grad), L.ptr(ws), L.stream_ptr())
     for _ in range(20):
         call()
     torch.cuda.synchronize()

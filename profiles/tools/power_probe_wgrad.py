@@ -31,7 +31,7 @@ def loop(u, v, stream, secs):
     with torch.cuda.stream(stream):
         while time.time() - t0 < secs:
             for _ in range(10):
-                L.call("rv_tap_wgrad", ctypes.byref(g), ctypes.byref(s), L.ptr(u), L.i32(C), L.ptr(v), L.i32(C), None, None, L.i32(1), L.ptr(grad), L.ptr(ws),
+                L.call("rv_tap_wgrad", ctypes.byref(g), ctypes.byref(s), L.ptr(u), C, L.ptr(v), C, None, None, 1, L.ptr(grad), L.ptr(ws),
                        L.stream_ptr())
             stream.synchronize(); n += 10
     return (time.time() - t0) / n * 1e6

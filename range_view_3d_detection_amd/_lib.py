@@ -1,5 +1,9 @@
 """ctypes binding of ``librv3d_hip.so`` (the C ABI declared in ``include/rv3d.h``).
 
+``include/rv3d.h`` is the single source of the binding's types: ``prototypes()`` parses its declarations once per process and
+``load()`` sets ``restype`` / ``argtypes`` of every declared symbol from them.  Call sites pass plain Python values (``int``,
+``float``, ``None``, ``ptr(t)``, a ctypes Structure or array); a wrong argument count or a wrong struct raises in Python.
+
 There is deliberately no CPU fallback: if the library is missing or a call fails the host
 code raises.  ``load()`` only dlopens the library (works without a GPU, which is what the
 CPU test-suite checks); every compute entry point needs a device.
@@ -10,7 +14,8 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-from typing import Dict, List, Optional
+import functools
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -163,11 +168,56 @@ def act_dtype() -> "torch.dtype":
     return torch.float16 if _OPERAND == "f16" else torch.bfloat16
 
 
-def declared_symbols() -> List[str]:
-    """Every function name declared in include/rv3d.h (used by the export test)."""
+_SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = ("void", "float", "double", "uint8_t", "int32_t", "int64_t", "uint64_t")  # T*, const T*, T* const*: all c_void_p
+_STRUCTS = {"rvTapGeom": ctypes.POINTER(TapGeom), "rvTapShape": ctypes.POINTER(TapShape), "rvBnbEpilogue": ctypes.POINTER(BnbEpilogue),
+            "rvTargetLevel": ctypes.POINTER(TargetLevel), "rvTargetOut": ctypes.POINTER(TargetOut), "rvLossEntry": ctypes.POINTER(LossEntry),
+            "rvLossParams": ctypes.POINTER(LossParams), "rvLossKinds": ctypes.POINTER(LossKinds),
+            # fed raw memory: converters/av2/roi.py builds the table as a numpy record array and keeps it in a device tensor
+            "rvRoiLayer": ctypes.c_void_p}
+
+
+def _ctype(decl: str, symbol: str):
+    """ctypes type of a parameter / return type as include/rv3d.h spells it."""
+    words = decl.replace("*", " * ").split()
+    base, depth = [w for w in words if w not in ("const", "*")], words.count("*")
+    if len(base) == 1:
+        if depth == 0 and base[0] in _SCALARS:
+            return _SCALARS[base[0]]
+        if (depth == 0 and base[0] == "rvStream") or (depth >= 1 and base[0] in _POINTEES):
+            return ctypes.c_void_p
+        if depth == 1 and base[0] in _STRUCTS:
+            return _STRUCTS[base[0]]
+        if words == ["const", "char", "*"]:
+            return ctypes.c_char_p
+    raise RvError(f"include/rv3d.h: cannot map the type {decl!r} in the declaration of {symbol}")
+
+
+@functools.lru_cache(maxsize=None)
+def prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    """``name -> (restype, ((ctype, parameter name), ...))`` of every function declared in include/rv3d.h."""
     text = open(HEADER_PATH).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", text)))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\b[^{;]*\{.*?\}[^;]*;", "", text, flags=re.S)
+    table = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s*]*?)\b(rv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        plist = []
+        for p in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"\s*(.*?)\b(\w+)\s*", p, flags=re.S)
+            if m is None or not m.group(1).strip():
+                raise RvError(f"include/rv3d.h: cannot parse the parameter {p.strip()!r} of {name}")
+            plist.append((_ctype(m.group(1), name), m.group(2)))
+        table[name] = (_ctype(ret, name), tuple(plist))
+    unparsed = set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", text)) - set(table)
+    if unparsed:
+        raise RvError(f"include/rv3d.h: cannot parse the declaration of {sorted(unparsed)}")
+    return table
+
+
+def declared_symbols() -> List[str]:
+    """Every function name declared in include/rv3d.h (used by the export test)."""
+    return sorted(prototypes())
 
 
 def load(tag: Optional[str] = None) -> ctypes.CDLL:
@@ -195,55 +245,38 @@ def _dlopen(path: str) -> ctypes.CDLL:
     if torch.cuda.device_count() > 0 and torch.cuda.is_available():
         torch.cuda.init()
     lib = ctypes.CDLL(path)
-    lib.rv_last_error.restype = ctypes.c_char_p
-    for name in ("rv_packed_weight_bytes", "rv_decode_num_candidates", "rv_wnms_workspace_bytes", "rv_tap_wgrad_workspace_bytes", "rv_bn_bwd_smallk_workspace_bytes", "rv_smallk_forward_workspace_bytes", "rv_nms_sweeps_workspace_bytes", "rv_nms_rotated_workspace_bytes", "rv_pack_batch_entry_bytes", "rv_soft_assign_workspace_bytes", "rv_db_paste_workspace_bytes",
-                 "rv_eval_summarize_workspace_bytes", "rv_waymo_match_workspace_bytes", "rv_roi_rasterize_workspace_bytes"):
-        if hasattr(lib, name):
-            getattr(lib, name).restype = ctypes.c_int64
+    # restype / argtypes of every declared symbol; the parameter names make ctypes refuse extra arguments too (a bare cdecl
+    # function pointer ignores them) and accept them as keywords
+    for name, (restype, params) in prototypes().items():
+        try:
+            fn = ctypes.CFUNCTYPE(restype, *[t for t, _ in params])((name, lib), tuple((1, p) for _, p in params))
+        except AttributeError:
+            raise RvError(f"{path} does not export {name}, which include/rv3d.h declares") from None
+        setattr(lib, name, fn)
     return lib
-
-
-def _as_arg(v):
-    if v is None:
-        return ctypes.c_void_p(0)
-    if isinstance(v, (ctypes.Structure,)):
-        return ctypes.byref(v)
-    if isinstance(v, float):
-        return ctypes.c_float(v)
-    if isinstance(v, int):
-        return ctypes.c_int64(v) if abs(v) > 0x7FFFFFFF else ctypes.c_int32(v)
-    return v
 
 
 _DEBUG = bool(int(os.environ.get("RV3D_DEBUG_SYNC", "0")))
 
 
-def _v(a):
-    return getattr(a, "value", a)
-
-
-def _px_c(a):
-    return float(_v(a[0])) * float(_v(a[1]))
-
-
 # Algorithmic bytes (every operand tensor once in, every result once out, 16-bit activations) of the HBM-bound entry
-# points, from their own arguments -- bench.py's `roofline_hbm` prices the group against the HBM roofline.  Argument positions as
-# declared in include/rv3d.h.
+# points, from their own arguments by the parameter names of include/rv3d.h -- bench.py's `roofline_hbm` prices the group against the
+# HBM roofline.
 HBM_BYTES = {
-    "rv_ew_combine": lambda a: 2.0 * _px_c(a) * (2 + (_v(a[6]) is not None)),
-    "rv_bn_bwd_reduce": lambda a: 2.0 * _px_c(a) * (2 + (_v(a[4]) is not None)),
-    "rv_bn_bwd_apply": lambda a: 2.0 * _px_c(a) * (3 + (_v(a[4]) is not None) + 2 * (_v(a[16]) is not None)),
-    "rv_bn_bwd_reduce_pair": lambda a: 2.0 * _px_c(a) * 4,
-    "rv_bn_bwd_apply_pair": lambda a: 2.0 * _px_c(a) * 6,
+    "rv_ew_combine": lambda a: 2.0 * a["pixels"] * a["c"] * (2 + (a["b"] is not None)),
+    "rv_bn_bwd_reduce": lambda a: 2.0 * a["pixels"] * a["c"] * (2 + (a["out"] is not None)),
+    "rv_bn_bwd_apply": lambda a: 2.0 * a["pixels"] * a["c"] * (3 + (a["out"] is not None) + 2 * (a["dres"] is not None)),
+    "rv_bn_bwd_reduce_pair": lambda a: 2.0 * a["pixels"] * a["c"] * 4,
+    "rv_bn_bwd_apply_pair": lambda a: 2.0 * a["pixels"] * a["c"] * 6,
     # MetaKernel stem: pixels = N H W, the 9x-grid tensors hold 9 C values per pixel
-    "rv_meta_modulate": lambda a: 2.0 * _v(a[5]) * _v(a[6]) * _v(a[7]) * _v(a[8]) * 19,
-    "rv_meta_modulate_bwd_sums": lambda a: 2.0 * _v(a[8]) * _v(a[9]) * _v(a[10]) * _v(a[11]) * 20,
-    "rv_meta_modulate_bwd_apply": lambda a: 2.0 * _v(a[9]) * _v(a[10]) * _v(a[11]) * _v(a[12]) * 28,
-    "rv_pos_forward": lambda a: float(_v(a[3])) * (16 + 4.0 * _v(a[9])),
-    "rv_pos_backward_sums": lambda a: float(_v(a[0])) * (16 + 2.0 * _v(a[1])),
+    "rv_meta_modulate": lambda a: 2.0 * a["N"] * a["H"] * a["W"] * a["C"] * 19,
+    "rv_meta_modulate_bwd_sums": lambda a: 2.0 * a["N"] * a["H"] * a["W"] * a["C"] * 20,
+    "rv_meta_modulate_bwd_apply": lambda a: 2.0 * a["N"] * a["H"] * a["W"] * a["C"] * 28,
+    "rv_pos_forward": lambda a: float(a["pixels"]) * (16 + 4.0 * a["c"]),
+    "rv_pos_backward_sums": lambda a: float(a["pixels"]) * (16 + 2.0 * a["c"]),
     # final conv of a tower fused with the BatchNorm backward in front of it: y (+ the 32-channel dY) in; _apply also writes dy
-    "rv_head_final_bwd_sums": lambda a: 2.0 * _v(a[0]) * (_v(a[1]) + 32),
-    "rv_head_final_bwd_apply": lambda a: 2.0 * _v(a[0]) * (2 * _v(a[1]) + 32),
+    "rv_head_final_bwd_sums": lambda a: 2.0 * a["pixels"] * (a["c"] + 32),
+    "rv_head_final_bwd_apply": lambda a: 2.0 * a["pixels"] * (2 * a["c"] + 32),
 }
 HBM_HOOK = None  # callable(name, algorithmic bytes, launch) or None: set by bench.py around its HBM-group measurement
 
@@ -254,7 +287,7 @@ def call(name: str, *args) -> None:
     ``RV3D_DEBUG_SYNC=1`` prints every call and synchronises after it (locates a faulting launch).
     """
     if HBM_HOOK is not None and name in HBM_BYTES:
-        hook, nbytes = HBM_HOOK, HBM_BYTES[name](args)
+        hook, nbytes = HBM_HOOK, HBM_BYTES[name](dict(zip((p for _, p in prototypes()[name][1]), args)))
         return hook(name, nbytes, lambda: _call(name, *args))
     return _call(name, *args)
 
@@ -278,7 +311,7 @@ def tap_launch_info(geom: TapGeom, shape: TapShape, scatter: bool):
     """``rv_tap_launch_info``: (kernel generation, variant, grid.x, grid.y) of the launch the library plans for this tap op, or ``None``
     when it rejects the shape (``rv_last_error`` says why).  Launches nothing."""
     info = (ctypes.c_int32 * 4)()
-    if load().rv_tap_launch_info(ctypes.byref(geom), ctypes.byref(shape), 1 if scatter else 0, info) != 0:
+    if load().rv_tap_launch_info(geom, shape, 1 if scatter else 0, info) != 0:
         return None
     return tuple(info)
 
@@ -290,17 +323,14 @@ def ew_pass_info(pass_id: int, pixels_or_rows: int, c: int, ld=None, has_out: bo
     raises ``RvError`` on a shape the library rejects."""
     info = (ctypes.c_int32 * 4)()
     lds = (ctypes.c_int32 * 5)(*(list(ld) + [0] * (5 - len(ld)))) if ld is not None else None
-    if load().rv_ew_pass_info(i32(pass_id), i64(pixels_or_rows), i32(c), lds, i32(1 if has_out else 0), i32(1 if has_dres else 0),
-                              i32(flags), info) != 0:
+    if load().rv_ew_pass_info(pass_id, pixels_or_rows, c, lds, 1 if has_out else 0, 1 if has_dres else 0, flags, info) != 0:
         raise RvError(f"rv_ew_pass_info failed: {load().rv_last_error().decode()}")
     return tuple(info)
 
 
-def ptr(t) -> ctypes.c_void_p:
-    """Device (or host) pointer of a torch tensor / None."""
-    if t is None:
-        return ctypes.c_void_p(0)
-    return ctypes.c_void_p(t.data_ptr())
+def ptr(t) -> Optional[ctypes.c_void_p]:
+    """Device (or host) pointer of a torch tensor; ``None`` (NULL) for ``None``, which is what ``HBM_BYTES`` tests."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
 def stream_ptr() -> ctypes.c_void_p:
@@ -309,6 +339,8 @@ def stream_ptr() -> ctypes.c_void_p:
     return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# the scalar types by their short names, for callers that build a ctypes array or an out-parameter (`f32 * 5`, a by-reference count);
+# no argument needs them: load() types every parameter
 i32 = ctypes.c_int32
 i64 = ctypes.c_int64
 f32 = ctypes.c_float

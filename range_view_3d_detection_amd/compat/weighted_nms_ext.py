@@ -46,9 +46,9 @@ def wnms_gpu(boxes: Tensor, data2merge_score: Tensor, output: Tensor, keep: Tens
         return 0
     with torch.cuda.device(boxes.device):
         keep_dev = torch.empty(n, dtype=torch.int64, device=boxes.device)
-        ws = torch.empty(L.load().rv_wnms_workspace_bytes(L.i64(n)), dtype=torch.uint8, device=boxes.device)
+        ws = torch.empty(L.load().rv_wnms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
         num_out = ctypes.c_int64(0)
-        L.call("rv_wnms", L.ptr(boxes), L.ptr(data2merge_score), L.i64(n), L.i32(d), L.f32(nms_thresh), L.f32(merge_thresh),
+        L.call("rv_wnms", L.ptr(boxes), L.ptr(data2merge_score), n, d, nms_thresh, merge_thresh,
                L.ptr(output), L.ptr(keep_dev), L.ptr(count), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
         k = int(num_out.value)
         keep[:k].copy_(keep_dev[:k])  # device -> host, synchronous

@@ -62,7 +62,7 @@ class RoiAtlas:
             offset += a.size
         raster = np.concatenate(flat) if flat else np.zeros(0, np.uint8)
         if len(log_ids):
-            L.call("rv_roi_atlas_check", ctypes.c_void_p(records.ctypes.data), L.i32(len(log_ids)), L.i64(raster.size))
+            L.call("rv_roi_atlas_check", ctypes.c_void_p(records.ctypes.data), len(log_ids), raster.size)
         return cls(log_ids, torch.from_numpy(raster), torch.from_numpy(records.view(np.uint8).copy()), records)
 
     @property
@@ -135,8 +135,8 @@ def roi_points(xyz: Tensor, sweep_offsets, layer_index, city_SE3_ego, atlas: Roi
     out = torch.empty(pts.shape[0], dtype=torch.uint8, device=dev)
     count = _stray_counter(stray, dev)
     with torch.cuda.device(dev):
-        L.call("rv_roi_points", L.ptr(pts), L.i32(1 if pts.dtype == torch.float64 else 0), L.i64(pts.shape[0]), L.ptr(off), L.i32(layer.shape[0]),
-               L.ptr(layer), L.ptr(pose), L.ptr(atlas.raster), L.i64(atlas.raster.numel()), L.ptr(atlas.layers), L.i32(atlas.n_layers), L.ptr(out),
+        L.call("rv_roi_points", L.ptr(pts), 1 if pts.dtype == torch.float64 else 0, pts.shape[0], L.ptr(off), layer.shape[0],
+               L.ptr(layer), L.ptr(pose), L.ptr(atlas.raster), atlas.raster.numel(), L.ptr(atlas.layers), atlas.n_layers, L.ptr(out),
                L.ptr(count), L.stream_ptr())
     if stray is None:
         _raise_on_stray(count, "points")
@@ -156,8 +156,8 @@ def roi_boxes(boxes: Tensor, batch_index: Tensor, layer_index, city_SE3_ego, atl
     out = torch.empty(rows.shape[0], dtype=torch.uint8, device=dev)
     count = _stray_counter(stray, dev)
     with torch.cuda.device(dev):
-        L.call("rv_roi_boxes", L.ptr(rows), L.ptr(bidx), L.i64(rows.shape[0]), L.i32(layer.shape[0]), L.ptr(layer), L.ptr(pose), L.ptr(atlas.raster),
-               L.i64(atlas.raster.numel()), L.ptr(atlas.layers), L.i32(atlas.n_layers), L.ptr(out), L.ptr(count), L.stream_ptr())
+        L.call("rv_roi_boxes", L.ptr(rows), L.ptr(bidx), rows.shape[0], layer.shape[0], L.ptr(layer), L.ptr(pose), L.ptr(atlas.raster),
+               atlas.raster.numel(), L.ptr(atlas.layers), atlas.n_layers, L.ptr(out), L.ptr(count), L.stream_ptr())
     if stray is None:
         _raise_on_stray(count, "boxes")
     return out
@@ -178,11 +178,11 @@ def rasterize_polygons(vertices: Tensor, polygon_offsets: Tensor, s: float, tx: 
     drivable = torch.empty((height, width), dtype=torch.uint8, device=dev)
     roi = torch.empty((height, width), dtype=torch.uint8, device=dev)
     n_poly = off.shape[0] - 1
-    ws_bytes = L.load().rv_roi_rasterize_workspace_bytes(L.i32(n_poly), L.i32(height), L.i32(width))
+    ws_bytes = L.load().rv_roi_rasterize_workspace_bytes(n_poly, height, width)
     ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        L.call("rv_roi_rasterize", L.ptr(verts), L.ptr(off), L.i64(verts.shape[0]), L.i32(n_poly), L.f64(s), L.f64(tx), L.f64(ty), L.i32(height),
-               L.i32(width), L.f64(radius_px), L.ptr(ws), L.ptr(drivable), L.ptr(roi), L.stream_ptr())
+        L.call("rv_roi_rasterize", L.ptr(verts), L.ptr(off), verts.shape[0], n_poly, s, tx, ty, height,
+               width, radius_px, L.ptr(ws), L.ptr(drivable), L.ptr(roi), L.stream_ptr())
     return drivable, roi
 
 

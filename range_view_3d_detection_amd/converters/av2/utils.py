@@ -44,8 +44,8 @@ def unmotion_compensate(xyz: Tensor, offset_ns: Tensor, timestamp_ns: int, pose_
     n = xyz.shape[0]
     out = torch.empty_like(xyz)
     kept = torch.empty(n, dtype=torch.uint8, device=dev)
-    L.call("rv_unmotion_compensate", L.ptr(xyz), L.ptr(off), L.i64(n), L.i64(int(timestamp_ns)), L.ptr(pts), L.ptr(pq), L.ptr(pt), L.i32(pts.shape[0]),
-           L.i32(int(hit[0, 0])), L.ptr(out), L.ptr(kept), L.stream_ptr())
+    L.call("rv_unmotion_compensate", L.ptr(xyz), L.ptr(off), n, int(timestamp_ns), L.ptr(pts), L.ptr(pq), L.ptr(pt), pts.shape[0],
+           int(hit[0, 0]), L.ptr(out), L.ptr(kept), L.stream_ptr())
     return out, kept.bool()
 
 
@@ -57,7 +57,7 @@ def correct_laser_numbers(laser_numbers: Tensor, affected: bool, laser_mapping: 
     lm = laser_mapping.to(dev, torch.int32).contiguous()
     rm = row_mapping.to(dev, torch.int32).contiguous()
     out = torch.empty_like(laser)
-    L.call("rv_correct_laser_numbers", L.ptr(laser), L.i64(laser.numel()), L.i32(1 if affected else 0), L.ptr(lm), L.ptr(rm), L.i32(rm.numel()), L.ptr(out),
+    L.call("rv_correct_laser_numbers", L.ptr(laser), laser.numel(), 1 if affected else 0, L.ptr(lm), L.ptr(rm), rm.numel(), L.ptr(out),
            L.stream_ptr())
     return out
 
@@ -73,7 +73,7 @@ def build_range_view(xyz_p: Tensor, kept: Tensor, features: Tensor, laser_number
     q, t = ext_q_wxyz.to(dev).double().contiguous(), ext_t.to(dev).double().contiguous()
     k8 = kept.to(dev, torch.uint8).contiguous()
     cart = torch.empty_like(xyz_p)
-    L.call("rv_se3_inverse_apply", L.ptr(xyz_p), L.i64(n), L.ptr(q), L.ptr(t), L.ptr(k8), L.ptr(cart), L.stream_ptr())
+    L.call("rv_se3_inverse_apply", L.ptr(xyz_p), n, L.ptr(q), L.ptr(t), L.ptr(k8), L.ptr(cart), L.stream_ptr())
     mapping = torch.arange(height, dtype=torch.int32, device=dev)  # utils.py:66: rows were already corrected
     rows, cols, radius = rv.range_view_indices(cart, laser_number.to(dev), mapping, height, width, "converter")
     feats = torch.cat([features.to(dev).double().T, offset_ns.to(dev).double()[None], radius[None]], dim=0).contiguous()

@@ -94,7 +94,7 @@ def range_image_to_sweep(range_image: Tensor, extrinsic, inclination, pixel_pose
     sweep = torch.empty((b, h, w, 6), dtype=torch.float32, device=ri.device)
     num_pts = torch.empty(b, dtype=torch.int64, device=ri.device)
     with torch.cuda.device(ri.device):
-        L.call("rv_waymo_range_image_to_sweep", L.ptr(ri), L.ptr(ext), L.ptr(inc), L.ptr(pp), L.ptr(inv), L.i32(b), L.i32(h), L.i32(w),
+        L.call("rv_waymo_range_image_to_sweep", L.ptr(ri), L.ptr(ext), L.ptr(inc), L.ptr(pp), L.ptr(inv), b, h, w,
                L.ptr(sweep), L.ptr(num_pts), L.stream_ptr())
     return (sweep[0], num_pts[0]) if single else (sweep, num_pts)
 
@@ -143,8 +143,8 @@ def batch_from_range_images(range_image: Tensor, extrinsic, inclination, pixel_p
     mask = torch.empty((b, 1, h, w + 2 * n_pad), dtype=torch.uint8, device=dev)
     num_pts = torch.empty(b, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        L.call("rv_waymo_range_image_to_batch", L.ptr(ri), L.ptr(ext), L.ptr(inc), L.ptr(pp), L.ptr(inv), L.i32(b), L.i32(h), L.i32(w),
-               L.i32(len(names)), feat_src, feat_op, L.i32(n_pad), L.i32(1 if padding_mode == "circular" else 0), L.ptr(features), L.ptr(cart),
+        L.call("rv_waymo_range_image_to_batch", L.ptr(ri), L.ptr(ext), L.ptr(inc), L.ptr(pp), L.ptr(inv), b, h, w,
+               len(names), feat_src, feat_op, n_pad, 1 if padding_mode == "circular" else 0, L.ptr(features), L.ptr(cart),
                L.ptr(mask), L.ptr(num_pts), L.stream_ptr())
     return {"features": features, "cart": cart, "mask": mask.bool(), "num_pts": num_pts}
 
@@ -161,15 +161,15 @@ def labels_to_annotations(labels: Mapping[str, Sequence], timestamp_ns: int, log
     if kind.size and (kind.min() < 0 or kind.max() >= len(LABEL_TYPES)):
         raise L.RvError(f"label types {sorted(set(kind.tolist()) - set(range(len(LABEL_TYPES))))} are not Waymo label types 0 .. 4")
     keep = np.flatnonzero((kind != LABEL_TYPES.index("SIGN")) & (kind != LABEL_TYPES.index("UNKNOWN")))
-    f64 = lambda name: np.asarray(labels[name], dtype=np.float64).reshape(-1)[keep]  # noqa: E731
-    heading = f64("heading")
+    col = lambda name: np.asarray(labels[name], dtype=np.float64).reshape(-1)[keep]  # noqa: E731
+    heading = col("heading")
     n = keep.size
     cols = {"timestamp_ns": pa.array(np.full(n, int(timestamp_ns), dtype=np.int64)),
             "track_uuid": pa.array([str(labels["id"][i]) for i in keep], type=pa.string()),
             "category": pa.array([LABEL_TYPES[int(kind[i])] for i in keep], type=pa.string()),
-            "length_m": pa.array(f64("length")), "width_m": pa.array(f64("width")), "height_m": pa.array(f64("height")),
+            "length_m": pa.array(col("length")), "width_m": pa.array(col("width")), "height_m": pa.array(col("height")),
             "qw": pa.array(np.cos(heading / 2.0)), "qx": pa.array(np.zeros(n)), "qy": pa.array(np.zeros(n)), "qz": pa.array(np.sin(heading / 2.0)),
-            "tx_m": pa.array(f64("center_x")), "ty_m": pa.array(f64("center_y")), "tz_m": pa.array(f64("center_z")),
+            "tx_m": pa.array(col("center_x")), "ty_m": pa.array(col("center_y")), "tz_m": pa.array(col("center_z")),
             "num_interior_pts": pa.array(np.asarray(labels["num_lidar_points_in_box"], dtype=np.int64).reshape(-1)[keep]),
             "difficulty_level": pa.array(np.asarray(labels["detection_difficulty_level"], dtype=np.int64).reshape(-1)[keep])}
     if log_id is not None:

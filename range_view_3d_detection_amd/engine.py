@@ -228,7 +228,7 @@ def _totals_into(partial: Tensor, rows: int, count: int, region: Tensor, local_c
         raise L.RvError("SyncBN: more than 2^24 elements per channel on one rank (the count travels as fp32)")
     n = region.numel() - 1
     if partial.is_cuda:
-        L.call("rv_reduce_rows_count", L.ptr(partial), L.i32(rows), L.i32(n), L.f32(float(count)), L.ptr(region), L.ptr(local_copy), L.stream_ptr())
+        L.call("rv_reduce_rows_count", L.ptr(partial), rows, n, float(count), L.ptr(region), L.ptr(local_copy), L.stream_ptr())
     else:  # the gloo tests of the host logic run this function on CPU tensors
         region[:n] = partial[:rows].double().sum(dim=0).float().view(-1)
         region[n] = float(count)
@@ -497,8 +497,8 @@ class Lazy:
     def materialized(self) -> Act:
         if self.plain is None:
             out = self.raw.like()
-            L.call("rv_ew_combine", L.i64(self.raw.pixels), L.i32(self.raw.cp), self.raw.ptr(), L.i32(self.raw.ld), L.ptr(self.bn.scale),
-                   L.ptr(self.bn.shift), None, L.i32(0), None, None, out.ptr(), L.i32(out.ld), L.i32(L.EW_RELU_A if self.relu else 0),
+            L.call("rv_ew_combine", self.raw.pixels, self.raw.cp, self.raw.ptr(), self.raw.ld, L.ptr(self.bn.scale),
+                   L.ptr(self.bn.shift), None, 0, None, None, out.ptr(), out.ld, L.EW_RELU_A if self.relu else 0,
                    L.stream_ptr())
             self.plain = out
         return self.plain
@@ -589,7 +589,7 @@ def prepack_stale() -> None:
     dev = stale[0].weight.device
     for l in stale:
         if not l._images:
-            n = L.load().rv_packed_weight_bytes(ctypes.byref(l.geom)) // 2
+            n = L.load().rv_packed_weight_bytes(l.geom) // 2
             l._images = {f: torch.empty(n, dtype=torch.bfloat16, device=dev) for f in ("gather", "scatter")}
     folded = [l for l in stale if l._fold_image is not None]  # (layers whose folded image has been used at least once)
     key = tuple((id(l), l.weight.data_ptr(), l._images["gather"].data_ptr(), l._images["scatter"].data_ptr(),
@@ -600,14 +600,14 @@ def prepack_stale() -> None:
         eb = L.load().rv_pack_batch_entry_bytes()
         host = (ctypes.c_uint8 * (eb * n_entries))()
         for i, l in enumerate(stale):
-            L.call("rv_pack_batch_fill", ctypes.byref(l.geom), L.ptr(l.weight), L.ptr(l._images["gather"]), L.ptr(l._images["scatter"]),
+            L.call("rv_pack_batch_fill", l.geom, L.ptr(l.weight), L.ptr(l._images["gather"]), L.ptr(l._images["scatter"]),
                    ctypes.byref(host, 2 * eb * i))
         for i, l in enumerate(folded):
-            L.call("rv_pack_batch_fill_folded", ctypes.byref(l.geom), L.ptr(l.weight), L.ptr(l._fold_image), ctypes.byref(host, eb * (2 * len(stale) + i)))
+            L.call("rv_pack_batch_fill_folded", l.geom, L.ptr(l.weight), L.ptr(l._fold_image), ctypes.byref(host, eb * (2 * len(stale) + i)))
         _PACK_TABLES.clear()  # one live table (a second model in the process rebuilds it: cheap)
         table = torch.frombuffer(host, dtype=torch.uint8).clone().to(dev)
         _PACK_TABLES[key] = table
-    L.call("rv_pack_batch", L.ptr(table), L.i32(n_entries), L.stream_ptr())
+    L.call("rv_pack_batch", L.ptr(table), n_entries, L.stream_ptr())
     for l in stale:
         l._packed = dict(l._images)
         l._version = (l.weight._version, l.weight.data_ptr())
@@ -680,7 +680,7 @@ class TapLayer:
             return None
         if self._fold_geom is None:
             gf = L.TapGeom()
-            L.call("rv_fold_geom", ctypes.byref(self.geom), ctypes.byref(gf))
+            L.call("rv_fold_geom", self.geom, gf)
             self._fold_geom = gf
         return self._fold_geom
 
@@ -690,18 +690,18 @@ class TapLayer:
             ver = (self.weight._version, self.weight.data_ptr())
             hit = self.__dict__.get("_fold_f16")
             if hit is None or hit[0] != ver:
-                n = L.load().rv_packed_weight_bytes(ctypes.byref(self.fold_geom())) // 2
+                n = L.load().rv_packed_weight_bytes(self.fold_geom()) // 2
                 img = torch.empty(n, dtype=L.act_dtype(), device=self.weight.device)
-                L.call("rv_pack_weight_folded", ctypes.byref(self.geom), L.ptr(self.weight.detach().contiguous().float()), L.ptr(img), L.stream_ptr())
+                L.call("rv_pack_weight_folded", self.geom, L.ptr(self.weight.detach().contiguous().float()), L.ptr(img), L.stream_ptr())
                 self.__dict__["_fold_f16"] = hit = (ver, img)
             return hit[1]
         ver = (self.weight._version, self.weight.data_ptr())
         if ver != self._fold_version or self._fold_image is None:
             gf = self.fold_geom()
-            n = L.load().rv_packed_weight_bytes(ctypes.byref(gf)) // 2
+            n = L.load().rv_packed_weight_bytes(gf) // 2
             if self._fold_image is None:
                 self._fold_image = torch.empty(n, dtype=torch.bfloat16, device=self.weight.device)
-            L.call("rv_pack_weight_folded", ctypes.byref(self.geom), L.ptr(self.weight.detach().contiguous().float()), L.ptr(self._fold_image), L.stream_ptr())
+            L.call("rv_pack_weight_folded", self.geom, L.ptr(self.weight.detach().contiguous().float()), L.ptr(self._fold_image), L.stream_ptr())
             self._fold_version = ver
         return self._fold_image
 
@@ -719,12 +719,12 @@ class TapLayer:
             shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
             w = self._torch_weight(out_scale=scale.float())
             geom = self.fold_geom() if form == "folded" else self.geom
-            nbytes = L.load().rv_packed_weight_bytes(ctypes.byref(geom))
+            nbytes = L.load().rv_packed_weight_bytes(geom)
             img = torch.empty(nbytes // 2, dtype=L.act_dtype(), device=self.weight.device)
             if form == "folded":
-                L.call("rv_pack_weight_folded", ctypes.byref(self.geom), L.ptr(w.contiguous()), L.ptr(img), L.stream_ptr())
+                L.call("rv_pack_weight_folded", self.geom, L.ptr(w.contiguous()), L.ptr(img), L.stream_ptr())
             else:
-                L.call("rv_pack_weight", ctypes.byref(self.geom), L.ptr(w), L.ptr(img if form == "gather" else None),
+                L.call("rv_pack_weight", self.geom, L.ptr(w), L.ptr(img if form == "gather" else None),
                        L.ptr(img if form == "scatter" else None), L.stream_ptr())
             bias = torch.zeros(cp, dtype=torch.float32, device=self.weight.device)
             bias[:c] = shift.float()
@@ -757,19 +757,19 @@ class TapLayer:
         if L.operand_tag() != "bf16":  # fp16 images (inference under autocast(float16)): their own cache entries, packed by that build
             key = form + ":" + L.operand_tag()
             if key not in self._packed:
-                nbytes = L.load().rv_packed_weight_bytes(ctypes.byref(self.geom))
+                nbytes = L.load().rv_packed_weight_bytes(self.geom)
                 buf = torch.empty(nbytes // 2, dtype=L.act_dtype(), device=self.weight.device)
-                L.call("rv_pack_weight", ctypes.byref(self.geom), L.ptr(self._torch_weight()), L.ptr(buf if form == "gather" else None),
+                L.call("rv_pack_weight", self.geom, L.ptr(self._torch_weight()), L.ptr(buf if form == "gather" else None),
                        L.ptr(buf if form == "scatter" else None), L.stream_ptr())
                 self._packed[key] = buf
             return self._packed[key]
         if form not in self._packed:
-            nbytes = L.load().rv_packed_weight_bytes(ctypes.byref(self.geom))
+            nbytes = L.load().rv_packed_weight_bytes(self.geom)
             w = self._torch_weight()
             # a training step needs both images (forward in one form, backward-data in the other): one launch writes both
             forms = ("gather", "scatter") if (torch.is_grad_enabled() and self.weight.requires_grad and "gather" not in self._packed and "scatter" not in self._packed) else (form,)
             bufs = {f: torch.empty(nbytes // 2, dtype=torch.bfloat16, device=self.weight.device) for f in forms}
-            L.call("rv_pack_weight", ctypes.byref(self.geom), L.ptr(w), L.ptr(bufs.get("gather")), L.ptr(bufs.get("scatter")), L.stream_ptr())
+            L.call("rv_pack_weight", self.geom, L.ptr(w), L.ptr(bufs.get("gather")), L.ptr(bufs.get("scatter")), L.stream_ptr())
             self._packed.update(bufs)
         return self._packed[form]
 
@@ -868,8 +868,8 @@ class Tape:
             self._masked_into(dout, mask, res[0], res[1])
 
     def _masked_into(self, dout: Act, mask: Optional[Act], dst: Act, accumulate: bool) -> None:
-        L.call("rv_ew_mask_grad", L.i64(dout.pixels), L.i32(dout.cp), dout.ptr(), L.i32(dout.ld), mask.ptr() if mask is not None else None,
-               L.i32(mask.ld if mask is not None else 0), dst.ptr(), L.i32(dst.ld), L.i32(1 if accumulate else 0), L.stream_ptr())
+        L.call("rv_ew_mask_grad", dout.pixels, dout.cp, dout.ptr(), dout.ld, mask.ptr() if mask is not None else None,
+               mask.ld if mask is not None else 0, dst.ptr(), dst.ld, 1 if accumulate else 0, L.stream_ptr())
 
     def _flatten_lazy_grad(self, key: int) -> None:
         dout, mask, res = (self.lazy_in[key] + (None,))[:3]
@@ -990,7 +990,7 @@ class ConvOp(Op):
         self.partial = None
         self.rows = 0
         if stats:
-            self.rows = L.load().rv_tap_stats_rows(ctypes.byref(lg), ctypes.byref(lshape), 1 if form == "scatter" else 0)
+            self.rows = L.load().rv_tap_stats_rows(lg, lshape, 1 if form == "scatter" else 0)
             if self.rows < 0:
                 raise L.RvError("rv_tap_stats_rows: " + L.load().rv_last_error().decode())
             self.partial = torch.empty((self.rows + L.STATS_SCRATCH_ROWS, 2, pad32(layer.c_out)), dtype=torch.float32,
@@ -999,12 +999,12 @@ class ConvOp(Op):
             wp, bias_p = layer.packed_eval("folded" if isinstance(wp, str) else form, eval_bn)
         elif wp is None:
             wp = layer.packed(form)
-        call = lambda: L.call("rv_tap_" + form, ctypes.byref(lg), ctypes.byref(lshape), src.ptr(), L.ptr(sc), L.ptr(sh),
+        call = lambda: L.call("rv_tap_" + form, lg, lshape, src.ptr(), L.ptr(sc), L.ptr(sh),
                               L.ptr(wp), L.ptr(bias_p), dst_ptr, L.ptr(self.partial), L.stream_ptr())
         if residual is not None:
             assert sc is None and flags & (L.IN_AFFINE | L.IN_RELU) == 0 and residual.cp == self.out.cp and residual.pixels == self.out.pixels
-            call = lambda: L.call("rv_tap_residual", ctypes.byref(lg), ctypes.byref(lshape), L.i32(1 if form == "scatter" else 0), src.ptr(),
-                                  L.ptr(wp), L.ptr(bias_p), residual.ptr(), L.i32(residual.ld), dst_ptr, L.stream_ptr())
+            call = lambda: L.call("rv_tap_residual", lg, lshape, 1 if form == "scatter" else 0, src.ptr(),
+                                  L.ptr(wp), L.ptr(bias_p), residual.ptr(), residual.ld, dst_ptr, L.stream_ptr())
         if precomputed is not None:
             assert out is not None and not out_f32 and bias is None
             self.partial, self.rows = precomputed
@@ -1050,8 +1050,8 @@ class BnOp(Op):
             if self.sync_world > 1:  # SyncBN: (sum, sum of squares, count) in one all-reduce; the kernel reads the global count
                 conv.partial = reduced if reduced is not None else allreduce_partial_rows(conv.partial, conv.rows, conv.count)
                 conv.rows, count_arg = 1, -1
-            L.call("rv_bn_finalize", L.ptr(conv.partial), L.i32(conv.rows), L.i32(cp), L.i64(count_arg), L.ptr(gamma),
-                   L.ptr(beta), L.f32(bn.eps), L.f32(bn.momentum if bn.momentum is not None else 0.1), L.ptr(rm),
+            L.call("rv_bn_finalize", L.ptr(conv.partial), conv.rows, cp, count_arg, L.ptr(gamma),
+                   L.ptr(beta), bn.eps, bn.momentum if bn.momentum is not None else 0.1, L.ptr(rm),
                    L.ptr(rv), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.stream_ptr())
             if bn.running_mean.shape[0] != cp:  # padded copies: write the logical channels back
                 bn.running_mean.copy_(rm[:c])
@@ -1061,7 +1061,7 @@ class BnOp(Op):
             self.state = BnState(bn, scale, shift, mean, invstd, conv.count)
         else:
             rm, rv = _padded(bn.running_mean, cp), _padded(bn.running_var, cp, 1.0)
-            L.call("rv_bn_fold_eval", L.i32(cp), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.f32(bn.eps),
+            L.call("rv_bn_fold_eval", cp, L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), bn.eps,
                    L.ptr(scale), L.ptr(shift), L.stream_ptr())
             self.state = BnState(bn, scale, shift)
         self.lazy = Lazy(conv.out, self.state, relu)
@@ -1113,9 +1113,9 @@ class SmallKOp(Op):
         if t.training:
             self.mean = torch.empty(cp, dtype=torch.float32, device=dev)
             self.invstd = torch.empty(cp, dtype=torch.float32, device=dev)
-            ws = torch.empty(L.load().rv_smallk_forward_workspace_bytes(L.i32(cin)), dtype=torch.uint8, device=dev)
+            ws = torch.empty(L.load().rv_smallk_forward_workspace_bytes(cin), dtype=torch.uint8, device=dev)
             moments = torch.empty(73, dtype=torch.float64, device=dev)
-            L.call("rv_smallk_moments", x.ptr(), L.i32(x.ld), L.i64(x.pixels), L.i32(cin), L.ptr(moments), L.ptr(ws), L.stream_ptr())
+            L.call("rv_smallk_moments", x.ptr(), x.ld, x.pixels, cin, L.ptr(moments), L.ptr(ws), L.stream_ptr())
             self.sync_world = bn_sync_world(bn, True)
             if self.sync_world > 1:
                 # SyncBN: the moments are sums over pixels -> all-reduce them together with this rank's pixel count (the slot
@@ -1125,21 +1125,21 @@ class SmallKOp(Op):
                 COLLECTIVES.add(moments)
                 all_reduce_(moments)
                 self.count = -1
-            L.call("rv_smallk_forward", x.ptr(), L.i32(x.ld), L.i64(x.pixels), L.i32(cin), L.ptr(wp), L.i32(pad32(cin)), L.i32(cp),
-                   L.ptr(moments), L.i64(self.count), L.ptr(self.gamma_p), L.ptr(self.beta_p), L.f32(bn.eps),
-                   L.f32(bn.momentum if bn.momentum is not None else 0.1), L.ptr(rm), L.ptr(rv), L.ptr(scale), L.ptr(shift),
-                   L.ptr(self.mean), L.ptr(self.invstd), L.i32(1), self.out.ptr() if apply else None, L.i32(self.out.ld), L.stream_ptr())
+            L.call("rv_smallk_forward", x.ptr(), x.ld, x.pixels, cin, L.ptr(wp), pad32(cin), cp,
+                   L.ptr(moments), self.count, L.ptr(self.gamma_p), L.ptr(self.beta_p), bn.eps,
+                   bn.momentum if bn.momentum is not None else 0.1, L.ptr(rm), L.ptr(rv), L.ptr(scale), L.ptr(shift),
+                   L.ptr(self.mean), L.ptr(self.invstd), 1, self.out.ptr() if apply else None, self.out.ld, L.stream_ptr())
             if bn.running_mean.shape[0] != cp:
                 bn.running_mean.copy_(rm[:c])
                 bn.running_var.copy_(rv[:c])
             t.bn_counters.append(bn.num_batches_tracked)
         else:
-            L.call("rv_bn_fold_eval", L.i32(cp), L.ptr(self.gamma_p), L.ptr(self.beta_p), L.ptr(rm), L.ptr(rv), L.f32(bn.eps),
+            L.call("rv_bn_fold_eval", cp, L.ptr(self.gamma_p), L.ptr(self.beta_p), L.ptr(rm), L.ptr(rv), bn.eps,
                    L.ptr(scale), L.ptr(shift), L.stream_ptr())
             if apply:
-                L.call("rv_smallk_forward", x.ptr(), L.i32(x.ld), L.i64(x.pixels), L.i32(cin), L.ptr(wp), L.i32(pad32(cin)), L.i32(cp),
-                       None, L.i64(self.count), None, None, L.f32(bn.eps), L.f32(0.1), None, None, L.ptr(scale), L.ptr(shift), None, None,
-                       L.i32(1), self.out.ptr(), L.i32(self.out.ld), L.stream_ptr())
+                L.call("rv_smallk_forward", x.ptr(), x.ld, x.pixels, cin, L.ptr(wp), pad32(cin), cp,
+                       None, self.count, None, None, bn.eps, 0.1, None, None, L.ptr(scale), L.ptr(shift), None, None,
+                       1, self.out.ptr(), self.out.ld, L.stream_ptr())
         t.ops.append(self)
 
     def backward(self, t: Tape) -> None:
@@ -1228,10 +1228,10 @@ def pos_pair(t: Tape, l0: TapLayer, bn0: nn.BatchNorm2d, l1: TapLayer, bn1: nn.B
     sk = SmallKOp(t, l0, x, bn0, apply=False)
     h1 = sk.out
     y2 = Act.empty(x.N, x.H, x.W, l1.c_out, t.device)
-    rows = L.load().rv_pos_forward_rows(L.i64(x.pixels))
+    rows = L.load().rv_pos_forward_rows(x.pixels)
     partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, y2.cp), dtype=torch.float32, device=t.device) if t.training else None
-    call = lambda: L.call("rv_pos_forward", x.ptr(), L.i32(x.ld), L.i32(l0.c_in), L.i64(x.pixels), L.ptr(l0.packed("gather")), L.i32(pad32(l0.c_in)),
-                          L.ptr(sk.scale), L.ptr(sk.shift), L.ptr(l1.packed("gather")), L.i32(y2.cp), h1.ptr(), y2.ptr(), L.ptr(partial), L.stream_ptr())
+    call = lambda: L.call("rv_pos_forward", x.ptr(), x.ld, l0.c_in, x.pixels, L.ptr(l0.packed("gather")), pad32(l0.c_in),
+                          L.ptr(sk.scale), L.ptr(sk.shift), L.ptr(l1.packed("gather")), y2.cp, h1.ptr(), y2.ptr(), L.ptr(partial), L.stream_ptr())
     if PROFILE is not None:
         _launch("pos_fwd_kernel", 2.0 * x.pixels * l1.c_in * l1.c_out, call)
     else:
@@ -1248,8 +1248,8 @@ def _eval_scale_shift(bn: nn.BatchNorm2d, cp: int, dev) -> Tuple[Tensor, Tensor]
     """Eval-mode BatchNorm as (scale, shift) over the padded channels."""
     scale = torch.empty(cp, dtype=torch.float32, device=dev)
     shift = torch.empty(cp, dtype=torch.float32, device=dev)
-    L.call("rv_bn_fold_eval", L.i32(cp), L.ptr(_padded(bn.weight, cp)), L.ptr(_padded(bn.bias, cp)), L.ptr(_padded(bn.running_mean, cp)),
-           L.ptr(_padded(bn.running_var, cp, 1.0)), L.f32(bn.eps), L.ptr(scale), L.ptr(shift), L.stream_ptr())
+    L.call("rv_bn_fold_eval", cp, L.ptr(_padded(bn.weight, cp)), L.ptr(_padded(bn.bias, cp)), L.ptr(_padded(bn.running_mean, cp)),
+           L.ptr(_padded(bn.running_var, cp, 1.0)), bn.eps, L.ptr(scale), L.ptr(shift), L.stream_ptr())
     return scale, shift
 
 
@@ -1269,9 +1269,9 @@ class PosModulateOp(Op):
         s1, t1 = _eval_scale_shift(bn0, cp, t.device)
         s2, t2 = _eval_scale_shift(bn1, cp, t.device)
         self.out = Act.empty(feat.N, feat.H, feat.W, 9 * cp, t.device)
-        call = lambda: L.call("rv_pos_modulate_forward", x.ptr(), L.i32(x.ld), L.i32(l0.c_in), L.ptr(l0.packed("gather")), L.i32(pad32(l0.c_in)),
-                              L.ptr(s1), L.ptr(t1), L.ptr(l1.packed("gather")), L.i32(cp), L.ptr(s2), L.ptr(t2), feat.ptr(), L.i32(feat.ld),
-                              L.i32(feat.N), L.i32(feat.H), L.i32(feat.W), self.out.ptr(), L.stream_ptr())
+        call = lambda: L.call("rv_pos_modulate_forward", x.ptr(), x.ld, l0.c_in, L.ptr(l0.packed("gather")), pad32(l0.c_in),
+                              L.ptr(s1), L.ptr(t1), L.ptr(l1.packed("gather")), cp, L.ptr(s2), L.ptr(t2), feat.ptr(), feat.ld,
+                              feat.N, feat.H, feat.W, self.out.ptr(), L.stream_ptr())
         if PROFILE is not None:
             _launch("pos_fwd_kernel<eval>", 2.0 * x.pixels * l1.c_in * l1.c_out, call)
         else:
@@ -1303,9 +1303,9 @@ class CombineOp(Op):
             flags |= L.EW_RELU_B if fb & L.IN_RELU else 0
             assert rb.cp == ra.cp and rb.pixels == ra.pixels
         self.out = out if out is not None else ra.like()
-        L.call("rv_ew_combine", L.i64(ra.pixels), L.i32(ra.cp), ra.ptr(), L.i32(ra.ld), L.ptr(sa), L.ptr(ta),
-               rb.ptr() if rb is not None else None, L.i32(rb.ld if rb is not None else 0), L.ptr(sb), L.ptr(tb),
-               self.out.ptr(), L.i32(self.out.ld), L.i32(flags), L.stream_ptr())
+        L.call("rv_ew_combine", ra.pixels, ra.cp, ra.ptr(), ra.ld, L.ptr(sa), L.ptr(ta),
+               rb.ptr() if rb is not None else None, rb.ld if rb is not None else 0, L.ptr(sb), L.ptr(tb),
+               self.out.ptr(), self.out.ld, flags, L.stream_ptr())
         t.producers[id(self.out)] = self
         t.ops.append(self)
 
@@ -1325,7 +1325,7 @@ class MetaRelativeOp(Op):
         n, _, h, w = cart.shape
         cart = cart.contiguous().float()
         self.out = Act.empty(n, h, w * 9, 3, t.device)
-        L.call("rv_meta_relative", L.ptr(cart), L.i32(n), L.i32(h), L.i32(w), self.out.ptr(), L.stream_ptr())
+        L.call("rv_meta_relative", L.ptr(cart), n, h, w, self.out.ptr(), L.stream_ptr())
         t.ops.append(self)
 
     def backward(self, t: Tape) -> None:
@@ -1340,8 +1340,8 @@ class MetaModulateOp(Op):
         n, h, w, cp = feat.N, feat.H, feat.W, feat.cp
         assert pos.raw.W == 9 * w and pos.raw.cp == cp and pos.raw.ld == cp
         self.out = Act.empty(n, h, w, 9 * cp, t.device)
-        L.call("rv_meta_modulate", pos.raw.ptr(), L.ptr(pos.bn.scale), L.ptr(pos.bn.shift), feat.ptr(), L.i32(feat.ld),
-               L.i32(n), L.i32(h), L.i32(w), L.i32(cp), self.out.ptr(), L.stream_ptr())
+        L.call("rv_meta_modulate", pos.raw.ptr(), L.ptr(pos.bn.scale), L.ptr(pos.bn.shift), feat.ptr(), feat.ld,
+               n, h, w, cp, self.out.ptr(), L.stream_ptr())
         t.ops.append(self)
 
     def backward(self, t: Tape) -> None:

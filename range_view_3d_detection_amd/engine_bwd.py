@@ -112,18 +112,18 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
             wp = layer.packed(bwd)
         else:
             wp = layer.packed(bwd)
-        call = lambda: L.call("rv_tap_" + bwd, ctypes.byref(bg), ctypes.byref(bshape), dout.ptr(), None, None, L.ptr(wp), None,
+        call = lambda: L.call("rv_tap_" + bwd, bg, bshape, dout.ptr(), None, None, L.ptr(wp), None,
                               dst.ptr(), None, L.stream_ptr())
         if E.BNB_FUSE and bg is g and isinstance(op.x, Lazy) and not accumulate and op.x.bn.mean is not None:
             # first (often only) consumer of relu(bn(y)): this launch can form that BatchNorm's backward sums on the way out
-            rows = L.load().rv_tap_bnb_rows(ctypes.byref(g), ctypes.byref(shape), L.i32(1 if bwd == "scatter" else 0))
+            rows = L.load().rv_tap_bnb_rows(g, shape, 1 if bwd == "scatter" else 0)
             if rows > 0:
                 lz, st = op.x, op.x.bn
                 partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, dst.cp), dtype=torch.float32, device=t.device)
-                epi = L.BnbEpilogue(lz.raw.ptr().value, lz.raw.ld, L.BNB_RELU_Z if lz.relu else 0, L.ptr(st.scale).value, L.ptr(st.shift).value,
-                                    L.ptr(st.mean).value, L.ptr(st.invstd).value, L.ptr(partial).value)
-                call = lambda: L.call("rv_tap_data_grad_bnb", ctypes.byref(g), ctypes.byref(shape), L.i32(1 if bwd == "scatter" else 0), dout.ptr(),
-                                      L.ptr(wp), dst.ptr(), ctypes.byref(epi), L.stream_ptr())
+                epi = L.BnbEpilogue(lz.raw.ptr(), lz.raw.ld, L.BNB_RELU_Z if lz.relu else 0, L.ptr(st.scale), L.ptr(st.shift),
+                                    L.ptr(st.mean), L.ptr(st.invstd), L.ptr(partial))
+                call = lambda: L.call("rv_tap_data_grad_bnb", g, shape, 1 if bwd == "scatter" else 0, dout.ptr(),
+                                      L.ptr(wp), dst.ptr(), epi, L.stream_ptr())
                 t.lazy_sums[id(lz)] = (partial, rows, dst)
         if E.OVERLAP_WGRAD and E.EARLY_WGRAD_FILL > 0:
             # a persistent backward-data launch whose LAST round of tiles fills only part of the chip (1328 tiles on 256 CUs: five full
@@ -160,25 +160,25 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
         wg, wsh, ld_v = gfw, L.TapShape(sp.N, sp.H, sp.Wu, sp.Wu, 0, 0, L.WGRAD_TORCH_LAYOUT), g.stride_w * v.ld
 
     def run_wgrad() -> None:
-        ws_bytes = L.load().rv_tap_wgrad_workspace_bytes(ctypes.byref(wg), ctypes.byref(wsh))
+        ws_bytes = L.load().rv_tap_wgrad_workspace_bytes(wg, wsh)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=t.device)
         grad = torch.empty((wg.cu, wg.cv, wg.kh, wg.kw), dtype=torch.float32, device=t.device)
         wname = "wgrad_kernel(+reduce)"
         if E.PROFILE is not None:
             winfo = (ctypes.c_int32 * 4)()
-            L.call("rv_tap_wgrad_info", ctypes.byref(wg), ctypes.byref(wsh), winfo)
+            L.call("rv_tap_wgrad_info", wg, wsh, winfo)
             wname = ("wgrad_kernel", "wgrad_kernel", "wgrad2_kernel", "wgrad3_kernel")[winfo[0]] + "(+reduce)"
         if os.environ.get("RV3D_PROFILE_SHAPES"):
             wname += f" k{g.kh}x{g.kw}s{g.stride_w} {g.cu}<->{g.cv} {wshape.N}x{wshape.H}x{wshape.Wu}"
         # the split-K reduction (one small launch behind the kernel) writes the torch layout dT[cu][cv][kh][kw] itself
         # (RV_WGRAD_TORCH_LAYOUT): no unpack pass
         E._launch(wname, E.tap_flops(g, wshape),
-                  lambda: L.call("rv_tap_wgrad", ctypes.byref(wg), ctypes.byref(wsh), u.ptr(), L.i32(u.ld), v.ptr(), L.i32(ld_v),
-                                 L.ptr(sc), L.ptr(sh), L.i32(v_affine), L.ptr(grad), L.ptr(ws), L.stream_ptr()),
+                  lambda: L.call("rv_tap_wgrad", wg, wsh, u.ptr(), u.ld, v.ptr(), ld_v,
+                                 L.ptr(sc), L.ptr(sh), v_affine, L.ptr(grad), L.ptr(ws), L.stream_ptr()),
                   E.tap_bytes(g, wshape, wgrad=True))
         if wg is not g:
             folded, grad = grad, torch.empty((g.cu, g.cv, g.kh, g.kw), dtype=torch.float32, device=t.device)
-            L.call("rv_unfold_weight_grad", ctypes.byref(g), L.ptr(folded), L.ptr(grad), L.i32(0), L.stream_ptr())
+            L.call("rv_unfold_weight_grad", g, L.ptr(folded), L.ptr(grad), 0, L.stream_ptr())
         t.add_param_grad(layer.weight, layer.unpermute_grad(grad))
 
     small = E.OVERLAP_MAX_TFLOP is None or E.tap_flops(g, wshape) < 1e12 * E.OVERLAP_MAX_TFLOP
@@ -229,14 +229,14 @@ def _head_final_sums(op: "E.ConvOp", t: Tape, dY: Act) -> None:
     lazy, layer = op.x, op.layer
     st, raw = lazy.bn, lazy.raw
     wp = layer.packed("scatter")
-    rows = L.load().rv_head_final_bwd_rows(L.i64(raw.pixels))
+    rows = L.load().rv_head_final_bwd_rows(raw.pixels)
     partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, raw.cp), dtype=torch.float32, device=t.device)
     dw_partial = torch.empty((rows, 32 * raw.cp), dtype=torch.float32, device=t.device)
-    head = (L.i64(raw.pixels), L.i32(raw.cp), raw.ptr(), L.i32(raw.ld), dY.ptr(), L.i32(dY.ld), L.ptr(wp), L.ptr(st.scale), L.ptr(st.shift),
-            L.ptr(st.mean), L.ptr(st.invstd), L.i32(1))
+    head = (raw.pixels, raw.cp, raw.ptr(), raw.ld, dY.ptr(), dY.ld, L.ptr(wp), L.ptr(st.scale), L.ptr(st.shift),
+            L.ptr(st.mean), L.ptr(st.invstd), 1)
     L.call("rv_head_final_bwd_sums", *head, L.ptr(partial), L.ptr(dw_partial), L.stream_ptr())
     dw = torch.empty((32, raw.cp), dtype=torch.float32, device=t.device)
-    L.call("rv_reduce_rows", L.ptr(dw_partial), L.i32(rows), L.i32(32 * raw.cp), L.ptr(dw), L.stream_ptr())
+    L.call("rv_reduce_rows", L.ptr(dw_partial), rows, 32 * raw.cp, L.ptr(dw), L.stream_ptr())
     g = layer.geom
     t.add_param_grad(layer.weight, dw[: g.cu, : g.cv].reshape(g.cu, g.cv, 1, 1))
     t.head_final[id(lazy)] = (head, partial, rows, dY, wp)
@@ -276,12 +276,12 @@ def _pos_pair_backward(op: "E.ConvOp", t: Tape, dy2: Act) -> None:
     l1 = op.layer
     cp, cin, pixels = sk.out.cp, lay0.c_in, sk.out.pixels
     dev = t.device
-    ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(L.i64(pixels), L.i32(cp), L.i32(cin)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(pixels, cp, cin), dtype=torch.uint8, device=dev)
     sums = torch.empty((2 + 4) * cp, dtype=torch.float64, device=dev)
     moms = torch.empty(4 + 16, dtype=torch.float64, device=dev)
     wp0 = lay0.packed("gather")
-    call = lambda: L.call("rv_pos_backward_sums", L.i64(pixels), L.i32(cp), dy2.ptr(), L.ptr(l1.packed("scatter")), rel.ptr(), L.i32(rel.ld), L.i32(cin),
-                          L.ptr(wp0), L.i32(E.pad32(cin)), L.ptr(sk.scale), L.ptr(sk.shift), L.ptr(sk.mean), L.ptr(sk.invstd), L.ptr(sums),
+    call = lambda: L.call("rv_pos_backward_sums", pixels, cp, dy2.ptr(), L.ptr(l1.packed("scatter")), rel.ptr(), rel.ld, cin,
+                          L.ptr(wp0), E.pad32(cin), L.ptr(sk.scale), L.ptr(sk.shift), L.ptr(sk.mean), L.ptr(sk.invstd), L.ptr(sums),
                           L.ptr(moms), L.ptr(ws), L.stream_ptr())
     if E.PROFILE is not None:
         E._launch("pos_bwd_kernel", 2.0 * pixels * cp * cp, call)
@@ -293,8 +293,8 @@ def _pos_pair_backward(op: "E.ConvOp", t: Tape, dy2: Act) -> None:
     g01 = None
     if sk.sync_world > 1:  # SyncBN: the normalisation needs the GLOBAL (sum g, sum g*xhat); the other sums stay this rank's (as _smallk_grads)
         g01 = _global_s01(sums, cp, pixels)
-    L.call("rv_bn_bwd_smallk_from_sums", L.i32(cp), L.i32(cin), L.ptr(sums), L.ptr(moms), L.ptr(g01), L.ptr(wp0), L.i32(E.pad32(cin)),
-           L.ptr(sk.gamma_p), L.ptr(sk.mean), L.ptr(sk.invstd), L.i64(sk.count), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dw), L.stream_ptr())
+    L.call("rv_bn_bwd_smallk_from_sums", cp, cin, L.ptr(sums), L.ptr(moms), L.ptr(g01), L.ptr(wp0), E.pad32(cin),
+           L.ptr(sk.gamma_p), L.ptr(sk.mean), L.ptr(sk.invstd), sk.count, L.ptr(dgamma), L.ptr(dbeta), L.ptr(dw), L.stream_ptr())
     c = bn0.num_features
     t.add_param_grad(bn0.weight, dgamma[:c])
     t.add_param_grad(bn0.bias, dbeta[:c])
@@ -320,24 +320,24 @@ def _smallk_grads(t: Tape, pixels: int, cp: int, dout: Act, mask: Optional[Act],
     form with the all-reduce of (sum g, sum g*xhat) in between."""
     cin = lay.c_in
     dev = t.device
-    ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(L.i64(pixels), L.i32(cp), L.i32(cin)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(pixels, cp, cin), dtype=torch.uint8, device=dev)
     dgamma = torch.empty(cp, dtype=torch.float32, device=dev)
     dbeta = torch.empty(cp, dtype=torch.float32, device=dev)
     dw = torch.empty((cp, cin), dtype=torch.float32, device=dev)
     wp = lay.packed("gather")
-    head = (L.i64(pixels), L.i32(cp), dout.ptr(), L.i32(dout.ld), mask.ptr() if mask is not None else None,
-            L.i32(mask.ld if mask is not None else 0), y.ptr() if y is not None else None, L.i32(y.ld if y is not None else 0), L.ptr(scale),
-            L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.i32(flags), v.ptr(), L.i32(v.ld), L.i32(cin), L.ptr(wp), L.i32(E.pad32(cin)))
+    head = (pixels, cp, dout.ptr(), dout.ld, mask.ptr() if mask is not None else None,
+            mask.ld if mask is not None else 0, y.ptr() if y is not None else None, y.ld if y is not None else 0, L.ptr(scale),
+            L.ptr(shift), L.ptr(mean), L.ptr(invstd), flags, v.ptr(), v.ld, cin, L.ptr(wp), E.pad32(cin))
     if sync:
         cin_pad = 4 if cin <= 4 else 8
         sums = torch.empty((2 + cin_pad) * cp, dtype=torch.float64, device=dev)
         moms = torch.empty(cin_pad + cin_pad * cin_pad, dtype=torch.float64, device=dev)
         L.call("rv_bn_bwd_smallk_sums", *head, L.ptr(sums), L.ptr(moms), L.ptr(ws), L.stream_ptr())
         g01 = _global_s01(sums, cp, pixels)  # SyncBN: global (sum g, sum g*xhat, pixel count); the other sums stay this rank's
-        L.call("rv_bn_bwd_smallk_from_sums", L.i32(cp), L.i32(cin), L.ptr(sums), L.ptr(moms), L.ptr(g01), L.ptr(wp), L.i32(E.pad32(cin)),
-               L.ptr(gamma_p), L.ptr(stat_mean), L.ptr(stat_invstd), L.i64(-1), L.ptr(dgamma), L.ptr(dbeta), L.ptr(dw), L.stream_ptr())
+        L.call("rv_bn_bwd_smallk_from_sums", cp, cin, L.ptr(sums), L.ptr(moms), L.ptr(g01), L.ptr(wp), E.pad32(cin),
+               L.ptr(gamma_p), L.ptr(stat_mean), L.ptr(stat_invstd), -1, L.ptr(dgamma), L.ptr(dbeta), L.ptr(dw), L.stream_ptr())
     else:
-        L.call("rv_bn_bwd_smallk", *head, L.ptr(gamma_p), L.ptr(stat_mean), L.ptr(stat_invstd), L.i64(count),
+        L.call("rv_bn_bwd_smallk", *head, L.ptr(gamma_p), L.ptr(stat_mean), L.ptr(stat_invstd), count,
                L.ptr(dgamma), L.ptr(dbeta), L.ptr(dw), L.ptr(ws), L.stream_ptr())
     return dgamma, dbeta, dw
 
@@ -389,16 +389,16 @@ def bn_backward_begin(op: "E.BnOp", t: Tape):
         t.add_param_grad(st.module.bias, dbeta[:c])
         t.add_param_grad(lay.weight, lay.unpermute_grad(dw[: lay.c_out].reshape(lay.c_out, cin, 1, 1).contiguous()))
         return None
-    common = (L.i64(pixels), L.i32(cp), dout.ptr(), L.i32(dout.ld), mask.ptr() if mask is not None else None,
-              L.i32(mask.ld if mask is not None else 0), raw.ptr(), L.i32(raw.ld), L.ptr(st.scale), L.ptr(st.shift),
+    common = (pixels, cp, dout.ptr(), dout.ld, mask.ptr() if mask is not None else None,
+              mask.ld if mask is not None else 0, raw.ptr(), raw.ld, L.ptr(st.scale), L.ptr(st.shift),
               L.ptr(st.mean), L.ptr(st.invstd))
     sums = t.lazy_sums.pop(id(lazy), None)
     if sums is not None and sums[2] is dout and ((len(sums) == 3 and mask is None and res is None) or (len(sums) == 4 and mask is not None)):
         partial, rows = sums[0], sums[1]  # formed by the backward-data launch that wrote dout (rv_tap_data_grad_bnb)
     else:
-        rows = L.load().rv_bn_bwd_rows(L.i64(pixels))
+        rows = L.load().rv_bn_bwd_rows(pixels)
         partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, cp), dtype=torch.float32, device=t.device)
-        L.call("rv_bn_bwd_reduce", *common, L.i32(flags), L.ptr(partial), L.stream_ptr())
+        L.call("rv_bn_bwd_reduce", *common, flags, L.ptr(partial), L.stream_ptr())
     return (op, common, partial, rows, pixels, flags, res, (dout, mask))  # (dout / mask referenced until the apply pass has been issued)
 
 
@@ -421,13 +421,13 @@ def bn_backward_finish(recs, t: Tape) -> None:
         dgamma, dbeta, coef = _bn_finalize(op, t, partial, rows, pixels, glob=g, local=loc)
         dy = raw.like()
         if common is None:  # the head-final form: dA recomputed from the final conv's output gradient (bn_backward_begin)
-            L.call("rv_head_final_bwd_apply", *_keep[1], L.ptr(coef), dy.ptr(), L.i32(dy.ld), L.stream_ptr())
+            L.call("rv_head_final_bwd_apply", *_keep[1], L.ptr(coef), dy.ptr(), dy.ld, L.stream_ptr())
         elif res is not None:
             rg, racc = res
-            L.call("rv_bn_bwd_apply", *common, L.ptr(coef), L.i32(flags | (L.BNB_RES_ACCUM if racc else 0)), dy.ptr(), L.i32(dy.ld),
-                   rg.ptr(), L.i32(rg.ld), L.stream_ptr())
+            L.call("rv_bn_bwd_apply", *common, L.ptr(coef), flags | (L.BNB_RES_ACCUM if racc else 0), dy.ptr(), dy.ld,
+                   rg.ptr(), rg.ld, L.stream_ptr())
         else:
-            L.call("rv_bn_bwd_apply", *common, L.ptr(coef), L.i32(flags), dy.ptr(), L.i32(dy.ld), None, L.i32(0), L.stream_ptr())
+            L.call("rv_bn_bwd_apply", *common, L.ptr(coef), flags, dy.ptr(), dy.ld, None, 0, L.stream_ptr())
         t.raw_grad[id(raw)] = dy
         c = st.module.num_features
         t.add_param_grad(st.module.weight, dgamma[:c])
@@ -447,13 +447,13 @@ def _bn_finalize(op: "E.BnOp", t: Tape, partial: Tensor, rows: int, pixels: int,
             local = torch.empty((2, cp), dtype=torch.float32, device=t.device)
             glob = E.allreduce_partial_rows(partial, rows, pixels, local)
             _release_held_wgrads(t)
-        L.call("rv_bn_bwd_finalize", L.ptr(glob), L.i32(1), L.i32(cp), L.i64(-1), L.ptr(op.gamma_p), L.ptr(st.invstd),
-               None, None, L.i32(0), L.ptr(coef), L.stream_ptr())
+        L.call("rv_bn_bwd_finalize", L.ptr(glob), 1, cp, -1, L.ptr(op.gamma_p), L.ptr(st.invstd),
+               None, None, 0, L.ptr(coef), L.stream_ptr())
         return local[1], local[0], coef
     dgamma = torch.empty(cp, dtype=torch.float32, device=t.device)
     dbeta = torch.empty(cp, dtype=torch.float32, device=t.device)
-    L.call("rv_bn_bwd_finalize", L.ptr(partial), L.i32(rows), L.i32(cp), L.i64(st.count), L.ptr(op.gamma_p), L.ptr(st.invstd),
-           L.ptr(dgamma), L.ptr(dbeta), L.i32(0), L.ptr(coef), L.stream_ptr())
+    L.call("rv_bn_bwd_finalize", L.ptr(partial), rows, cp, st.count, L.ptr(op.gamma_p), L.ptr(st.invstd),
+           L.ptr(dgamma), L.ptr(dbeta), 0, L.ptr(coef), L.stream_ptr())
     return dgamma, dbeta, coef
 
 
@@ -465,7 +465,7 @@ def _bn_backward_meta(op: "E.BnOp", t: Tape, meta) -> None:
     dgamma, dbeta, coef = _bn_finalize(op, t, partial, rows, raw.pixels)
     dy = raw.like()
     L.call("rv_meta_modulate_bwd_apply", dgeo.ptr(), raw.ptr(), L.ptr(st.scale), L.ptr(st.shift), L.ptr(st.mean), L.ptr(st.invstd),
-           L.ptr(coef), feat.ptr(), L.i32(feat.ld), L.i32(feat.N), L.i32(feat.H), L.i32(feat.W), L.i32(feat.cp), dy.ptr(), L.stream_ptr())
+           L.ptr(coef), feat.ptr(), feat.ld, feat.N, feat.H, feat.W, feat.cp, dy.ptr(), L.stream_ptr())
     t.raw_grad[id(raw)] = dy
     c = st.module.num_features
     t.add_param_grad(st.module.weight, dgamma[:c])
@@ -488,11 +488,11 @@ def combine_backward(op: "E.CombineOp", t: Tape) -> None:
         # out = relu(bn_a(ya) + bn_b(yb)) (a block with a projection): the sums of BOTH BatchNorm backwards from one pass
         # over (dOut, out, ya, yb); each bn_backward_begin then finds its rows and skips its own reduce pass
         la, lb = lazies
-        rows = L.load().rv_bn_bwd_rows(L.i64(gout.pixels))
+        rows = L.load().rv_bn_bwd_rows(gout.pixels)
         pa = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, gout.cp), dtype=torch.float32, device=t.device)
         pb = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, gout.cp), dtype=torch.float32, device=t.device)
-        L.call("rv_bn_bwd_reduce_pair", L.i64(gout.pixels), L.i32(gout.cp), gout.ptr(), L.i32(gout.ld), mask.ptr(), L.i32(mask.ld),
-               la.raw.ptr(), L.i32(la.raw.ld), L.ptr(la.bn.mean), L.ptr(la.bn.invstd), lb.raw.ptr(), L.i32(lb.raw.ld), L.ptr(lb.bn.mean),
+        L.call("rv_bn_bwd_reduce_pair", gout.pixels, gout.cp, gout.ptr(), gout.ld, mask.ptr(), mask.ld,
+               la.raw.ptr(), la.raw.ld, L.ptr(la.bn.mean), L.ptr(la.bn.invstd), lb.raw.ptr(), lb.raw.ld, L.ptr(lb.bn.mean),
                L.ptr(lb.bn.invstd), L.ptr(pa), L.ptr(pb), L.stream_ptr())
         ops = [t.bn_of.get(id(x)) for x in lazies]
         if all(o is not None for o in ops) and (all(o.sync_world == 1 for o in ops) or (E.GROUP_SYNC_BN and all(o.sync_world > 1 for o in ops))):
@@ -511,9 +511,9 @@ def combine_backward(op: "E.CombineOp", t: Tape) -> None:
                 t.add_param_grad(o.lazy.bn.module.bias, dbeta[:c])
                 coefs.append(coef)
             dya, dyb = la.raw.like(), lb.raw.like()
-            L.call("rv_bn_bwd_apply_pair", L.i64(gout.pixels), L.i32(gout.cp), gout.ptr(), L.i32(gout.ld), mask.ptr(), L.i32(mask.ld),
-                   la.raw.ptr(), L.i32(la.raw.ld), L.ptr(la.bn.mean), L.ptr(la.bn.invstd), L.ptr(coefs[0]), dya.ptr(), L.i32(dya.ld),
-                   lb.raw.ptr(), L.i32(lb.raw.ld), L.ptr(lb.bn.mean), L.ptr(lb.bn.invstd), L.ptr(coefs[1]), dyb.ptr(), L.i32(dyb.ld), L.stream_ptr())
+            L.call("rv_bn_bwd_apply_pair", gout.pixels, gout.cp, gout.ptr(), gout.ld, mask.ptr(), mask.ld,
+                   la.raw.ptr(), la.raw.ld, L.ptr(la.bn.mean), L.ptr(la.bn.invstd), L.ptr(coefs[0]), dya.ptr(), dya.ld,
+                   lb.raw.ptr(), lb.raw.ld, L.ptr(lb.bn.mean), L.ptr(lb.bn.invstd), L.ptr(coefs[1]), dyb.ptr(), dyb.ld, L.stream_ptr())
             t.raw_grad[id(la.raw)] = dya
             t.raw_grad[id(lb.raw)] = dyb
             return
@@ -532,9 +532,9 @@ def combine_backward(op: "E.CombineOp", t: Tape) -> None:
         return
     for x in plains:
         g, have_x = t.grad_buffer(x)
-        L.call("rv_ew_mask_grad", L.i64(gout.pixels), L.i32(gout.cp), gout.ptr(), L.i32(gout.ld),
-               mask.ptr() if mask is not None else None, L.i32(mask.ld if mask is not None else 0), g.ptr(), L.i32(g.ld),
-               L.i32(1 if have_x else 0), L.stream_ptr())
+        L.call("rv_ew_mask_grad", gout.pixels, gout.cp, gout.ptr(), gout.ld,
+               mask.ptr() if mask is not None else None, mask.ld if mask is not None else 0, g.ptr(), g.ld,
+               1 if have_x else 0, L.stream_ptr())
         t.mark_written(x)
 
 
@@ -553,17 +553,17 @@ def modulate_backward(op: "E.MetaModulateOp", t: Tape) -> None:
     if META_BWD_FUSE and pos.relu and st.mean is not None and id(pos) not in t.lazy_in:
         # fused with the BatchNorm(+ReLU) backward of the positional layer: this pass forms dfeat and the (sum z, sum z*xhat)
         # rows; bn_backward finalizes them and a second pass writes dy -- the activated-gradient tensor is never written
-        rows = L.load().rv_meta_bwd_rows(L.i32(feat.N), L.i32(feat.H), L.i32(feat.W))
+        rows = L.load().rv_meta_bwd_rows(feat.N, feat.H, feat.W)
         partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, feat.cp), dtype=torch.float32, device=t.device)
         L.call("rv_meta_modulate_bwd_sums", g.ptr(), pos.raw.ptr(), L.ptr(st.scale), L.ptr(st.shift), L.ptr(st.mean), L.ptr(st.invstd),
-               feat.ptr(), L.i32(feat.ld), L.i32(feat.N), L.i32(feat.H), L.i32(feat.W), L.i32(feat.cp), gf.ptr(), L.i32(gf.ld),
+               feat.ptr(), feat.ld, feat.N, feat.H, feat.W, feat.cp, gf.ptr(), gf.ld,
                L.ptr(partial), L.stream_ptr())
         t.mark_written(feat)
         t.meta_in[id(pos)] = (g, feat, partial, rows)
         return
     dpos = pos.raw.like()
-    L.call("rv_meta_modulate_bwd", g.ptr(), pos.raw.ptr(), L.ptr(pos.bn.scale), L.ptr(pos.bn.shift), feat.ptr(), L.i32(feat.ld),
-           L.i32(feat.N), L.i32(feat.H), L.i32(feat.W), L.i32(feat.cp), dpos.ptr(), gf.ptr(), L.i32(gf.ld), L.stream_ptr())
+    L.call("rv_meta_modulate_bwd", g.ptr(), pos.raw.ptr(), L.ptr(pos.bn.scale), L.ptr(pos.bn.shift), feat.ptr(), feat.ld,
+           feat.N, feat.H, feat.W, feat.cp, dpos.ptr(), gf.ptr(), gf.ld, L.stream_ptr())
     t.mark_written(feat)
     dpos._rv_owned = True
     t.add_lazy_grad(pos, dpos, None)

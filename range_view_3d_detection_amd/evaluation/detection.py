@@ -131,9 +131,9 @@ def match(dts: Tensor, scores: Tensor, dt_segment: Tensor, gts: Tensor, gt_valid
         roi_arg = (ctypes.c_void_p(dt_roi.data_ptr()),)  # (an empty tensor has no pointer: the kernel reads no flag of 0 rows)
     else:
         roi_arg = ()
-    L.call("rv_eval_match" if dt_roi is None else "rv_eval_match_roi", L.ptr(dts), L.ptr(dt_order), L.ptr(dt_off), L.i64(n), L.ptr(gts),
-           L.ptr(gt_valid), L.ptr(gt_order), L.ptr(gt_off), L.i64(m), L.i32(n_segments), thresholds, L.i32(n_thr), L.f64(cfg.tp_threshold_m),
-           L.f64(cfg.max_range_m), L.i32(cfg.max_num_dts_per_category), *roi_arg, L.ptr(out["evaluated"]), L.ptr(out["tp"]), L.ptr(out["err"]),
+    L.call("rv_eval_match" if dt_roi is None else "rv_eval_match_roi", L.ptr(dts), L.ptr(dt_order), L.ptr(dt_off), n, L.ptr(gts),
+           L.ptr(gt_valid), L.ptr(gt_order), L.ptr(gt_off), m, n_segments, thresholds, n_thr, cfg.tp_threshold_m,
+           cfg.max_range_m, cfg.max_num_dts_per_category, *roi_arg, L.ptr(out["evaluated"]), L.ptr(out["tp"]), L.ptr(out["err"]),
            L.ptr(out["matched_gt"]), L.ptr(out["gt_evaluated"]), L.stream_ptr())
     return out
 
@@ -153,13 +153,13 @@ def summarize(scores: Tensor, categories: Tensor, evaluated: Tensor, tp: Tensor,
     n_rows = int(offsets[n_cat])
     order = order[:n_rows]
     flags, errors = tp[order].contiguous(), err[order].contiguous()
-    ws_bytes = L.load().rv_eval_summarize_workspace_bytes(L.i64(n_rows), L.i32(n_cat), L.i32(n_thr))
+    ws_bytes = L.load().rv_eval_summarize_workspace_bytes(n_rows, n_cat, n_thr)
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
     table = torch.empty((n_cat + 1, 5), dtype=torch.float64, device=dev)
     ap_t = torch.empty((n_cat, n_thr), dtype=torch.float64, device=dev)
     defaults = cfg.metrics_defaults
-    L.call("rv_eval_summarize", L.ptr(flags), L.ptr(errors), L.ptr(cat_off), L.ptr(n_gt), L.i64(n_rows), L.i32(n_cat), L.i32(n_thr),
-           L.f64(cfg.tp_threshold_m), L.i32(cfg.num_recall_samples), L.f64(defaults[1]), L.f64(defaults[2]), L.ptr(ws), L.ptr(table),
+    L.call("rv_eval_summarize", L.ptr(flags), L.ptr(errors), L.ptr(cat_off), L.ptr(n_gt), n_rows, n_cat, n_thr,
+           cfg.tp_threshold_m, cfg.num_recall_samples, defaults[1], defaults[2], L.ptr(ws), L.ptr(table),
            L.ptr(ap_t), L.stream_ptr())
     return table.cpu(), ap_t.cpu(), offsets[1:] - offsets[:-1]
 

@@ -14,6 +14,7 @@ The three steps (``rv_waymo_iou``, ``rv_waymo_match``, ``rv_waymo_summarize``) a
 
 from __future__ import annotations
 
+import ctypes
 import math
 from dataclasses import dataclass
 from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple
@@ -88,10 +89,10 @@ def pairwise_iou(dts: Tensor, dt_order: Tensor, dt_off: Tensor, gts: Tensor, gt_
     _require_cuda(dts, "detections")
     _require_cuda(gts, "ground truth")
     n, m = dts.shape[0], gts.shape[0]
-    ws_bytes = L.load().rv_waymo_match_workspace_bytes(L.i64(n), L.i64(m), L.i32(n_segments))
+    ws_bytes = L.load().rv_waymo_match_workspace_bytes(n, m, n_segments)
     ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=dts.device)
-    L.call("rv_waymo_iou", L.ptr(dts), L.ptr(dt_order), L.ptr(dt_off), L.i64(n), L.ptr(gts), L.ptr(gt_order), L.ptr(gt_off), L.i64(m),
-           L.i32(n_segments), L.ptr(ws), L.stream_ptr())
+    L.call("rv_waymo_iou", L.ptr(dts), L.ptr(dt_order), L.ptr(dt_off), n, L.ptr(gts), L.ptr(gt_order), L.ptr(gt_off), m,
+           n_segments, L.ptr(ws), L.stream_ptr())
     return ws
 
 
@@ -115,9 +116,9 @@ def accumulate(dts: Tensor, scores: Tensor, dt_segment: Tensor, gts: Tensor, gt_
             0, torch.where(inside, gt_segment >> 2, n_sweeps), inside.to(torch.int64))
         sweep_valid = (sweep_valid[:n_sweeps] > 0).to(torch.uint8)
     ws = pairwise_iou(dts, dt_order, dt_off, gts, gt_order, gt_off, n_seg)
-    thresholds = (L.f32 * 5)(*[float(t) for t in cfg.iou_thresholds])
-    L.call("rv_waymo_match", L.ptr(dts), L.ptr(scores), L.ptr(dt_order), L.ptr(dt_off), L.i64(n), L.ptr(gts), L.ptr(gt_level),
-           L.ptr(gt_order), L.ptr(gt_off), L.i64(m), L.ptr(sweep_valid), L.i32(n_sweeps), thresholds, L.ptr(ws), L.ptr(tables),
+    thresholds = (ctypes.c_float * 5)(*[float(t) for t in cfg.iou_thresholds])
+    L.call("rv_waymo_match", L.ptr(dts), L.ptr(scores), L.ptr(dt_order), L.ptr(dt_off), n, L.ptr(gts), L.ptr(gt_level),
+           L.ptr(gt_order), L.ptr(gt_off), m, L.ptr(sweep_valid), n_sweeps, thresholds, L.ptr(ws), L.ptr(tables),
            L.ptr(errors), L.stream_ptr())
     return ws
 

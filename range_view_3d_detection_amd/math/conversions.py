@@ -15,7 +15,7 @@ def _convert(name: str, x: Tensor) -> Tensor:
     if flat.dtype not in (torch.float32, torch.float64):
         flat = flat.float()
     out = torch.empty_like(flat)
-    L.call(name, L.ptr(flat), L.i64(flat.shape[0]), L.i32(1 if flat.dtype == torch.float64 else 0), L.ptr(out), L.stream_ptr())
+    L.call(name, L.ptr(flat), flat.shape[0], 1 if flat.dtype == torch.float64 else 0, L.ptr(out), L.stream_ptr())
     return out.reshape(x.shape).to(x.dtype if x.dtype.is_floating_point else out.dtype)
 
 

@@ -15,5 +15,5 @@ def yaw_to_quat(yaw_rad: Tensor) -> Tensor:
     n = yaw_rad.shape[0]
     y = yaw_rad[:, -1].float().contiguous()
     out = torch.empty((n, 4), dtype=torch.float32, device=y.device)
-    L.call("rv_yaw_to_quat", L.ptr(y), L.i64(n), L.i64(1), L.ptr(out), L.stream_ptr())
+    L.call("rv_yaw_to_quat", L.ptr(y), n, 1, L.ptr(out), L.stream_ptr())
     return out.to(yaw_rad.dtype)

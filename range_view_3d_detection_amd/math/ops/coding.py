@@ -20,8 +20,8 @@ def decode_range_view(regressands: Tensor, cart: Tensor, enable_azimuth_invarian
     reg = regressands.detach().float().contiguous()
     c = cart.detach().float().contiguous()
     out = torch.empty((B, 7, H, W), dtype=torch.float32, device=reg.device)
-    L.call("rv_decode_range_view", L.ptr(reg), L.ptr(c), L.i32(B), L.i32(H), L.i32(W),
-           L.i32(1 if enable_azimuth_invariant_targets else 0), L.ptr(out), L.stream_ptr())
+    L.call("rv_decode_range_view", L.ptr(reg), L.ptr(c), B, H, W,
+           1 if enable_azimuth_invariant_targets else 0, L.ptr(out), L.stream_ptr())
     return out.to(dtype)
 
 

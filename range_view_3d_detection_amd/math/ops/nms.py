@@ -34,9 +34,9 @@ def weighted_nms(boxes: Tensor, data2merge: Tensor, scores: Tensor, nms_threshol
     output = torch.zeros_like(data)
     keep = torch.zeros(n, dtype=torch.long, device=boxes.device)
     count = torch.zeros(n, dtype=torch.long, device=boxes.device)
-    ws = torch.empty(L.load().rv_wnms_workspace_bytes(L.i64(n)), dtype=torch.uint8, device=boxes.device)
+    ws = torch.empty(L.load().rv_wnms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
     num_out = ctypes.c_int64(0)
-    L.call("rv_wnms", L.ptr(boxes), L.ptr(data), L.i64(n), L.i32(d), L.f32(nms_threshold), L.f32(merge_thresh), L.ptr(output),
+    L.call("rv_wnms", L.ptr(boxes), L.ptr(data), n, d, nms_threshold, merge_thresh, L.ptr(output),
            L.ptr(keep), L.ptr(count), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
     k = int(num_out.value)
     return order[keep[:k]].contiguous(), output[:k], count[:k]
@@ -78,18 +78,18 @@ def nms_sweeps(cuboids: Tensor, scores: Tensor, categories: Tensor, n_classes: i
     os_ = torch.empty((B, out_cap), dtype=torch.float32, device=dev)
     oc = torch.empty((B, out_cap), dtype=torch.int32, device=dev)
     counts = torch.empty((B, 4), dtype=torch.int64, device=dev)
-    ws = torch.empty(L.load().rv_nms_sweeps_workspace_bytes(L.i32(B), L.i32(cap)), dtype=torch.uint8, device=dev)
+    ws = torch.empty(L.load().rv_nms_sweeps_workspace_bytes(B, cap), dtype=torch.uint8, device=dev)
     num_pre = int(min(num_pre_nms, 2**31 - 1))
 
     def run(mask_words: int, resume: int) -> List[List[int]]:
         masks = torch.empty((B, 1 if hard else 2, mask_words), dtype=torch.int64, device=dev)
-        head = (L.ptr(sc), L.ptr(ct), L.ptr(cub), L.i32(B), L.i64(K), L.i32(n_classes), L.f32(min_confidence), L.f32(iou_threshold))
-        tail = (L.i32(num_pre), L.i32(num_post_nms), L.i32(cap), L.i32(out_cap), L.ptr(ob), L.ptr(os_), L.ptr(oc), L.ptr(counts), L.ptr(ws),
-                L.ptr(masks), L.i64(mask_words), L.i32(resume), L.stream_ptr())
+        head = (L.ptr(sc), L.ptr(ct), L.ptr(cub), B, K, n_classes, min_confidence, iou_threshold)
+        tail = (num_pre, num_post_nms, cap, out_cap, L.ptr(ob), L.ptr(os_), L.ptr(oc), L.ptr(counts), L.ptr(ws),
+                L.ptr(masks), mask_words, resume, L.stream_ptr())
         if hard:
             L.call("rv_nms_sweeps_hard", *head, *tail)
         else:
-            L.call("rv_nms_sweeps", *head, L.f32(0.5), *tail)
+            L.call("rv_nms_sweeps", *head, 0.5, *tail)
         return counts.tolist()  # the one device->host read of the batch (a second one only when the mask budget was exceeded)
 
     budget = int(min(MASK_WORDS, max(1, (cap // 64 + 1) * cap)))  # (small inputs: no more than one class could need)
@@ -143,9 +143,9 @@ def nms_rotated_sorted(boxes: Tensor, iou_threshold: float, cats: Tensor = None)
     n = b.shape[0]
     c = None if cats is None else cats.detach().to(torch.int32).contiguous()
     keep = torch.empty(n, dtype=torch.long, device=b.device)
-    ws = torch.empty(L.load().rv_nms_rotated_workspace_bytes(L.i64(n)), dtype=torch.uint8, device=b.device)
+    ws = torch.empty(L.load().rv_nms_rotated_workspace_bytes(n), dtype=torch.uint8, device=b.device)
     num_out = ctypes.c_int64(0)
-    L.call("rv_nms_rotated", L.ptr(b), L.ptr(c), L.i64(n), L.f32(iou_threshold), L.ptr(keep), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
+    L.call("rv_nms_rotated", L.ptr(b), L.ptr(c), n, iou_threshold, L.ptr(keep), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
     return keep[: int(num_out.value)]
 
 

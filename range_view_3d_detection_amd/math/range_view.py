@@ -31,8 +31,8 @@ def range_view_indices(cart: Tensor, laser_numbers: Tensor, laser_mapping: Tenso
     rows = torch.empty(n, dtype=torch.int32, device=cart.device)
     cols = torch.empty(n, dtype=torch.int32, device=cart.device)
     rng = torch.empty(n, dtype=torch.float64, device=cart.device)
-    L.call("rv_project_indices", L.ptr(cart), L.ptr(laser), L.ptr(mapping), L.i64(n), L.i32(height), L.i32(width),
-           L.i32(VARIANTS[variant]), L.ptr(rows), L.ptr(cols), L.ptr(rng), L.stream_ptr())
+    L.call("rv_project_indices", L.ptr(cart), L.ptr(laser), L.ptr(mapping), n, height, width,
+           VARIANTS[variant], L.ptr(rows), L.ptr(cols), L.ptr(rng), L.stream_ptr())
     return rows, cols, rng
 
 
@@ -41,7 +41,7 @@ def atan2_cr(y: Tensor, x: Tensor) -> Tensor:
     _require_cuda(y, "y")
     y, x = y.double().contiguous(), x.double().contiguous()
     out = torch.empty_like(y)
-    L.call("rv_atan2_cr", L.ptr(y), L.ptr(x), L.i64(y.numel()), L.ptr(out), L.stream_ptr())
+    L.call("rv_atan2_cr", L.ptr(y), L.ptr(x), y.numel(), L.ptr(out), L.stream_ptr())
     return out
 
 
@@ -50,7 +50,7 @@ def hypot_libc(x: Tensor, y: Tensor) -> Tensor:
     _require_cuda(x, "x")
     x, y = x.double().contiguous(), y.double().contiguous()
     out = torch.empty_like(x)
-    L.call("rv_hypot_libc", L.ptr(x), L.ptr(y), L.i64(x.numel()), L.ptr(out), L.stream_ptr())
+    L.call("rv_hypot_libc", L.ptr(x), L.ptr(y), x.numel(), L.ptr(out), L.stream_ptr())
     return out
 
 
@@ -67,8 +67,8 @@ def z_buffer(rows: Tensor, cols: Tensor, distances: Tensor, features: Tensor, he
     # temporaries must stay referenced until the launch is enqueued (the caching allocator would hand
     # their memory to the next temporary otherwise)
     rows_i, cols_i, dist = rows.to(torch.int32).contiguous(), cols.to(torch.int32).contiguous(), distances.double().contiguous()
-    L.call("rv_z_buffer", L.ptr(rows_i), L.ptr(cols_i), L.ptr(dist), L.ptr(feats), L.i64(n), L.i32(c), L.i32(height), L.i32(width),
-           L.f64(min_distance), L.ptr(keys), L.ptr(image), L.ptr(winner), L.stream_ptr())
+    L.call("rv_z_buffer", L.ptr(rows_i), L.ptr(cols_i), L.ptr(dist), L.ptr(feats), n, c, height, width,
+           min_distance, L.ptr(keys), L.ptr(image), L.ptr(winner), L.stream_ptr())
     return image, winner
 
 

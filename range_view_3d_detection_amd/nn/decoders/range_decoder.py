@@ -36,12 +36,12 @@ def decode_candidates(logits: Tensor, regressands: Tensor, cart: Tensor, mask: T
     lo = (ctypes.c_float * max(nb, 1))(*[float(v) for v in lower])
     hi = (ctypes.c_float * max(nb, 1))(*[float(v) for v in upper])
     rt = (ctypes.c_int32 * max(nb, 1))(*[int(v) for v in rates])
-    K = L.load().rv_decode_num_candidates(L.i32(H), L.i32(W), L.i32(nb), rt)
+    K = L.load().rv_decode_num_candidates(H, W, nb, rt)
     scores = torch.empty((B, K), dtype=torch.float32, device=dev)
     cats = torch.empty((B, K), dtype=torch.int64, device=dev)
     boxes = torch.empty((B, K, 7), dtype=torch.float32, device=dev)
-    L.call("rv_decode_candidates", L.ptr(lg), L.ptr(rg), L.ptr(ct), L.ptr(mk), L.i32(B), L.i32(C), L.i32(H), L.i32(W),
-           L.i32(1 if azimuth_invariant else 0), L.i32(nb), lo, hi, rt, L.i64(category_offset), L.ptr(scores), L.ptr(cats),
+    L.call("rv_decode_candidates", L.ptr(lg), L.ptr(rg), L.ptr(ct), L.ptr(mk), B, C, H, W,
+           1 if azimuth_invariant else 0, nb, lo, hi, rt, category_offset, L.ptr(scores), L.ptr(cats),
            L.ptr(boxes), L.stream_ptr())
     return scores, cats, boxes
 

@@ -177,8 +177,8 @@ def _assign_targets(cart32: Tensor, cub_d: Tensor, off_d: Tensor, m: int, tasks_
     reg = torch.empty((B, 8, H, W), dtype=torch.float32, device=dev)
     ppo = torch.empty((B, 1, H, W), dtype=torch.int64, device=dev)
     nobj = torch.empty(1, dtype=torch.int32, device=dev)
-    L.call("rv_assign_targets", L.ptr(cub_d) if m else None, L.i32(m), L.ptr(off_d), L.ptr(cart32), L.i32(B), L.i32(H), L.i32(W),
-           L.i32(n_cls), L.i32(1 if az_inv else 0), L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(scratch[2]), L.ptr(labels),
+    L.call("rv_assign_targets", L.ptr(cub_d) if m else None, m, L.ptr(off_d), L.ptr(cart32), B, H, W,
+           n_cls, 1 if az_inv else 0, L.ptr(scratch[0]), L.ptr(scratch[1]), L.ptr(scratch[2]), L.ptr(labels),
            L.ptr(pan), L.ptr(reg), L.ptr(ppo), L.ptr(nobj), L.stream_ptr())
     return {1: {t_id: {"points_per_obj": ppo, "panoptics": pan, "classification_labels": labels, "regression_targets": reg,
                        "num_objects": nobj, "num_category": torch.ones((B, n_cls, 1, 1), device=dev)}}}
@@ -217,8 +217,8 @@ def _compute_targets_multilevel(cart32: Tensor, cub_d: Tensor, off_d: Tensor, m:
             outs[e] = L.TargetOut(tg["classification_labels"].data_ptr(), tg["panoptics"].data_ptr(), tg["regression_targets"].data_ptr(),
                                   tg["points_per_obj"].data_ptr())
             result[s][t] = tg
-    L.call("rv_assign_targets_multilevel", L.ptr(cub_d) if m else None, L.i32(m), L.ptr(off_d), L.ptr(cart32), L.i32(B), L.i32(H), L.i32(W),
-           L.i32(n_l), levels, L.i32(n_t), task_ids, task_cls, L.i32(1 if az_inv else 0), L.ptr(scratch), outs, L.ptr(nobj), L.stream_ptr())
+    L.call("rv_assign_targets_multilevel", L.ptr(cub_d) if m else None, m, L.ptr(off_d), L.ptr(cart32), B, H, W,
+           n_l, levels, n_t, task_ids, task_cls, 1 if az_inv else 0, L.ptr(scratch), outs, L.ptr(nobj), L.stream_ptr())
     return result
 
 
@@ -244,10 +244,10 @@ class _DetectionLossFn(torch.autograd.Function):
         soft = torch.empty((B, n_cls, H, W), dtype=torch.float32, device=dev)
         fg = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
         coding = (ctypes.c_float * 8)(*[float(v) for v in hp["coding_weights"]])
-        args = (L.ptr(lg), L.i32(ld_l), L.ptr(rg), L.i32(ld_r), L.ptr(cart32), L.ptr(mask8), L.ptr(tg["classification_labels"]),
+        args = (L.ptr(lg), ld_l, L.ptr(rg), ld_r, L.ptr(cart32), L.ptr(mask8), L.ptr(tg["classification_labels"]),
                 L.ptr(tg["panoptics"]), L.ptr(tg["regression_targets"]), L.ptr(tg["points_per_obj"]), L.ptr(tg["num_objects"]),
-                L.i32(B), L.i32(n_cls), L.i32(H), L.i32(W), coding, L.f32(hp["cls_weight"]), L.f32(hp["reg_weight"]),
-                L.f32(hp["smoothing"]), L.f32(hp["sigma"]), L.f32(hp["alpha"]), L.f32(hp["gamma"]), L.i32(1 if hp["az_inv"] else 0))
+                B, n_cls, H, W, coding, hp["cls_weight"], hp["reg_weight"],
+                hp["smoothing"], hp["sigma"], hp["alpha"], hp["gamma"], 1 if hp["az_inv"] else 0)
         L.call("rv_detection_loss_forward", *args, L.ptr(sums), L.ptr(soft), L.ptr(fg), L.stream_ptr())
         ctx.args, ctx.keep = args, (lg, rg, cart32, mask8, tg, coding)
         ctx.sums, ctx.meta = sums, (B, n_cls, H, W, ld_l, ld_r, logits.dtype, regressands.dtype)
@@ -263,7 +263,7 @@ class _DetectionLossFn(torch.autograd.Function):
         d_l = torch.empty((B, H, W, ld_l), dtype=torch.float32, device=dev)
         d_r = torch.empty((B, H, W, ld_r), dtype=torch.float32, device=dev)
         ctx.sums[15:16].copy_(g_loss.reshape(1))  # the incoming gradient as the kernel's device-side factor: one 8-byte copy instead of two passes over the gradients
-        L.call("rv_detection_loss_backward", *ctx.args, L.ptr(ctx.sums), L.f32(1.0), L.ptr(d_l), L.ptr(d_r), L.stream_ptr())
+        L.call("rv_detection_loss_backward", *ctx.args, L.ptr(ctx.sums), 1.0, L.ptr(d_l), L.ptr(d_r), L.stream_ptr())
         return (d_l[..., :n_cls].permute(0, 3, 1, 2).to(dt_l), d_r[..., :8].permute(0, 3, 1, 2).to(dt_r), None, None, None, None)
 
 
@@ -314,22 +314,22 @@ class _MultiLevelLossFn(torch.autograd.Function):
         ctx.kinds = L.LossKinds(*hp["kinds"]) if hp.get("kinds") is not None else None
         if hp.get("soft") is None:
             if ctx.kinds is None:
-                L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), L.ptr(sums), L.stream_ptr())
+                L.call("rv_detection_loss_multilevel_forward", table, n, params, L.ptr(sums), L.stream_ptr())
             else:
-                L.call("rv_detection_loss_table_forward", table, L.i32(n), ctypes.byref(params), ctypes.byref(ctx.kinds), None, L.ptr(sums), L.stream_ptr())
+                L.call("rv_detection_loss_table_forward", table, n, params, ctx.kinds, None, L.ptr(sums), L.stream_ptr())
         else:
             fn, normalize, k = hp["soft"]
             off_d, m = hp["box_offsets"], int(hp["box_count"])
             B = meta[0][0]
             maps = [torch.empty((m_[0], 1, m_[2], m_[3]), dtype=torch.float32, device=dev) for m_ in meta]
             map_ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in maps])
-            ws = torch.empty(max(int(L.load().rv_soft_assign_workspace_bytes(L.i32(n), L.i32(m), L.i32(B))), 1), dtype=torch.uint8, device=dev)
-            L.call("rv_soft_assign", table, L.i32(n), ctypes.byref(params), L.i32(fn), L.i32(1 if normalize else 0), L.i32(k), L.ptr(off_d),
-                   L.i32(m), L.ptr(ws), map_ptrs, L.stream_ptr())
+            ws = torch.empty(max(int(L.load().rv_soft_assign_workspace_bytes(n, m, B)), 1), dtype=torch.uint8, device=dev)
+            L.call("rv_soft_assign", table, n, params, fn, 1 if normalize else 0, k, L.ptr(off_d),
+                   m, L.ptr(ws), map_ptrs, L.stream_ptr())
             if ctx.kinds is None:
-                L.call("rv_detection_loss_multilevel_forward_aff", table, L.i32(n), ctypes.byref(params), map_ptrs, L.ptr(sums), L.stream_ptr())
+                L.call("rv_detection_loss_multilevel_forward_aff", table, n, params, map_ptrs, L.ptr(sums), L.stream_ptr())
             else:
-                L.call("rv_detection_loss_table_forward", table, L.i32(n), ctypes.byref(params), ctypes.byref(ctx.kinds), map_ptrs, L.ptr(sums), L.stream_ptr())
+                L.call("rv_detection_loss_table_forward", table, n, params, ctx.kinds, map_ptrs, L.ptr(sums), L.stream_ptr())
             ctx.maps = (map_ptrs, maps)
             for ent, amap in zip(entries, maps):
                 ent["affinity"] = amap
@@ -349,12 +349,12 @@ class _MultiLevelLossFn(torch.autograd.Function):
             bufs.append((d_l, d_r))
         ctx.sums[n, 15:16].copy_(g_loss.reshape(1))  # the incoming gradient as the kernel's device-side factor
         if ctx.kinds is not None:
-            L.call("rv_detection_loss_table_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), ctypes.byref(ctx.kinds),
-                   None if ctx.maps is None else ctx.maps[0], L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
+            L.call("rv_detection_loss_table_backward", ctx.table, n, ctx.params, ctx.kinds,
+                   None if ctx.maps is None else ctx.maps[0], L.ptr(ctx.sums), 1.0, L.stream_ptr())
         elif ctx.maps is None:
-            L.call("rv_detection_loss_multilevel_backward", ctx.table, L.i32(n), ctypes.byref(ctx.params), L.ptr(ctx.sums), L.f32(1.0), L.stream_ptr())
+            L.call("rv_detection_loss_multilevel_backward", ctx.table, n, ctx.params, L.ptr(ctx.sums), 1.0, L.stream_ptr())
         else:
-            L.call("rv_detection_loss_multilevel_backward_aff", ctx.table, L.i32(n), ctypes.byref(ctx.params), ctx.maps[0], L.ptr(ctx.sums), L.f32(1.0),
+            L.call("rv_detection_loss_multilevel_backward_aff", ctx.table, n, ctx.params, ctx.maps[0], L.ptr(ctx.sums), 1.0,
                    L.stream_ptr())
         grads = []
         for (d_l, d_r), (_, n_cls, _, _, _, _, dt_l, dt_r) in zip(bufs, ctx.meta):

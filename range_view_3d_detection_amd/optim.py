@@ -106,9 +106,9 @@ class AdamW(torch.optim.Optimizer):
             for p in ps:
                 self.state[p]["step"] += 1
             beta1, beta2 = group["betas"]
-            L.call("rv_adamw_step", L.ptr(plan["table"]), L.ptr(plan["chunks"]), L.i32(plan["n_chunks"]), L.ptr(plan["partial"]),
-                   L.f64(float(group["lr"])), L.f64(float(beta1)), L.f64(float(beta2)), L.f64(float(group["eps"])),
-                   L.f64(float(group["weight_decay"])), L.i64(step), L.f64(float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0),
+            L.call("rv_adamw_step", L.ptr(plan["table"]), L.ptr(plan["chunks"]), plan["n_chunks"], L.ptr(plan["partial"]),
+                   float(group["lr"]), float(beta1), float(beta2), float(group["eps"]),
+                   float(group["weight_decay"]), step, float(self.max_grad_norm) if self.max_grad_norm is not None else 0.0,
                    L.ptr(plan["norm"]), L.stream_ptr())
             # the kernel wrote the parameters and moments behind torch's back: tell autograd (and everything keyed on
             # Tensor._version, e.g. the packed bf16 weight images of engine.TapLayer) that they changed

@@ -178,8 +178,8 @@ def range_partition_program(t: Tape, m: nn.Module, features: Tensor, cart: Tenso
         lo = (ctypes.c_float * bands)(*[float(v) for v in m.lower_bounds.detach().flatten().tolist()])
         hi = (ctypes.c_float * bands)(*[float(v) for v in m.upper_bounds.detach().flatten().tolist()])
         m.__dict__["_rv_bounds"] = bounds = (ver, lo, hi)
-    L.call("rv_range_partition", L.ptr(feats32), L.ptr(cart32), L.ptr(mask8), L.i32(n), L.i32(c), L.i32(h), L.i32(w), bounds[1], bounds[2], L.i32(bands),
-           x.ptr(), L.i32(x.ld), L.stream_ptr())
+    L.call("rv_range_partition", L.ptr(feats32), L.ptr(cart32), L.ptr(mask8), n, c, h, w, bounds[1], bounds[2], bands,
+           x.ptr(), x.ld, L.stream_ptr())
     return basic_block_program(t, m.projection, x, out=out, need_input_grad=False)
 
 
@@ -218,8 +218,8 @@ def range_net_program(t: Tape, m: nn.Module, features: Tensor, cart: Tensor, mas
         return range_backbone_program(t, m.net, stem, feat1)
     x = Act.empty(n, h, w, c, t.device, zero=True)
     feats32 = features.contiguous().float()  # keep the temporary referenced across the launch
-    L.call("rv_nchw_f32_to_nhwc_bf16", L.ptr(feats32), L.i32(n), L.i32(c), L.i32(h), L.i32(w), x.ptr(),
-           L.i32(x.ld), L.i32(0), L.stream_ptr())
+    L.call("rv_nchw_f32_to_nhwc_bf16", L.ptr(feats32), n, c, h, w, x.ptr(),
+           x.ld, 0, L.stream_ptr())
     if m.stem_type == "META":
         stem = meta_kernel_program(t, m.stem, x, cart, out=stem_out)
     elif m.stem_type == "BASIC":

@@ -248,20 +248,20 @@ def paste_database(batch: Mapping[str, Any], db: ObjectDatabase, draws: Sequence
         if M:
             rect_a_d, ann_b = up(rect_a), up(ann[:, 12].numpy().astype(np.int32))
             iou_as = torch.empty((M, B * S), dtype=torch.float32, device=dev)
-            L.call("rv_rotated_iou", L.ptr(rect_a_d), L.i64(M), L.ptr(rect_s_d), L.i64(B * S), L.ptr(iou_as), L.stream_ptr())
+            L.call("rv_rotated_iou", L.ptr(rect_a_d), M, L.ptr(rect_s_d), B * S, L.ptr(iou_as), L.stream_ptr())
             keep = keep & ~((iou_as > 0) & (ann_b[:, None] == slot_b[None, :])).any(dim=0)  # loader.py:728-731
         iou_ss = torch.empty((B * S, B * S), dtype=torch.float32, device=dev)
-        L.call("rv_rotated_iou", L.ptr(rect_s_d), L.i64(B * S), L.ptr(rect_s_d), L.i64(B * S), L.ptr(iou_ss), L.stream_ptr())
+        L.call("rv_rotated_iou", L.ptr(rect_s_d), B * S, L.ptr(rect_s_d), B * S, L.ptr(iou_ss), L.stream_ptr())
         hits = ((iou_ss > 0) & (slot_b[:, None] == slot_b[None, :]) & keep[:, None]).sum(dim=0)
         keep = (keep & (hits == 1)).to(torch.uint8).contiguous()  # loader.py:732-733: exactly one hit, the sample itself
         owned = torch.empty(B * S, dtype=torch.uint8, device=dev)
         ws = torch.empty(int(L.load().rv_db_paste_workspace_bytes(B, S, H, W)), dtype=torch.uint8, device=dev)
         f_in, c_in, m_in = feats.float().contiguous(), cart.float().contiguous(), mask.to(torch.uint8).contiguous()
         f_out, c_out, m_out = torch.empty_like(f_in), torch.empty_like(c_in), torch.empty_like(m_in)
-        L.call("rv_db_paste_keys", L.ptr(samples_d), L.ptr(keep), L.i32(B), L.i32(S), L.ptr(db.d_offsets), L.i64(len(db)), L.ptr(db.d_range),
-               L.ptr(db.d_index), L.i64(db.index_max), L.i64(max_work), L.i32(H), L.i32(W), L.ptr(owned), L.ptr(ws), L.stream_ptr())
-        L.call("rv_db_paste_resolve", L.ptr(f_in), L.ptr(c_in), L.ptr(m_in), L.ptr(f_out), L.ptr(c_out), L.ptr(m_out), L.i32(B), L.i32(F), L.i32(H),
-               L.i32(W), L.ptr(samples_d), L.i32(S), L.ptr(db.d_offsets), L.ptr(db.d_points), L.ptr(ws), L.ptr(owned), L.stream_ptr())
+        L.call("rv_db_paste_keys", L.ptr(samples_d), L.ptr(keep), B, S, L.ptr(db.d_offsets), len(db), L.ptr(db.d_range),
+               L.ptr(db.d_index), db.index_max, max_work, H, W, L.ptr(owned), L.ptr(ws), L.stream_ptr())
+        L.call("rv_db_paste_resolve", L.ptr(f_in), L.ptr(c_in), L.ptr(m_in), L.ptr(f_out), L.ptr(c_out), L.ptr(m_out), B, F, H,
+               W, L.ptr(samples_d), S, L.ptr(db.d_offsets), L.ptr(db.d_points), L.ptr(ws), L.ptr(owned), L.stream_ptr())
         alive = (keep & owned).cpu().numpy().reshape(B, S)  # the ONE device-to-host copy, after everything is enqueued
     out["features"], out["cart"], out["mask"] = f_out, c_out, m_out.bool()
     out["pasted"] = [[int(samples[b, s]) for s in range(S) if alive[b, s]] for b in range(B)]
@@ -291,13 +291,13 @@ def extract_interior_pixels(cart: Tensor, mask: Tensor, annotations: Tensor):
         c32, m8 = cart.float().contiguous(), mask.to(torch.uint8).contiguous()
         counts = torch.empty(m, dtype=torch.int64, device=dev)
         obj_offsets = torch.empty(m + 1, dtype=torch.int64, device=dev)
-        args = (L.ptr(c32), L.ptr(m8), L.i32(B), L.i32(H), L.i32(W), L.ptr(cub_d), L.i32(m), L.ptr(offs_d), L.ptr(counts), L.ptr(obj_offsets))
-        L.call("rv_db_extract", *args, L.ptr(None), L.i64(0), L.stream_ptr())
+        args = (L.ptr(c32), L.ptr(m8), B, H, W, L.ptr(cub_d), m, L.ptr(offs_d), L.ptr(counts), L.ptr(obj_offsets))
+        L.call("rv_db_extract", *args, L.ptr(None), 0, L.stream_ptr())
         host_offsets = obj_offsets.cpu().numpy()
         total = int(host_offsets[-1])
         index = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
         if total:
-            L.call("rv_db_extract", *args, L.ptr(index), L.i64(total), L.stream_ptr())
+            L.call("rv_db_extract", *args, L.ptr(index), total, L.stream_ptr())
         return host_offsets, index[:total].cpu().numpy()
 
 

@@ -21,7 +21,7 @@ def _pad(x: Tensor, mask, pad: int, circular: bool) -> Tensor:
     src = x.float().contiguous()
     m = mask.float().reshape(h, w).contiguous() if mask is not None else None
     out = torch.empty((c, h, w + 2 * pad), dtype=torch.float32, device=x.device)
-    L.call("rv_pad_range_view", L.ptr(src), L.ptr(m), L.i32(c), L.i32(h), L.i32(w), L.i32(pad), L.i32(1 if circular else 0), L.ptr(out),
+    L.call("rv_pad_range_view", L.ptr(src), L.ptr(m), c, h, w, pad, 1 if circular else 0, L.ptr(out),
            L.stream_ptr())
     return out
 
@@ -115,8 +115,8 @@ def range_view_from_table(table: Mapping[str, Any], range_view_config: Mapping[s
     cart = torch.empty((3, h, w), dtype=torch.float32, device=dev)
     mask = torch.empty((1, h, w), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
-        L.call("rv_table_to_range_view", L.ptr(block), L.i32(len(need)), L.i64(h * w), L.i32(len(names)), feat_col, feat_op, cart_col,
-               L.i32(need.index("range")), L.i32(need.index("is_within_roi") if roi else -1), L.ptr(features), L.ptr(cart), L.ptr(mask),
+        L.call("rv_table_to_range_view", L.ptr(block), len(need), h * w, len(names), feat_col, feat_op, cart_col,
+               need.index("range"), need.index("is_within_roi") if roi else -1, L.ptr(features), L.ptr(cart), L.ptr(mask),
                L.stream_ptr())
         if not pad:
             return {"features": features, "mask": mask.bool(), "cart": cart}
@@ -282,10 +282,10 @@ def apply_sweep_transforms(x: Tensor, transforms: Sequence[SweepTransform], xyz_
     if keep is not None:
         assert keep.dtype == torch.uint8 and keep.shape == (b, h * w) and keep.is_contiguous()
         post = torch.stack([(t.post if t.post is not None else SweepTransform(w)).packed() for t in transforms]).to(src.device)
-        L.call("rv_augment_dropout", L.ptr(src), L.ptr(out), L.i32(b), L.i32(c), L.i32(h), L.i32(w), L.i32(ix), L.i32(iy), L.i32(iz),
-               L.i32(range_channel), L.ptr(params), L.ptr(post), L.ptr(keep), L.stream_ptr())
+        L.call("rv_augment_dropout", L.ptr(src), L.ptr(out), b, c, h, w, ix, iy, iz,
+               range_channel, L.ptr(params), L.ptr(post), L.ptr(keep), L.stream_ptr())
         return out > 0.5 if was_bool else out
-    L.call("rv_augment", L.ptr(src), L.ptr(out), L.i32(b), L.i32(c), L.i32(h), L.i32(w), L.i32(ix), L.i32(iy), L.i32(iz), L.i32(range_channel),
+    L.call("rv_augment", L.ptr(src), L.ptr(out), b, c, h, w, ix, iy, iz, range_channel,
            L.ptr(params), L.stream_ptr())
     return out > 0.5 if was_bool else out
 

@@ -115,7 +115,7 @@ def _reg(kinds: Kinds, r, r32, tg32, reg_w: float):
         l1 = l1_32 + (l1_64 - l1_64.detach())
         return l1, l1.detach()
     d = r - tg
-    ad, c = d.abs(), R.f32(kinds.reg_param)
+    ad, c = d.abs(), R.fp32(kinds.reg_param)
     if kinds.reg_kind == REG_MSE:
         loss = d * d
         size = loss
@@ -151,17 +151,17 @@ def _entry_forward(e: R.Entry, p: R.Params, kinds: Kinds, aff_map: Optional[torc
     t = aff[:, None] * one_hot
     pos = t > 0
     sp, prob = R._softplus(x), torch.sigmoid(x)
-    alpha, gamma, cls_w = R.f32(p.alpha), R.f32(p.gamma), R.f32(p.cls_weight)
+    alpha, gamma, cls_w = R.fp32(p.alpha), R.fp32(p.gamma), R.fp32(p.cls_weight)
     elem, elem_size, grad_size = _cls(kinds.cls_kind, x, t, sp, prob, alpha, gamma)
     cls = cls_w * elem * m
     size = (cls_w * m * elem_size).detach()
     s = [cls.sum(), (cls * fg[:, None]).sum(), (cls * bg[:, None]).sum(), fg.sum().double()]
     sizes = [size.sum(), (size * fg[:, None]).sum(), (size * bg[:, None]).sum()]
-    smoothing, reg_w = R.f32(p.smoothing), R.f32(p.reg_weight)
+    smoothing, reg_w = R.fp32(p.smoothing), R.fp32(p.reg_weight)
     on = e.labels < n
     norm = torch.where(on, 1.0 / (e.points_per_obj.double() + smoothing).where(on, torch.ones(())), torch.zeros(()).double())[:, None]
     l, l_size = _reg(kinds, r, r32, e.reg_targets, reg_w)
-    coding = torch.tensor([R.f32(c) for c in p.coding_weights], dtype=torch.float64).view(1, 8, 1, 1)
+    coding = torch.tensor([R.fp32(c) for c in p.coding_weights], dtype=torch.float64).view(1, 8, 1, 1)
     per = l * norm * m * coding / 8.0 * on[:, None].double()
     s += list(per.sum(dim=(0, 2, 3)))
     reg_sizes = list((l_size * norm * m * coding / 8.0 * on[:, None].double()).sum(dim=(0, 2, 3)))
@@ -174,7 +174,7 @@ def loss_table(entries: Sequence[R.Entry], params: R.Params, kinds: Kinds = DEFA
     """``loss_ref.loss_table`` with ``kinds``: what ``rv_detection_loss_table_forward`` / ``_backward`` return."""
     n = len(entries)
     parts = [_entry_forward(e, params, kinds, None if aff_maps is None else aff_maps[k]) for k, e in enumerate(entries)]
-    smoothing, cls_w = R.f32(params.smoothing), R.f32(params.cls_weight)
+    smoothing, cls_w = R.fp32(params.smoothing), R.fp32(params.cls_weight)
     total_fg = sum(float(q["s"][3]) for q in parts) + smoothing
     total_obj = float(max(sum(int(e.num_objects) for e in entries), 1))
     rows = torch.zeros((n + 1, R.SUMS_LEN), dtype=torch.float64)
@@ -201,7 +201,7 @@ def loss_table(entries: Sequence[R.Entry], params: R.Params, kinds: Kinds = DEFA
     rows[n, 16:24] = rows[:n, 16:24].sum(dim=0)
     rows[n, 12], rows[n, 13], rows[n, 15] = n * total_obj, n * total_fg, 1.0
     sizes[n, 16:24] = sizes[:n, 16:24].sum(dim=0)
-    scale = R.f32(grad_scale) * float(device_factor)
+    scale = R.fp32(grad_scale) * float(device_factor)
     (total * scale).backward()
     out = []
     for q in parts:
@@ -300,7 +300,7 @@ def torch32_figures(e: R.Entry, p: R.Params, kinds: Kinds, aff_map: Optional[tor
     ref = ref or loss_table([e], p, kinds, None if aff_map is None else [aff_map])
     row, soft, fg, d_l, d_r = torch32_loss(e, p, kinds, aff_map)
     assert torch.equal(fg.double(), ref.entries[0].foreground), "fp32 torch's foreground differs from the reference's"
-    if R.f32(p.smoothing) == 0:  # (0 x inf off the instances in the torch form of the regression part)
+    if R.fp32(p.smoothing) == 0:  # (0 x inf off the instances in the torch form of the regression part)
         row = {j: v for j, v in row.items() if j in (17, 18, 19)}
         d_r = None
     out = figures(ref, 0, row=row, soft=None if aff_map is not None else soft, d_logits=d_l, d_regressands=d_r)

@@ -51,7 +51,7 @@ SUMS_LEN = 24
 NAN = float("nan")
 
 
-def f32(v: float) -> float:
+def fp32(v: float) -> float:
     """The fp32 number the C ABI carries for a Python float."""
     return float(torch.tensor(float(v), dtype=torch.float32))
 
@@ -143,9 +143,9 @@ def decode_centre(r: torch.Tensor, cart: torch.Tensor, az_inv: bool) -> torch.Te
 def gaussian_affinity(e: Entry, p: Params):
     """(affinity (B,H,W) f64 with the fp32 zeros, d / sigma^2 (B,H,W) f64)."""
     r = e.regressands[..., :8].permute(0, 3, 1, 2)
-    sigma = f32(p.sigma)
+    sigma = fp32(p.sigma)
     d = (decode_centre(r, e.cart, True) - decode_centre(e.reg_targets, e.cart, bool(p.az_inv))).norm(dim=1)
-    u = d / f32(sigma * sigma)
+    u = d / fp32(sigma * sigma)
     inst = e.panoptics > 0
     band = inst & (u > 60.0) & (u < 125.0)
     assert not bool(band.any()), "an instance pixel with d / sigma^2 in (60, 125): fp32 exponentials may differ in denormal handling there"
@@ -177,20 +177,20 @@ def _entry_forward(e: Entry, p: Params, aff_map: Optional[torch.Tensor]):
     t = aff[:, None] * one_hot
     pos = t > 0
     sp, prob = _softplus(x), torch.sigmoid(x)
-    alpha, gamma, cls_w = f32(p.alpha), f32(p.gamma), f32(p.cls_weight)
+    alpha, gamma, cls_w = fp32(p.alpha), fp32(p.gamma), fp32(p.cls_weight)
     vfl = torch.where(pos, t * (sp - x * t), alpha * prob.pow(gamma) * sp)
     cls = cls_w * vfl * m
     size = (cls_w * m * torch.where(pos, t * torch.maximum(sp, x.abs() * t), vfl)).detach()
     s = [cls.sum(), (cls * fg[:, None]).sum(), (cls * bg[:, None]).sum(), fg.sum().double()]
     sizes = [size.sum(), (size * fg[:, None]).sum(), (size * bg[:, None]).sum()]
     # regression
-    smoothing, reg_w = f32(p.smoothing), f32(p.reg_weight)
+    smoothing, reg_w = fp32(p.smoothing), fp32(p.reg_weight)
     on = e.labels < n  # (off these pixels points_per_obj is 0 and, with smoothing 0, the normaliser is not defined: they take no part)
     norm = torch.where(on, 1.0 / (e.points_per_obj.double() + smoothing).where(on, torch.ones(())), torch.zeros(()).double())[:, None]
     l1_32 = ((r32 - e.reg_targets).abs() * torch.tensor(reg_w, dtype=torch.float32)).double()  # the fp32 tensors of the operation
     l1_64 = (r - e.reg_targets.double()).abs() * reg_w
     l1 = l1_32 + (l1_64 - l1_64.detach())  # value: fp32-defined; gradient: through the fp64 expression
-    coding = torch.tensor([f32(c) for c in p.coding_weights], dtype=torch.float64).view(1, 8, 1, 1)
+    coding = torch.tensor([fp32(c) for c in p.coding_weights], dtype=torch.float64).view(1, 8, 1, 1)
     per = l1 * norm * m * coding / 8.0 * on[:, None].double()
     s += list(per.sum(dim=(0, 2, 3)))
     return dict(x=x, r=r, s=s, sizes=sizes, t=t.detach(), pos=pos, prob=prob.detach(), fg=fg, u=u)
@@ -202,7 +202,7 @@ def loss_table(entries: Sequence[Entry], params: Params, aff_maps: Optional[Sequ
     row); ``aff_maps``: the ``_aff`` form.  ``device_factor`` is what the caller left in [15] of the totals row before backward."""
     n = len(entries)
     parts = [_entry_forward(e, params, None if aff_maps is None else aff_maps[k]) for k, e in enumerate(entries)]
-    smoothing, cls_w = f32(params.smoothing), f32(params.cls_weight)
+    smoothing, cls_w = fp32(params.smoothing), fp32(params.cls_weight)
     total_fg = sum(float(q["s"][3]) for q in parts) + smoothing
     total_obj = float(max(sum(int(e.num_objects) for e in entries), 1))
     rows = torch.zeros((n + 1, SUMS_LEN), dtype=torch.float64)
@@ -224,7 +224,7 @@ def loss_table(entries: Sequence[Entry], params: Params, aff_maps: Optional[Sequ
     rows[n, 16:24] = rows[:n, 16:24].sum(dim=0)
     rows[n, 12], rows[n, 13], rows[n, 15] = n * total_obj, n * total_fg, 1.0
     sizes[n, 16:20] = sizes[:n, 16:20].sum(dim=0)
-    scale = f32(grad_scale) * float(device_factor)
+    scale = fp32(grad_scale) * float(device_factor)
     (total * scale).backward()
     out = []
     for q in parts:
@@ -298,7 +298,7 @@ def oracle_fp32_figures(e: Entry, p: Params, ref: Optional[TableResult] = None) 
     out, d_l, _ = oracle_loss(e, p, torch.float32)
     assert torch.equal(out["foreground"][:, 0].double(), ref.entries[0].foreground), "the fp32 oracle's foreground differs from the reference's"
     # (smoothing 0: the oracle's regression part is 0 x inf off the instances, and with it its total; the classification scalars stand)
-    keys = {j: k for j, k in ORACLE_ROW.items() if j != 16 or f32(p.smoothing) != 0}
+    keys = {j: k for j, k in ORACLE_ROW.items() if j != 16 or fp32(p.smoothing) != 0}
     return figures(ref, 0, row={j: float(out[k].detach()) for j, k in keys.items()}, soft=out["targets"], d_logits=d_l)
 
 
@@ -433,7 +433,7 @@ def yardstick_cases():
     cases = []
     for i, (name, p) in enumerate(OPTIONS.items()):
         for n_cls, ld in ((3, 32), (26, 32), (7, 40)):
-            cases.append((f"{name}-{n_cls}", make_entry(1000 + 7 * i + n_cls, 2, 5, 67, n_cls, ld, 8, underflow=f32(p.sigma) == 0.25), p))
+            cases.append((f"{name}-{n_cls}", make_entry(1000 + 7 * i + n_cls, 2, 5, 67, n_cls, ld, 8, underflow=fp32(p.sigma) == 0.25), p))
     return cases
 
 

@@ -75,8 +75,8 @@ def test_both_builds_export_the_evaluation_entry_points(tag):
     assert set(EVAL_SYMBOLS) <= set(_lib.declared_symbols())
     assert all(hasattr(handle, s) for s in EVAL_SYMBOLS)
     # 12 bytes per row and threshold + the per-category sums, each part rounded up to 256 bytes
-    assert handle.rv_eval_summarize_workspace_bytes(_lib.i64(1000), _lib.i32(26), _lib.i32(4)) == 32000 + 16128 + 1024
-    assert handle.rv_eval_summarize_workspace_bytes(_lib.i64(-1), _lib.i32(26), _lib.i32(4)) == 0
+    assert handle.rv_eval_summarize_workspace_bytes(1000, 26, 4) == 32000 + 16128 + 1024
+    assert handle.rv_eval_summarize_workspace_bytes(-1, 26, 4) == 0
 
 
 def test_argument_checks_need_no_device():
@@ -88,13 +88,13 @@ def test_argument_checks_need_no_device():
     thr = (ctypes.c_double * 9)(*([1.0] * 9))
     null = ctypes.c_void_p(0)
     with pytest.raises(L.RvError, match="thresholds"):
-        L.call("rv_eval_match", null, null, null, L.i64(0), null, null, null, null, L.i64(0), L.i32(1), thr, L.i32(9), L.f64(2.0), L.f64(150.0),
-               L.i32(100), null, null, null, null, null, null)
+        L.call("rv_eval_match", null, null, null, 0, null, null, null, null, 0, 1, thr, 9, 2.0, 150.0,
+               100, null, null, null, null, null, null)
     with pytest.raises(L.RvError, match="max_num_dts"):
-        L.call("rv_eval_match", null, null, null, L.i64(0), null, null, null, null, L.i64(0), L.i32(1), thr, L.i32(4), L.f64(2.0), L.f64(150.0),
-               L.i32(L.EVAL_MAX_DTS + 1), null, null, null, null, null, null)
+        L.call("rv_eval_match", null, null, null, 0, null, null, null, null, 0, 1, thr, 4, 2.0, 150.0,
+               L.EVAL_MAX_DTS + 1, null, null, null, null, null, null)
     with pytest.raises(L.RvError, match="null"):
-        L.call("rv_eval_summarize", null, null, null, null, L.i64(0), L.i32(1), L.i32(4), L.f64(2.0), L.i32(100), L.f64(1.0), L.f64(math.pi),
+        L.call("rv_eval_summarize", null, null, null, null, 0, 1, 4, 2.0, 100, 1.0, math.pi,
                null, null, null, null)
 
 

@@ -60,17 +60,17 @@ class _Table:
 
     def assign(self, affinity_fn, normalize, k, off_d, m):
         L = self.L
-        nbytes = int(L.load().rv_soft_assign_workspace_bytes(L.i32(self.n), L.i32(m), L.i32(self.B)))
+        nbytes = int(L.load().rv_soft_assign_workspace_bytes(self.n, m, self.B))
         assert nbytes >= self.n * (m + self.B) * 259 * 4
         ws = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device=DEV)
-        L.call("rv_soft_assign", self.table, L.i32(self.n), ctypes.byref(self.params), L.i32(L.AFFINITY_BEV if affinity_fn.upper() == "BEV" else L.AFFINITY_GAUSSIAN),
-               L.i32(1 if normalize else 0), L.i32(0 if k == INF else int(k)), L.ptr(off_d), L.i32(m), L.ptr(ws), self.map_ptrs, L.stream_ptr())
+        L.call("rv_soft_assign", self.table, self.n, ctypes.byref(self.params), L.AFFINITY_BEV if affinity_fn.upper() == "BEV" else L.AFFINITY_GAUSSIAN,
+               1 if normalize else 0, 0 if k == INF else int(k), L.ptr(off_d), m, L.ptr(ws), self.map_ptrs, L.stream_ptr())
         return self
 
     def loss(self):
         L = self.L
-        L.call("rv_detection_loss_multilevel_forward_aff", self.table, L.i32(self.n), ctypes.byref(self.params), self.map_ptrs, L.ptr(self.sums), L.stream_ptr())
-        L.call("rv_detection_loss_multilevel_backward_aff", self.table, L.i32(self.n), ctypes.byref(self.params), self.map_ptrs, L.ptr(self.sums), L.f32(1.0),
+        L.call("rv_detection_loss_multilevel_forward_aff", self.table, self.n, ctypes.byref(self.params), self.map_ptrs, L.ptr(self.sums), L.stream_ptr())
+        L.call("rv_detection_loss_multilevel_backward_aff", self.table, self.n, ctypes.byref(self.params), self.map_ptrs, L.ptr(self.sums), 1.0,
                L.stream_ptr())
         torch.cuda.synchronize()
         return self

@@ -117,18 +117,18 @@ def test_bn_backward_kernels_exact():
         dv = lambda t_, dt=None: t_.to(DEV) if dt is None else t_.to(DEV, dt)
         d_dout, d_y, d_out = dv(dout, torch.bfloat16), dv(y, torch.bfloat16), dv(out, torch.bfloat16)
         d_sc, d_sh, d_mu, d_is, d_ga = dv(scale), dv(shift), dv(mean), dv(invstd), dv(gamma)
-        rows = L.load().rv_bn_bwd_rows(L.i64(n_px))
+        rows = L.load().rv_bn_bwd_rows(n_px)
         partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, c), dtype=torch.float32, device=DEV)
-        common = (L.i64(n_px), L.i32(c), L.ptr(d_dout), L.i32(c), L.ptr(d_out) if use_out else None, L.i32(c), L.ptr(d_y), L.i32(c),
+        common = (n_px, c, L.ptr(d_dout), c, L.ptr(d_out) if use_out else None, c, L.ptr(d_y), c,
                   L.ptr(d_sc), L.ptr(d_sh), L.ptr(d_mu), L.ptr(d_is))
-        L.call("rv_bn_bwd_reduce", *common, L.i32(flags), L.ptr(partial), L.stream_ptr())
+        L.call("rv_bn_bwd_reduce", *common, flags, L.ptr(partial), L.stream_ptr())
         dgamma = torch.empty(c, device=DEV)
         dbeta = torch.empty(c, device=DEV)
         coef = torch.empty((3, c), device=DEV)
-        L.call("rv_bn_bwd_finalize", L.ptr(partial), L.i32(rows), L.i32(c), L.i64(n_px), L.ptr(d_ga), L.ptr(d_is), L.ptr(dgamma),
-               L.ptr(dbeta), L.i32(0), L.ptr(coef), L.stream_ptr())
+        L.call("rv_bn_bwd_finalize", L.ptr(partial), rows, c, n_px, L.ptr(d_ga), L.ptr(d_is), L.ptr(dgamma),
+               L.ptr(dbeta), 0, L.ptr(coef), L.stream_ptr())
         dy = torch.empty((n_px, c), dtype=torch.bfloat16, device=DEV)
-        L.call("rv_bn_bwd_apply", *common, L.ptr(coef), L.i32(flags), L.ptr(dy), L.i32(c), None, L.i32(0), L.stream_ptr())
+        L.call("rv_bn_bwd_apply", *common, L.ptr(coef), flags, L.ptr(dy), c, None, 0, L.stream_ptr())
         assert rel_err(dbeta, s0) < 1e-5 and rel_err(dgamma, s1) < 1e-5
         assert rel_err(dy.float(), dy_ref) < 4e-3  # one bf16 ulp
 
@@ -372,14 +372,14 @@ def test_meta_modulate_backward_fused_kernels_vs_fp32(N, H, W, C):
     invstd = (0.5 + torch.rand(C, generator=gen)).to(DEV)
     coef = torch.stack([0.5 + torch.rand(C, generator=gen), 0.1 * torch.randn(C, generator=gen), 0.1 * torch.randn(C, generator=gen)]).to(DEV)
     lib = L.load()
-    rows = lib.rv_meta_bwd_rows(L.i32(N), L.i32(H), L.i32(W))
+    rows = lib.rv_meta_bwd_rows(N, H, W)
     partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, C), float("nan"), dtype=torch.float32, device=DEV)
     dfeat = torch.empty_like(feat)
     dy = torch.empty_like(y)
-    L.call("rv_meta_modulate_bwd_sums", L.ptr(dgeo), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.ptr(feat), L.i32(C),
-           L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(dfeat), L.i32(C), L.ptr(partial), L.stream_ptr())
+    L.call("rv_meta_modulate_bwd_sums", L.ptr(dgeo), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.ptr(feat), C,
+           N, H, W, C, L.ptr(dfeat), C, L.ptr(partial), L.stream_ptr())
     L.call("rv_meta_modulate_bwd_apply", L.ptr(dgeo), L.ptr(y), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.ptr(coef), L.ptr(feat),
-           L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(dy), L.stream_ptr())
+           C, N, H, W, C, L.ptr(dy), L.stream_ptr())
     torch.cuda.synchronize()
     # fp32 restatement: nbr[n,h,w,k] = feat[n, h+k//3-1, w+k%3-1] (zero outside), exactly F.unfold's neighbourhood order
     fp = F.pad(feat.float(), (0, 0, 1, 1, 1, 1))
@@ -453,10 +453,10 @@ def test_pos_backward_sums_kernel_vs_fp64(P, C):
     s1, t1 = 0.5 + torch.rand(C, generator=gen), 0.3 * torch.randn(C, generator=gen)
     mu, isd = 0.2 * torch.randn(C, generator=gen), 0.5 + torch.rand(C, generator=gen)
     rel, w1, w2s, dy2, s1, t1, mu, isd = (x.to(DEV) for x in (rel, w1, w2s, dy2, s1, t1, mu, isd))
-    ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(L.i64(P), L.i32(C), L.i32(3)), dtype=torch.uint8, device=DEV)
+    ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(P, C, 3), dtype=torch.uint8, device=DEV)
     sums = torch.zeros(6 * C, dtype=torch.float64, device=DEV)
     moms = torch.zeros(20, dtype=torch.float64, device=DEV)
-    L.call("rv_pos_backward_sums", L.i64(P), L.i32(C), L.ptr(dy2), L.ptr(w2s), L.ptr(rel), L.i32(32), L.i32(3), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1),
+    L.call("rv_pos_backward_sums", P, C, L.ptr(dy2), L.ptr(w2s), L.ptr(rel), 32, 3, L.ptr(w1), 32, L.ptr(s1), L.ptr(t1),
            L.ptr(mu), L.ptr(isd), L.ptr(sums), L.ptr(moms), L.ptr(ws), L.stream_ptr())
     torch.cuda.synchronize()
     r3 = rel[:, :3].double()
@@ -730,13 +730,13 @@ def test_head_final_sums_kernel_vs_fp64_with_and_without_relu(relu):
     shift = (0.3 * torch.randn(C, generator=gen)).to(DEV)
     mean = (0.1 * torch.randn(C, generator=gen)).to(DEV)
     invstd = (0.8 + 0.4 * torch.rand(C, generator=gen)).to(DEV)
-    rows = lib.rv_head_final_bwd_rows(L.i64(P))
+    rows = lib.rv_head_final_bwd_rows(P)
     partial = torch.zeros((rows + L.STATS_SCRATCH_ROWS, 2, C), dtype=torch.float32, device=DEV)
     dw_partial = torch.zeros((rows, 32 * C), dtype=torch.float32, device=DEV)
-    L.call("rv_head_final_bwd_sums", L.i64(P), L.i32(C), L.ptr(y), L.i32(C), L.ptr(dY), L.i32(32), L.ptr(wp), L.ptr(scale), L.ptr(shift),
-           L.ptr(mean), L.ptr(invstd), L.i32(relu), L.ptr(partial), L.ptr(dw_partial), L.stream_ptr())
+    L.call("rv_head_final_bwd_sums", P, C, L.ptr(y), C, L.ptr(dY), 32, L.ptr(wp), L.ptr(scale), L.ptr(shift),
+           L.ptr(mean), L.ptr(invstd), relu, L.ptr(partial), L.ptr(dw_partial), L.stream_ptr())
     dw = torch.empty((32, C), dtype=torch.float32, device=DEV)
-    L.call("rv_reduce_rows", L.ptr(dw_partial), L.i32(rows), L.i32(32 * C), L.ptr(dw), L.stream_ptr())
+    L.call("rv_reduce_rows", L.ptr(dw_partial), rows, 32 * C, L.ptr(dw), L.stream_ptr())
     torch.cuda.synchronize()
     yd, dYd = y.double().cpu(), dY.double().cpu()
     t = yd * scale.double().cpu() + shift.double().cpu()

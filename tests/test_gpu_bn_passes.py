@@ -184,13 +184,13 @@ def _run_reduce(D, n, layout, use_out, relu_z, expect_form, y_op=None):
     c = D.c
     (dout, ld_dout), (out, ld_out), (y, ld_y) = D.op("dout", layout, n), D.op("out", layout, n), y_op or D.op("y", layout, n)
     info = _info(L.EW_PASS_BWD_REDUCE, n, c, (ld_dout, ld_out, ld_y), use_out)
-    rows = L.load().rv_bn_bwd_rows(L.i64(n))
+    rows = L.load().rv_bn_bwd_rows(n)
     assert rows == (n + 511) // 512
     assert info == (expect_form, 0, rows, 1 if (use_out and expect_form == L.EW_FORM_LEAN) else 0), info
     partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, c), float("nan"), dtype=torch.float32, device=DEV)
     flags = L.BNB_RELU_Z if relu_z else 0
-    L.call("rv_bn_bwd_reduce", L.i64(n), L.i32(c), L.ptr(dout), L.i32(ld_dout), L.ptr(out) if use_out else None, L.i32(ld_out), L.ptr(y), L.i32(ld_y),
-           L.ptr(D.scale), L.ptr(D.shift), L.ptr(D.mean), L.ptr(D.invstd), L.i32(flags), L.ptr(partial), L.stream_ptr())
+    L.call("rv_bn_bwd_reduce", n, c, L.ptr(dout), ld_dout, L.ptr(out) if use_out else None, ld_out, L.ptr(y), ld_y,
+           L.ptr(D.scale), L.ptr(D.shift), L.ptr(D.mean), L.ptr(D.invstd), flags, L.ptr(partial), L.stream_ptr())
     _sync()
     g = R.masked_grad(D.dout[:n], D.out[:n] if use_out else None, D.y[:n], D.scale, D.shift, relu_z)
     s0, s1 = R.bwd_sums(g, R.xhat(D.y[:n], D.mean, D.invstd))
@@ -210,11 +210,11 @@ def _run_reduce_pair(D, n, layout, expect_form, ya_op=None):
     c = D.c
     (dout, ld_dout), (out, ld_out), (ya, ld_ya), (yb, ld_yb) = D.op("dout", layout, n), D.op("out", layout, n), ya_op or D.op("y", layout, n), D.op("yb", layout, n)
     info = _info(L.EW_PASS_BWD_REDUCE_PAIR, n, c, (ld_dout, ld_out, ld_ya, ld_yb), True)
-    rows = L.load().rv_bn_bwd_rows(L.i64(n))
+    rows = L.load().rv_bn_bwd_rows(n)
     assert info == (expect_form, 0, rows, 0), info
     pa, pb = (torch.full((rows + L.STATS_SCRATCH_ROWS, 2, c), float("nan"), dtype=torch.float32, device=DEV) for _ in range(2))
-    L.call("rv_bn_bwd_reduce_pair", L.i64(n), L.i32(c), L.ptr(dout), L.i32(ld_dout), L.ptr(out), L.i32(ld_out), L.ptr(ya), L.i32(ld_ya), L.ptr(D.mean),
-           L.ptr(D.invstd), L.ptr(yb), L.i32(ld_yb), L.ptr(D.mean_b), L.ptr(D.invstd_b), L.ptr(pa), L.ptr(pb), L.stream_ptr())
+    L.call("rv_bn_bwd_reduce_pair", n, c, L.ptr(dout), ld_dout, L.ptr(out), ld_out, L.ptr(ya), ld_ya, L.ptr(D.mean),
+           L.ptr(D.invstd), L.ptr(yb), ld_yb, L.ptr(D.mean_b), L.ptr(D.invstd_b), L.ptr(pa), L.ptr(pb), L.stream_ptr())
     _sync()
     g = R.masked_grad(D.dout[:n], D.out[:n], None, None, None, False)
     what = f"reduce_pair n={n} c={c} {layout}"
@@ -249,9 +249,9 @@ def _run_apply(D, n, layout, use_out, relu_z, dres_mode, expect, dt=torch.float6
     else:
         lanes, index = 256 // (c // 8), nt
     assert info == (form, nt, min(4096, (n + lanes - 1) // lanes), index), info
-    L.call("rv_bn_bwd_apply", L.i64(n), L.i32(c), L.ptr(dout), L.i32(ld_dout), L.ptr(out) if use_out else None, L.i32(ld_out_arg), L.ptr(y), L.i32(ld_y),
-           L.ptr(D.scale), L.ptr(D.shift), L.ptr(D.mean), L.ptr(D.invstd), L.ptr(D.coef), L.i32(flags), L.ptr(dy.view), L.i32(dy.ld),
-           L.ptr(dr.view) if dr else None, L.i32(ld_dres_arg), L.stream_ptr())
+    L.call("rv_bn_bwd_apply", n, c, L.ptr(dout), ld_dout, L.ptr(out) if use_out else None, ld_out_arg, L.ptr(y), ld_y,
+           L.ptr(D.scale), L.ptr(D.shift), L.ptr(D.mean), L.ptr(D.invstd), L.ptr(D.coef), flags, L.ptr(dy.view), dy.ld,
+           L.ptr(dr.view) if dr else None, ld_dres_arg, L.stream_ptr())
     _sync()
     what = f"apply n={n} c={c} {layout} out={use_out} relu_z={relu_z} dres={dres_mode} F/MODE={index}"
 
@@ -272,9 +272,9 @@ def _run_apply_pair(D, n, layout, expect_nt, dt=torch.float64, wide=True):
     info = _info(L.EW_PASS_BWD_APPLY_PAIR, n, c, None, True)
     lanes = 256 // (c // 8)
     assert info == (L.EW_FORM_OCTET, expect_nt, min(4096, (n + lanes - 1) // lanes), expect_nt), info
-    L.call("rv_bn_bwd_apply_pair", L.i64(n), L.i32(c), L.ptr(dout), L.i32(ld_dout), L.ptr(out), L.i32(ld_out), L.ptr(ya), L.i32(ld_ya), L.ptr(D.mean),
-           L.ptr(D.invstd), L.ptr(D.coef), L.ptr(dya.view), L.i32(dya.ld), L.ptr(yb), L.i32(ld_yb), L.ptr(D.mean_b), L.ptr(D.invstd_b), L.ptr(D.coef_b),
-           L.ptr(dyb.view), L.i32(dyb.ld), L.stream_ptr())
+    L.call("rv_bn_bwd_apply_pair", n, c, L.ptr(dout), ld_dout, L.ptr(out), ld_out, L.ptr(ya), ld_ya, L.ptr(D.mean),
+           L.ptr(D.invstd), L.ptr(D.coef), L.ptr(dya.view), dya.ld, L.ptr(yb), ld_yb, L.ptr(D.mean_b), L.ptr(D.invstd_b), L.ptr(D.coef_b),
+           L.ptr(dyb.view), dyb.ld, L.stream_ptr())
     _sync()
     g_of = lambda p0, p1: R.masked_grad(D.dout[p0:p1], D.out[p0:p1], None, None, None, False, dt)
     what = f"apply_pair n={n} c={c} {layout}"
@@ -298,8 +298,8 @@ def _run_combine(D, n, layout, variant, expect, dt=torch.float64, wide=True):
     assert info == (*expect, 1 if (has_b and expect[0] == L.EW_FORM_ROWS) else 0), info
     sa, ta = (D.sa, D.ta) if aff_a else (None, None)
     sb, tb = (D.sb, D.tb) if (aff_b and has_b) else (None, None)
-    L.call("rv_ew_combine", L.i64(n), L.i32(c), L.ptr(a), L.i32(ld_a), L.ptr(sa), L.ptr(ta), L.ptr(b) if has_b else None, L.i32(ld_b if has_b else 0),
-           L.ptr(sb), L.ptr(tb), L.ptr(o.view), L.i32(o.ld), L.i32(flags), L.stream_ptr())
+    L.call("rv_ew_combine", n, c, L.ptr(a), ld_a, L.ptr(sa), L.ptr(ta), L.ptr(b) if has_b else None, ld_b if has_b else 0,
+           L.ptr(sb), L.ptr(tb), L.ptr(o.view), o.ld, flags, L.stream_ptr())
     _sync()
     o.check(lambda p0, p1: R.combine(D.y[p0:p1], sa, ta, D.yb[p0:p1] if has_b else None, sb, tb, flags, dt), f"combine n={n} c={c} {layout} {variant}")
 
@@ -311,8 +311,8 @@ def _run_mask_grad(D, n, layout, use_out, accumulate, expect_grid):
     d = _Out(n, c, D.dtype, init=D.dres_old[:n] if accumulate else None)
     info = _info(L.EW_PASS_MASK_GRAD, n, c, None, use_out)
     assert info == (L.EW_FORM_COMB, 0, expect_grid, 0), info
-    L.call("rv_ew_mask_grad", L.i64(n), L.i32(c), L.ptr(dout), L.i32(ld_dout), L.ptr(out) if use_out else None, L.i32(ld_out if use_out else 0),
-           L.ptr(d.view), L.i32(d.ld), L.i32(1 if accumulate else 0), L.stream_ptr())
+    L.call("rv_ew_mask_grad", n, c, L.ptr(dout), ld_dout, L.ptr(out) if use_out else None, ld_out if use_out else 0,
+           L.ptr(d.view), d.ld, 1 if accumulate else 0, L.stream_ptr())
     _sync()
     d.check(lambda p0, p1: R.mask_grad(D.dout[p0:p1], D.out[p0:p1] if use_out else None, D.dres_old[p0:p1] if accumulate else None),
             f"mask_grad n={n} c={c} {layout} out={use_out} accumulate={accumulate}")
@@ -516,7 +516,7 @@ def _bn_finalize(partial, rows, c, count, gamma, beta, rm, rv, want_stats=True):
     L = _L()
     o = {k: torch.full((c + 8,), SENTINEL, dtype=torch.float32, device=DEV) for k in ("scale", "shift", "mean", "invstd")}
     opt = lambda t: L.ptr(t) if (t is not None and want_stats) else None
-    L.call("rv_bn_finalize", L.ptr(partial), L.i32(rows), L.i32(c), L.i64(count), L.ptr(gamma), L.ptr(beta), L.f32(EPS), L.f32(MOMENTUM), opt(rm), opt(rv),
+    L.call("rv_bn_finalize", L.ptr(partial), rows, c, count, L.ptr(gamma), L.ptr(beta), EPS, MOMENTUM, opt(rm), opt(rv),
            L.ptr(o["scale"]), L.ptr(o["shift"]), opt(o["mean"]), opt(o["invstd"]), L.stream_ptr())
     _sync()
     for k, t in o.items():
@@ -587,7 +587,7 @@ def test_bn_fold_eval(c):
     rnd = lambda *s: torch.rand(s, generator=g, device=DEV)
     gamma, beta, rm, rv = rnd(c) + 0.5, rnd(c) - 0.5, rnd(c) * 4 - 2, rnd(c) + 0.01
     scale, shift = (torch.full((c + 8,), SENTINEL, dtype=torch.float32, device=DEV) for _ in range(2))
-    L.call("rv_bn_fold_eval", L.i32(c), L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), L.f32(EPS), L.ptr(scale), L.ptr(shift), L.stream_ptr())
+    L.call("rv_bn_fold_eval", c, L.ptr(gamma), L.ptr(beta), L.ptr(rm), L.ptr(rv), EPS, L.ptr(scale), L.ptr(shift), L.stream_ptr())
     _sync()
     ref_scale, ref_shift = R.bn_fold_eval(gamma, beta, rm, rv, EPS)
     _check_fin({"scale": scale[:c], "shift": shift[:c]}, {"scale": ref_scale, "shift": ref_shift}, ("scale", "shift"), f"fold_eval c={c}")
@@ -616,8 +616,8 @@ def _check_bwd_finalize(partial, rows, c, count, count_arg, g, what):
         dgamma[:c], dbeta[:c] = old[0], old[1]
         coef = torch.full((3 * c + 8,), SENTINEL, dtype=torch.float32, device=DEV)
         ref_dgamma, ref_dbeta, ref_coef = R.bwd_finalize(tot[0], tot[1], count, gamma, invstd, *((old[0], old[1]) if mode == "accumulate" else ()))
-        L.call("rv_bn_bwd_finalize", L.ptr(partial), L.i32(rows), L.i32(c), L.i64(count_arg), L.ptr(gamma), L.ptr(invstd),
-               L.ptr(dgamma) if mode != "null" else None, L.ptr(dbeta) if mode != "null" else None, L.i32(1 if mode == "accumulate" else 0), L.ptr(coef),
+        L.call("rv_bn_bwd_finalize", L.ptr(partial), rows, c, count_arg, L.ptr(gamma), L.ptr(invstd),
+               L.ptr(dgamma) if mode != "null" else None, L.ptr(dbeta) if mode != "null" else None, 1 if mode == "accumulate" else 0, L.ptr(coef),
                L.stream_ptr())
         _sync()
         w = f"{what} ({mode})"
@@ -668,12 +668,12 @@ def test_reduce_rows(cols):
         ref = partial[:rows].double().sum(0)
         new = lambda: torch.full((cols + 4,), SENTINEL, dtype=torch.float32, device=DEV)
         out = new()
-        L.call("rv_reduce_rows", L.ptr(partial), L.i32(rows), L.i32(cols), L.ptr(out), L.stream_ptr())
+        L.call("rv_reduce_rows", L.ptr(partial), rows, cols, L.ptr(out), L.stream_ptr())
         _sync()
         assert torch.equal(out[:cols].double(), ref) and bool((out[cols:] == SENTINEL).all()), (rows, cols)
         for with_copy in (True, False):
             out, copy = new(), new()
-            L.call("rv_reduce_rows_count", L.ptr(partial), L.i32(rows), L.i32(cols), L.f32(float(rows * 512 - 1)), L.ptr(out), L.ptr(copy) if with_copy else None,
+            L.call("rv_reduce_rows_count", L.ptr(partial), rows, cols, float(rows * 512 - 1), L.ptr(out), L.ptr(copy) if with_copy else None,
                    L.stream_ptr())
             _sync()
             assert torch.equal(out[:cols].double(), ref) and float(out[cols]) == rows * 512 - 1 and bool((out[cols + 1:] == SENTINEL).all()), (rows, cols)
@@ -705,7 +705,7 @@ def test_chained_passes_on_random_data(c):
     scale, shift = gamma * invstd, beta - mean * gamma * invstd
     form = L.EW_FORM_LEAN if c <= 1024 else L.EW_FORM_OCTET
     ld = c + 8
-    rows = L.load().rv_bn_bwd_rows(L.i64(n))
+    rows = L.load().rv_bn_bwd_rows(n)
     for flags, use_out in ((0, True), (L.BNB_RELU_Z, False), (L.BNB_RELU_Z, True), (0, False)):
         gg = R.masked_grad(dout, out if use_out else None, y, scale, shift, bool(flags))
         xh = R.xhat(y, mean, invstd)
@@ -714,14 +714,14 @@ def test_chained_passes_on_random_data(c):
         assert _info(L.EW_PASS_BWD_REDUCE, n, c, (ld, ld, ld), use_out)[0] == form and _info(L.EW_PASS_BWD_FINALIZE, rows, c)[0] == L.EW_FORM_FUSED_FINALIZE
         assert _info(L.EW_PASS_BWD_APPLY, n, c, (ld, ld, ld, 2 * c, 0), use_out, False, flags)[:2] == (form, 0)
         partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, c), dtype=torch.float32, device=DEV)
-        common = (L.i64(n), L.i32(c), L.ptr(dout), L.i32(ld), L.ptr(out) if use_out else None, L.i32(ld), L.ptr(y), L.i32(ld), L.ptr(scale), L.ptr(shift),
+        common = (n, c, L.ptr(dout), ld, L.ptr(out) if use_out else None, ld, L.ptr(y), ld, L.ptr(scale), L.ptr(shift),
                   L.ptr(mean), L.ptr(invstd))
-        L.call("rv_bn_bwd_reduce", *common, L.i32(flags), L.ptr(partial), L.stream_ptr())
+        L.call("rv_bn_bwd_reduce", *common, flags, L.ptr(partial), L.stream_ptr())
         dgamma, dbeta, coef = torch.empty(c, device=DEV), torch.empty(c, device=DEV), torch.empty((3, c), device=DEV)
-        L.call("rv_bn_bwd_finalize", L.ptr(partial), L.i32(rows), L.i32(c), L.i64(n), L.ptr(gamma), L.ptr(invstd), L.ptr(dgamma), L.ptr(dbeta), L.i32(0),
+        L.call("rv_bn_bwd_finalize", L.ptr(partial), rows, c, n, L.ptr(gamma), L.ptr(invstd), L.ptr(dgamma), L.ptr(dbeta), 0,
                L.ptr(coef), L.stream_ptr())
         dy = _Out(n, c, torch.bfloat16)
-        L.call("rv_bn_bwd_apply", *common, L.ptr(coef), L.i32(flags), L.ptr(dy.view), L.i32(dy.ld), None, L.i32(0), L.stream_ptr())
+        L.call("rv_bn_bwd_apply", *common, L.ptr(coef), flags, L.ptr(dy.view), dy.ld, None, 0, L.stream_ptr())
         _sync()
         assert rel_err(dbeta, s0) < 1e-5 and rel_err(dgamma, s1) < 1e-5
         assert rel_err(dy.view.float(), dy_ref) < 4e-3  # one bf16 ulp
@@ -740,20 +740,20 @@ def test_argument_checks():
     k = L.ptr(consts)
 
     def reduce(n=n, c=c, ld_dout=c, ld_out=c, ld_y=c, out=True):
-        L.call("rv_bn_bwd_reduce", L.i64(n), L.i32(c), L.ptr(src), L.i32(ld_dout), L.ptr(src) if out else None, L.i32(ld_out), L.ptr(src), L.i32(ld_y), k, k, k, k,
-               L.i32(0), L.ptr(partial), L.stream_ptr())
+        L.call("rv_bn_bwd_reduce", n, c, L.ptr(src), ld_dout, L.ptr(src) if out else None, ld_out, L.ptr(src), ld_y, k, k, k, k,
+               0, L.ptr(partial), L.stream_ptr())
 
     def apply(n=n, c=c, ld_dout=c, ld_out=c, ld_y=c, ld_dy=c, ld_dres=c, out=True, dres=True):
-        L.call("rv_bn_bwd_apply", L.i64(n), L.i32(c), L.ptr(src), L.i32(ld_dout), L.ptr(src) if out else None, L.i32(ld_out), L.ptr(src), L.i32(ld_y), k, k, k, k, k,
-               L.i32(0), L.ptr(dst), L.i32(ld_dy), L.ptr(dst) if dres else None, L.i32(ld_dres), L.stream_ptr())
+        L.call("rv_bn_bwd_apply", n, c, L.ptr(src), ld_dout, L.ptr(src) if out else None, ld_out, L.ptr(src), ld_y, k, k, k, k, k,
+               0, L.ptr(dst), ld_dy, L.ptr(dst) if dres else None, ld_dres, L.stream_ptr())
 
     def combine(n=n, c=c, ld_a=c, ld_b=c, ld_out=c, b=True, a_scale=True, a_shift=True, b_scale=True, b_shift=True):
         p = lambda on: k if on else None
-        L.call("rv_ew_combine", L.i64(n), L.i32(c), L.ptr(src), L.i32(ld_a), p(a_scale), p(a_shift), L.ptr(src) if b else None, L.i32(ld_b), p(b_scale and b),
-               p(b_shift and b), L.ptr(dst), L.i32(ld_out), L.i32(0), L.stream_ptr())
+        L.call("rv_ew_combine", n, c, L.ptr(src), ld_a, p(a_scale), p(a_shift), L.ptr(src) if b else None, ld_b, p(b_scale and b),
+               p(b_shift and b), L.ptr(dst), ld_out, 0, L.stream_ptr())
 
     def mask_grad(n=n, c=c, ld_dout=c, ld_out=c, ld_d=c, out=True):
-        L.call("rv_ew_mask_grad", L.i64(n), L.i32(c), L.ptr(src), L.i32(ld_dout), L.ptr(src) if out else None, L.i32(ld_out), L.ptr(dst), L.i32(ld_d), L.i32(0),
+        L.call("rv_ew_mask_grad", n, c, L.ptr(src), ld_dout, L.ptr(src) if out else None, ld_out, L.ptr(dst), ld_d, 0,
                L.stream_ptr())
 
     bad = []
@@ -771,12 +771,12 @@ def test_argument_checks():
         for kw in (dict(n=0), dict(c=0), dict(c=12), dict(c=2056, ld=2056), dict(ld=c - 8), dict(ld=c + 4)):
             nn, cc = kw.get("n", n), kw.get("c", c)
             ld = kw.get("ld", cc)
-            s = (L.ptr(src), L.i32(ld))
+            s = (L.ptr(src), ld)
             with pytest.raises(L.RvError):
                 if name.endswith("reduce_pair"):
-                    L.call(name, L.i64(nn), L.i32(cc), *s, *s, *s, k, k, *s, k, k, L.ptr(partial), L.ptr(partial), L.stream_ptr())
+                    L.call(name, nn, cc, *s, *s, *s, k, k, *s, k, k, L.ptr(partial), L.ptr(partial), L.stream_ptr())
                 else:
-                    L.call(name, L.i64(nn), L.i32(cc), *s, *s, *s, k, k, k, L.ptr(dst), L.i32(ld), *s, k, k, k, L.ptr(dst), L.i32(ld), L.stream_ptr())
+                    L.call(name, nn, cc, *s, *s, *s, k, k, k, L.ptr(dst), ld, *s, k, k, k, L.ptr(dst), ld, L.stream_ptr())
     _sync()
     assert bool((dst == SENTINEL).all()) and bool((partial == SENTINEL).all()), "a rejected call launched something"
     # an optional tensor that is NOT given may carry any pitch (the engine passes 0)

@@ -204,14 +204,14 @@ def test_pos_modulate_forward_equals_the_two_kernels(N, H, W, C, tag):
     with L.operand(tag):
         h1 = torch.empty((P, C), dtype=dt, device=DEV)
         y2 = torch.empty((P, C), dtype=dt, device=DEV)
-        L.call("rv_pos_forward", L.ptr(rel), L.i32(32), L.i32(3), L.i64(P), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1), L.ptr(w2), L.i32(C),
+        L.call("rv_pos_forward", L.ptr(rel), 32, 3, P, L.ptr(w1), 32, L.ptr(s1), L.ptr(t1), L.ptr(w2), C,
                L.ptr(h1), L.ptr(y2), None, L.stream_ptr())
         want = torch.full((N * H * W, 9 * C), float("nan"), dtype=dt, device=DEV)
-        L.call("rv_meta_modulate", L.ptr(y2), L.ptr(s2), L.ptr(t2), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.i32(C), L.ptr(want),
+        L.call("rv_meta_modulate", L.ptr(y2), L.ptr(s2), L.ptr(t2), L.ptr(feat), C, N, H, W, C, L.ptr(want),
                L.stream_ptr())
         got = torch.full((N * H * W, 9 * C), float("nan"), dtype=dt, device=DEV)
-        L.call("rv_pos_modulate_forward", L.ptr(rel), L.i32(32), L.i32(3), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1), L.ptr(w2), L.i32(C),
-               L.ptr(s2), L.ptr(t2), L.ptr(feat), L.i32(C), L.i32(N), L.i32(H), L.i32(W), L.ptr(got), L.stream_ptr())
+        L.call("rv_pos_modulate_forward", L.ptr(rel), 32, 3, L.ptr(w1), 32, L.ptr(s1), L.ptr(t1), L.ptr(w2), C,
+               L.ptr(s2), L.ptr(t2), L.ptr(feat), C, N, H, W, L.ptr(got), L.stream_ptr())
         torch.cuda.synchronize()
     assert not bool(torch.isnan(want.float()).any()) and float(want.float().abs().max()) > 0
     a, b = got.float().cpu(), want.float().cpu()

@@ -229,7 +229,7 @@ def test_range_partition_operand_is_exact():
     f_d, c_d, m_d = feats.to(DEV), cart.to(DEV), mask.to(DEV).view(torch.uint8)
     lo = (ctypes.c_float * 6)(*[float(v) for v in lower.flatten()])
     hi = (ctypes.c_float * 6)(*[float(v) for v in upper.flatten()])
-    L.call("rv_range_partition", L.ptr(f_d), L.ptr(c_d), L.ptr(m_d), L.i32(N), L.i32(C), L.i32(H), L.i32(W), lo, hi, L.i32(6), L.ptr(out), L.i32(ld), L.stream_ptr())
+    L.call("rv_range_partition", L.ptr(f_d), L.ptr(c_d), L.ptr(m_d), N, C, H, W, lo, hi, 6, L.ptr(out), ld, L.stream_ptr())
     got = out.cpu()
     assert torch.equal(got[..., : 6 * C].permute(0, 3, 1, 2).contiguous().view(torch.int16), want.contiguous().view(torch.int16))
     assert not got[..., 6 * C :].float().any()
@@ -618,9 +618,9 @@ def test_pos_forward_kernel_vs_fp32(P, C):
     rel, w1, w2, s1, t1 = (x.to(DEV) for x in (rel, w1, w2, s1, t1))
     h1 = torch.full((P, C), float("nan"), dtype=torch.bfloat16, device=DEV)
     y2 = torch.full((P, C), float("nan"), dtype=torch.bfloat16, device=DEV)
-    rows = L.load().rv_pos_forward_rows(L.i64(P))
+    rows = L.load().rv_pos_forward_rows(P)
     partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, C), float("nan"), dtype=torch.float32, device=DEV)
-    L.call("rv_pos_forward", L.ptr(rel), L.i32(32), L.i32(3), L.i64(P), L.ptr(w1), L.i32(32), L.ptr(s1), L.ptr(t1), L.ptr(w2), L.i32(C),
+    L.call("rv_pos_forward", L.ptr(rel), 32, 3, P, L.ptr(w1), 32, L.ptr(s1), L.ptr(t1), L.ptr(w2), C,
            L.ptr(h1), L.ptr(y2), L.ptr(partial), L.stream_ptr())
     torch.cuda.synchronize()
     want_h1 = torch.relu((rel[:, :3].float() @ w1[:, :3].float().t()) * s1 + t1)

@@ -95,21 +95,21 @@ class _Device:
     def head(self):
         from range_view_3d_detection_amd import _lib as L
 
-        return (L.i64(self.P), L.i32(self.c), L.ptr(self.y), L.i32(self.ld_y), L.ptr(self.dY), L.i32(self.ld_dy), L.ptr(self.wp),
+        return (self.P, self.c, L.ptr(self.y), self.ld_y, L.ptr(self.dY), self.ld_dy, L.ptr(self.wp),
                 *[L.ptr(v) for v in self.vec])
 
     def sums(self, relu, with_dw):
         """-> (rows, partial [rows + scratch][2][c] on the CPU, dW [32][c] or None, dw_partial tail still NaN)"""
         from range_view_3d_detection_amd import _lib as L
 
-        rows = L.load().rv_head_final_bwd_rows(L.i64(self.P))
+        rows = L.load().rv_head_final_bwd_rows(self.P)
         partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, self.c), NAN, dtype=torch.float32, device=DEV)
         dwp = torch.full((rows + L.STATS_SCRATCH_ROWS, 32 * self.c), NAN, dtype=torch.float32, device=DEV) if with_dw else None
-        L.call("rv_head_final_bwd_sums", *self.head(), L.i32(relu), L.ptr(partial), L.ptr(dwp), L.stream_ptr())
+        L.call("rv_head_final_bwd_sums", *self.head(), relu, L.ptr(partial), L.ptr(dwp), L.stream_ptr())
         dw, tail = None, True
         if with_dw:
             dw = torch.full((32, self.c), NAN, dtype=torch.float32, device=DEV)
-            L.call("rv_reduce_rows", L.ptr(dwp), L.i32(rows), L.i32(32 * self.c), L.ptr(dw), L.stream_ptr())
+            L.call("rv_reduce_rows", L.ptr(dwp), rows, 32 * self.c, L.ptr(dw), L.stream_ptr())
             torch.cuda.synchronize()
             assert bool(torch.isfinite(dwp[:rows]).all())
             dw, tail = dw.cpu(), bool(torch.isnan(dwp[rows:]).all())
@@ -120,7 +120,7 @@ class _Device:
         from range_view_3d_detection_amd import _lib as L
 
         dy = torch.full((self.P, self.ld_out), NAN, dtype=self.dtype, device=DEV)
-        L.call("rv_head_final_bwd_apply", *self.head(), L.i32(relu), L.ptr(self.coef), L.ptr(dy), L.i32(self.ld_out), L.stream_ptr())
+        L.call("rv_head_final_bwd_apply", *self.head(), relu, L.ptr(self.coef), L.ptr(dy), self.ld_out, L.stream_ptr())
         torch.cuda.synchronize()
         return dy.cpu()
 
@@ -273,12 +273,12 @@ def test_bad_arguments_fail_before_any_launch(what, match):
     partial = torch.full((1 + L.STATS_SCRATCH_ROWS, 2, c), NAN, device=DEV)
     dy = torch.full((P, c), NAN, dtype=torch.bfloat16, device=DEV)
     cc, ld_dy, ld_out = (128 if what == "c" else c), (24 if what == "ld_dy" else 32), (c - 8 if what == "ld_out" else c)
-    head = (L.i64(P), L.i32(cc), L.ptr(y), L.i32(c), L.ptr(dY), L.i32(ld_dy), L.ptr(wp), *[L.ptr(v) for v in vec], L.i32(1))
+    head = (P, cc, L.ptr(y), c, L.ptr(dY), ld_dy, L.ptr(wp), *[L.ptr(v) for v in vec], 1)
     if what != "ld_out":
         with pytest.raises(L.RvError, match=match):
             L.call("rv_head_final_bwd_sums", *head, L.ptr(None if what == "partial" else partial), None, L.stream_ptr())
     if what != "partial":
         with pytest.raises(L.RvError, match=match):
-            L.call("rv_head_final_bwd_apply", *head, L.ptr(coef), L.ptr(dy), L.i32(ld_out), L.stream_ptr())
+            L.call("rv_head_final_bwd_apply", *head, L.ptr(coef), L.ptr(dy), ld_out, L.stream_ptr())
     torch.cuda.synchronize()
     assert bool(torch.isnan(partial).all()) and bool(torch.isnan(dy).all())

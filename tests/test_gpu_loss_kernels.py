@@ -141,9 +141,9 @@ class _Dev:
         B, H, W = e.shape
         lg, rg, rest = self.inp[0], self.inp[1], self.inp[2:]
         self.coding = (ctypes.c_float * 8)(*[float(c) for c in p.coding_weights])
-        return (L.ptr(lg), L.i32(ld_logits or e.ld_logits), L.ptr(rg), L.i32(ld_reg or e.ld_reg), *[L.ptr(t) for t in rest], L.ptr(self.nobj),
-                L.i32(B), L.i32(e.n_cls), L.i32(H), L.i32(W), self.coding, L.f32(p.cls_weight), L.f32(p.reg_weight), L.f32(p.smoothing), L.f32(p.sigma),
-                L.f32(p.alpha), L.f32(p.gamma), L.i32(1 if p.az_inv else 0))
+        return (L.ptr(lg), ld_logits or e.ld_logits, L.ptr(rg), ld_reg or e.ld_reg, *[L.ptr(t) for t in rest], L.ptr(self.nobj),
+                B, e.n_cls, H, W, self.coding, p.cls_weight, p.reg_weight, p.smoothing, p.sigma,
+                p.alpha, p.gamma, 1 if p.az_inv else 0)
 
 
 def _params(p):
@@ -162,7 +162,7 @@ def _run_one(d: _Dev, p, grad_scale=1.0, device_factor=1.0):
     rows = sums.body(1, R.SUMS_LEN)
     if device_factor != 1.0:
         sums.t[15] = device_factor
-    L.call("rv_detection_loss_backward", *args, L.ptr(sums.t), L.f32(grad_scale), L.ptr(d.d_l.t), L.ptr(d.d_r.t), L.stream_ptr())
+    L.call("rv_detection_loss_backward", *args, L.ptr(sums.t), grad_scale, L.ptr(d.d_l.t), L.ptr(d.d_r.t), L.stream_ptr())
     torch.cuda.synchronize()
     return rows, sums
 
@@ -177,17 +177,17 @@ def _run_table(devs, p, grad_scale=1.0, device_factor=1.0):
     maps = (ctypes.c_void_p * n)(*[d.aff.data_ptr() for d in devs]) if aff else None
     tail = (L.ptr(sums.t),)
     if aff:
-        L.call("rv_detection_loss_multilevel_forward_aff", table, L.i32(n), ctypes.byref(params), maps, *tail, L.stream_ptr())
+        L.call("rv_detection_loss_multilevel_forward_aff", table, n, ctypes.byref(params), maps, *tail, L.stream_ptr())
     else:
-        L.call("rv_detection_loss_multilevel_forward", table, L.i32(n), ctypes.byref(params), *tail, L.stream_ptr())
+        L.call("rv_detection_loss_multilevel_forward", table, n, ctypes.byref(params), *tail, L.stream_ptr())
     torch.cuda.synchronize()
     rows = sums.body(n + 1, R.SUMS_LEN)
     if device_factor != 1.0:
         sums.t[n * R.SUMS_LEN + 15] = device_factor
     if aff:
-        L.call("rv_detection_loss_multilevel_backward_aff", table, L.i32(n), ctypes.byref(params), maps, *tail, L.f32(grad_scale), L.stream_ptr())
+        L.call("rv_detection_loss_multilevel_backward_aff", table, n, ctypes.byref(params), maps, *tail, grad_scale, L.stream_ptr())
     else:
-        L.call("rv_detection_loss_multilevel_backward", table, L.i32(n), ctypes.byref(params), *tail, L.f32(grad_scale), L.stream_ptr())
+        L.call("rv_detection_loss_multilevel_backward", table, n, ctypes.byref(params), *tail, grad_scale, L.stream_ptr())
     torch.cuda.synchronize()
     return rows, sums
 
@@ -295,7 +295,7 @@ def test_one_entry_row_forms(i, dims):
 @pytest.mark.parametrize("name", list(R.OPTIONS))
 def test_options(name, form):
     p = R.OPTIONS[name]
-    quarter = R.f32(p.sigma) == 0.25
+    quarter = R.fp32(p.sigma) == 0.25
     e = R.make_entry(500 + form[0], 2, 5, 67, *form, underflow=quarter)
     ref, _, _ = _one(e, p, f"{name}, {form}")
     er = ref.entries[0]
@@ -382,7 +382,7 @@ def test_entry_tables(kind):
     ref, devs, rows = _table(entries, p, kind, **kw)
     if kind.startswith("three"):
         assert entries[1].num_objects == 0 and float(rows[1, 3]) == 0 and float(rows[0, 3]) > 20 and float(rows[2, 3]) > 20
-        assert float(rows[0, 13]) == float(rows[0, 3]) + float(rows[2, 3]) + R.f32(p.smoothing)  # the GLOBAL count, not the entry's own
+        assert float(rows[0, 13]) == float(rows[0, 3]) + float(rows[2, 3]) + R.fp32(p.smoothing)  # the GLOBAL count, not the entry's own
     if kind == "one":  # "with one entry every tensor and row 0 equal the one-level entry points' results"
         d = _Dev(entries[0])
         rows1, _ = _run_one(d, p)
@@ -426,28 +426,28 @@ def test_refusals():
     sums = _Buf(2 * R.SUMS_LEN, torch.float64, guard=R.SUMS_LEN)
     outs = list(d.outputs()) + [sums]
     st = L.stream_ptr()
-    fwd_tail, bwd_tail = (L.ptr(sums.t), L.ptr(d.soft.t), L.ptr(d.fg.t), st), (L.ptr(sums.t), L.f32(1.0), L.ptr(d.d_l.t), L.ptr(d.d_r.t), st)
+    fwd_tail, bwd_tail = (L.ptr(sums.t), L.ptr(d.soft.t), L.ptr(d.fg.t), st), (L.ptr(sums.t), 1.0, L.ptr(d.d_l.t), L.ptr(d.d_r.t), st)
     for what, kw, match in (("ld_logits < n_cls", dict(ld_logits=4), "strides"), ("ld_reg = 10", dict(ld_reg=10), "strides")):
         _refused(what, "rv_detection_loss_forward", d.one_level_args(p, **kw) + fwd_tail, outs, match)
         _refused(what, "rv_detection_loss_backward", d.one_level_args(p, **kw) + bwd_tail, outs, match)
         table = (L.LossEntry * 1)(d.struct(**kw))
-        _refused(what, "rv_detection_loss_multilevel_forward", (table, L.i32(1), ctypes.byref(_params(p)), L.ptr(sums.t), st), outs, match)
-        _refused(what, "rv_detection_loss_multilevel_backward", (table, L.i32(1), ctypes.byref(_params(p)), L.ptr(sums.t), L.f32(1.0), st), outs, match)
-    _refused("null d_logits", "rv_detection_loss_backward", d.one_level_args(p) + (L.ptr(sums.t), L.f32(1.0), None, L.ptr(d.d_r.t), st), outs, "null gradient")
-    _refused("null d_regressands", "rv_detection_loss_backward", d.one_level_args(p) + (L.ptr(sums.t), L.f32(1.0), L.ptr(d.d_l.t), None, st), outs, "null gradient")
+        _refused(what, "rv_detection_loss_multilevel_forward", (table, 1, ctypes.byref(_params(p)), L.ptr(sums.t), st), outs, match)
+        _refused(what, "rv_detection_loss_multilevel_backward", (table, 1, ctypes.byref(_params(p)), L.ptr(sums.t), 1.0, st), outs, match)
+    _refused("null d_logits", "rv_detection_loss_backward", d.one_level_args(p) + (L.ptr(sums.t), 1.0, None, L.ptr(d.d_r.t), st), outs, "null gradient")
+    _refused("null d_regressands", "rv_detection_loss_backward", d.one_level_args(p) + (L.ptr(sums.t), 1.0, L.ptr(d.d_l.t), None, st), outs, "null gradient")
     table = (L.LossEntry * 17)(*[d.struct() for _ in range(17)])
     maps = (ctypes.c_void_p * 17)(*[d.aff.data_ptr()] * 17)
     params = _params(p)
     for n in (0, 17):
-        _refused(f"{n} entries", "rv_detection_loss_multilevel_forward", (table, L.i32(n), ctypes.byref(params), L.ptr(sums.t), st), outs, "entries")
-        _refused(f"{n} entries", "rv_detection_loss_multilevel_backward", (table, L.i32(n), ctypes.byref(params), L.ptr(sums.t), L.f32(1.0), st), outs, "entries")
-        _refused(f"{n} entries", "rv_detection_loss_multilevel_forward_aff", (table, L.i32(n), ctypes.byref(params), maps, L.ptr(sums.t), st), outs, "entries")
-        _refused(f"{n} entries", "rv_detection_loss_multilevel_backward_aff", (table, L.i32(n), ctypes.byref(params), maps, L.ptr(sums.t), L.f32(1.0), st), outs, "entries")
+        _refused(f"{n} entries", "rv_detection_loss_multilevel_forward", (table, n, ctypes.byref(params), L.ptr(sums.t), st), outs, "entries")
+        _refused(f"{n} entries", "rv_detection_loss_multilevel_backward", (table, n, ctypes.byref(params), L.ptr(sums.t), 1.0, st), outs, "entries")
+        _refused(f"{n} entries", "rv_detection_loss_multilevel_forward_aff", (table, n, ctypes.byref(params), maps, L.ptr(sums.t), st), outs, "entries")
+        _refused(f"{n} entries", "rv_detection_loss_multilevel_backward_aff", (table, n, ctypes.byref(params), maps, L.ptr(sums.t), 1.0, st), outs, "entries")
     no_grad = (L.LossEntry * 1)(d.struct(d_l=False))
-    _refused("null d_logits in the table", "rv_detection_loss_multilevel_backward", (no_grad, L.i32(1), ctypes.byref(params), L.ptr(sums.t), L.f32(1.0), st), outs, "null gradient")
-    _refused("null d_logits in the table", "rv_detection_loss_multilevel_backward_aff", (no_grad, L.i32(1), ctypes.byref(params), maps, L.ptr(sums.t), L.f32(1.0), st), outs,
+    _refused("null d_logits in the table", "rv_detection_loss_multilevel_backward", (no_grad, 1, ctypes.byref(params), L.ptr(sums.t), 1.0, st), outs, "null gradient")
+    _refused("null d_logits in the table", "rv_detection_loss_multilevel_backward_aff", (no_grad, 1, ctypes.byref(params), maps, L.ptr(sums.t), 1.0, st), outs,
              "null gradient")
     null_map = (ctypes.c_void_p * 1)(None)
     for m, match in ((None, "null affinity maps"), (null_map, "null affinity map of entry 0")):
-        _refused("null map", "rv_detection_loss_multilevel_forward_aff", (table, L.i32(1), ctypes.byref(params), m, L.ptr(sums.t), st), outs, match)
-        _refused("null map", "rv_detection_loss_multilevel_backward_aff", (table, L.i32(1), ctypes.byref(params), m, L.ptr(sums.t), L.f32(1.0), st), outs, match)
+        _refused("null map", "rv_detection_loss_multilevel_forward_aff", (table, 1, ctypes.byref(params), m, L.ptr(sums.t), st), outs, match)
+        _refused("null map", "rv_detection_loss_multilevel_backward_aff", (table, 1, ctypes.byref(params), m, L.ptr(sums.t), 1.0, st), outs, match)

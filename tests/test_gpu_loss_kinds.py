@@ -99,12 +99,12 @@ def _run(devs, p, kinds: K.Kinds, grad_scale=1.0, device_factor=1.0):
     table = (L.LossEntry * n)(*[d.struct() for d in devs])
     params, kk = T._params(p), _kinds(kinds)
     maps = (ctypes.c_void_p * n)(*[d.aff.data_ptr() for d in devs]) if devs[0].aff is not None else None
-    L.call("rv_detection_loss_table_forward", table, L.i32(n), ctypes.byref(params), ctypes.byref(kk), maps, L.ptr(sums.t), L.stream_ptr())
+    L.call("rv_detection_loss_table_forward", table, n, ctypes.byref(params), ctypes.byref(kk), maps, L.ptr(sums.t), L.stream_ptr())
     torch.cuda.synchronize()
     rows = sums.body(n + 1, R.SUMS_LEN)
     if device_factor != 1.0:
         sums.t[n * R.SUMS_LEN + 15] = device_factor
-    L.call("rv_detection_loss_table_backward", table, L.i32(n), ctypes.byref(params), ctypes.byref(kk), maps, L.ptr(sums.t), L.f32(grad_scale), L.stream_ptr())
+    L.call("rv_detection_loss_table_backward", table, n, ctypes.byref(params), ctypes.byref(kk), maps, L.ptr(sums.t), grad_scale, L.stream_ptr())
     torch.cuda.synchronize()
     return rows, sums
 
@@ -276,7 +276,7 @@ def test_backward_factors(grad_scale, device_factor, form):
     ref, devs, _ = _case([e], CLS_PARAMS[K.CLS_PENALTY_REDUCED], kinds, f"grad_scale {grad_scale}, sums[15] {device_factor}, {form}",
                          grad_scale=grad_scale, device_factor=device_factor)
     plain = K.loss_table([e], CLS_PARAMS[K.CLS_PENALTY_REDUCED], kinds)
-    f = R.f32(grad_scale) * device_factor  # (exact in fp64: the reference's gradients carry the product once)
+    f = R.fp32(grad_scale) * device_factor  # (exact in fp64: the reference's gradients carry the product once)
     assert torch.allclose(ref.entries[0].d_regressands, plain.entries[0].d_regressands * f, rtol=1e-13, atol=0.0)
 
 
@@ -311,7 +311,7 @@ def test_entry_tables(kind):
     assert float(rows[n, 12]) == n * float(rows[0, 12]) and float(rows[n, 13]) == n * float(rows[0, 13])
     if kind == "three":
         assert entries[1].num_objects == 0 and float(rows[1, 3]) == 0 and float(rows[0, 3]) > 20 and float(rows[2, 3]) > 20
-        assert float(rows[0, 13]) == float(rows[0, 3]) + float(rows[2, 3]) + R.f32(p.smoothing)
+        assert float(rows[0, 13]) == float(rows[0, 3]) + float(rows[2, 3]) + R.fp32(p.smoothing)
 
 
 def test_affinity_map_table():
@@ -363,21 +363,21 @@ def test_refusals():
     for m in (None, maps):
         for (c, r, v), match in bad:
             kk = L.LossKinds(c, r, v)
-            T._refused(f"kinds {c, r, v}", "rv_detection_loss_table_forward", (table, L.i32(1), ctypes.byref(params), ctypes.byref(kk), m, L.ptr(sums.t), st), outs, match)
-            T._refused(f"kinds {c, r, v}", "rv_detection_loss_table_backward", (table, L.i32(1), ctypes.byref(params), ctypes.byref(kk), m, L.ptr(sums.t), L.f32(1.0), st),
+            T._refused(f"kinds {c, r, v}", "rv_detection_loss_table_forward", (table, 1, ctypes.byref(params), ctypes.byref(kk), m, L.ptr(sums.t), st), outs, match)
+            T._refused(f"kinds {c, r, v}", "rv_detection_loss_table_backward", (table, 1, ctypes.byref(params), ctypes.byref(kk), m, L.ptr(sums.t), 1.0, st),
                        outs, match)
-        T._refused("null kinds", "rv_detection_loss_table_forward", (table, L.i32(1), ctypes.byref(params), None, m, L.ptr(sums.t), st), outs, "null kinds")
-        T._refused("null kinds", "rv_detection_loss_table_backward", (table, L.i32(1), ctypes.byref(params), None, m, L.ptr(sums.t), L.f32(1.0), st), outs, "null kinds")
+        T._refused("null kinds", "rv_detection_loss_table_forward", (table, 1, ctypes.byref(params), None, m, L.ptr(sums.t), st), outs, "null kinds")
+        T._refused("null kinds", "rv_detection_loss_table_backward", (table, 1, ctypes.byref(params), None, m, L.ptr(sums.t), 1.0, st), outs, "null kinds")
     ok = L.LossKinds(1, 1, 0.5)
     big = (L.LossEntry * 17)(*[d.struct() for _ in range(17)])
     for n in (0, 17):
-        T._refused(f"{n} entries", "rv_detection_loss_table_forward", (big, L.i32(n), ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), st), outs, "entries")
-        T._refused(f"{n} entries", "rv_detection_loss_table_backward", (big, L.i32(n), ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), L.f32(1.0), st), outs,
+        T._refused(f"{n} entries", "rv_detection_loss_table_forward", (big, n, ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), st), outs, "entries")
+        T._refused(f"{n} entries", "rv_detection_loss_table_backward", (big, n, ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), 1.0, st), outs,
                    "entries")
     no_grad = (L.LossEntry * 1)(d.struct(d_l=False))
-    T._refused("null d_logits", "rv_detection_loss_table_backward", (no_grad, L.i32(1), ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), L.f32(1.0), st), outs,
+    T._refused("null d_logits", "rv_detection_loss_table_backward", (no_grad, 1, ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), 1.0, st), outs,
                "null gradient")
     null_map = (ctypes.c_void_p * 1)(None)
-    T._refused("null map", "rv_detection_loss_table_forward", (table, L.i32(1), ctypes.byref(params), ctypes.byref(ok), null_map, L.ptr(sums.t), st), outs, "null affinity map of entry 0")
-    T._refused("bad stride", "rv_detection_loss_table_forward", ((L.LossEntry * 1)(d.struct(ld_reg=10)), L.i32(1), ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), st),
+    T._refused("null map", "rv_detection_loss_table_forward", (table, 1, ctypes.byref(params), ctypes.byref(ok), null_map, L.ptr(sums.t), st), outs, "null affinity map of entry 0")
+    T._refused("bad stride", "rv_detection_loss_table_forward", ((L.LossEntry * 1)(d.struct(ld_reg=10)), 1, ctypes.byref(params), ctypes.byref(ok), None, L.ptr(sums.t), st),
                outs, "strides")

@@ -404,7 +404,7 @@ def test_rotated_iou_matches_oracle():
     ref = onms.pairwise_iou(rect.numpy(), rect.numpy())
     rd = rect.to(DEV)
     out = torch.empty((200, 200), dtype=torch.float32, device=DEV)
-    L.call("rv_rotated_iou", L.ptr(rd), L.i64(200), L.ptr(rd), L.i64(200), L.ptr(out), L.stream_ptr())
+    L.call("rv_rotated_iou", L.ptr(rd), 200, L.ptr(rd), 200, L.ptr(out), L.stream_ptr())
     assert np.array_equal(out.cpu().numpy(), ref)
     assert abs(float(out.diagonal().min()) - 1.0) < 1e-5 and float(out.max()) <= 1.0 + 1e-6
 

@@ -51,8 +51,8 @@ def _targets_through_the_c_abi(cart, annotations, case):
             res[s][t] = tg
     nobj = torch.full((n_l * n_t,), SENTINEL, dtype=torch.int32, device=DEV)
     scratch = torch.full((3 * n_l * max(m, 1),), SENTINEL, dtype=torch.int32, device=DEV)
-    L.call("rv_assign_targets_multilevel", L.ptr(cub_d) if m else None, L.i32(m), L.ptr(off_d), L.ptr(cart32), L.i32(B), L.i32(H), L.i32(W), L.i32(n_l),
-           levels, L.i32(n_t), (ctypes.c_int32 * n_t)(*range(n_t)), (ctypes.c_int32 * n_t)(*classes), L.i32(1), L.ptr(scratch), outs, L.ptr(nobj),
+    L.call("rv_assign_targets_multilevel", L.ptr(cub_d) if m else None, m, L.ptr(off_d), L.ptr(cart32), B, H, W, n_l,
+           levels, n_t, (ctypes.c_int32 * n_t)(*range(n_t)), (ctypes.c_int32 * n_t)(*classes), 1, L.ptr(scratch), outs, L.ptr(nobj),
            L.stream_ptr())
     torch.cuda.synchronize()
     return res, nobj.cpu()

@@ -278,8 +278,8 @@ def test_an_all_covering_roi_changes_nothing():
                torch.full((n, 3), 7.0, dtype=torch.float32, device=DEV), torch.full((n,), 7, dtype=torch.int32, device=DEV),
                torch.full((m,), 7, dtype=torch.uint8, device=DEV)]
         flags = (ctypes.c_void_p(0),) if name == "rv_eval_match_roi" else ()
-        L.call(name, L.ptr(dts), L.ptr(dt_order), L.ptr(dt_off), L.i64(n), L.ptr(gts), L.ptr(valid), L.ptr(gt_order), L.ptr(gt_off), L.i64(m),
-               L.i32(n_seg), thr, L.i32(4), L.f64(2.0), L.f64(150.0), L.i32(100), *flags, *[L.ptr(t) for t in out], L.stream_ptr())
+        L.call(name, L.ptr(dts), L.ptr(dt_order), L.ptr(dt_off), n, L.ptr(gts), L.ptr(valid), L.ptr(gt_order), L.ptr(gt_off), m,
+               n_seg, thr, 4, 2.0, 150.0, 100, *flags, *[L.ptr(t) for t in out], L.stream_ptr())
         results.append([t.cpu().numpy() for t in out])
     for a, b in zip(*results):
         assert np.array_equal(a, b, equal_nan=True)

@@ -205,7 +205,7 @@ def _run_modulate(D, layout, what):
     geo = _Out(D.px, 9 * D.c, D.dtype)
     ref = S.modulate(D.pos, D.scale, D.shift, D.feat, D.dims)
     _fits_fp32(ref, what)
-    _call(D.dtype, "rv_meta_modulate", *_ptrs(D.pos, D.scale, D.shift, feat), L.i32(ld_feat), L.i32(n), L.i32(h), L.i32(w), L.i32(D.c), L.ptr(geo.view), L.stream_ptr())
+    _call(D.dtype, "rv_meta_modulate", *_ptrs(D.pos, D.scale, D.shift, feat), ld_feat, n, h, w, D.c, L.ptr(geo.view), L.stream_ptr())
     _sync()
     geo.check(ref, what + " geo")
     border = ~D.inside.expand(D.px, 9, D.c).reshape(D.px, 9 * D.c)
@@ -220,8 +220,8 @@ def _run_bwd(D, layout, what):
     dpos, dfeat = _Out(D.px * 9, D.c, D.dtype), _Out(D.px, D.c, D.dtype, layout)
     ref_dpos, ref_dfeat = S.modulate_bwd(D.dgeo, D.pos, D.scale, D.shift, D.feat, D.dims)
     _fits_fp32(ref_dpos, what), _fits_fp32(ref_dfeat, what)
-    _call(D.dtype, "rv_meta_modulate_bwd", *_ptrs(D.dgeo, D.pos, D.scale, D.shift, feat), L.i32(ld_feat), L.i32(n), L.i32(h), L.i32(w), L.i32(D.c),
-          L.ptr(dpos.view), L.ptr(dfeat.view), L.i32(dfeat.ld), L.stream_ptr())
+    _call(D.dtype, "rv_meta_modulate_bwd", *_ptrs(D.dgeo, D.pos, D.scale, D.shift, feat), ld_feat, n, h, w, D.c,
+          L.ptr(dpos.view), L.ptr(dfeat.view), dfeat.ld, L.stream_ptr())
     _sync()
     dpos.check(ref_dpos, what + " dpos_act")
     dfeat.check(ref_dfeat, what + " dfeat")
@@ -232,7 +232,7 @@ def _run_bwd_sums(D, layout, what, sums_exact=True):
     L = _L()
     n, h, w = D.dims
     feat, ld_feat = _place(D.feat, layout)
-    rows = L.load().rv_meta_bwd_rows(L.i32(n), L.i32(h), L.i32(w))
+    rows = L.load().rv_meta_bwd_rows(n, h, w)
     assert rows == (D.px + 511) // 512
     z = S.modulate_z(D.dgeo, D.pos, D.scale, D.shift, D.feat, D.dims)
     xh = R.xhat(D.pos, D.mean, D.invstd)
@@ -247,8 +247,8 @@ def _run_bwd_sums(D, layout, what, sums_exact=True):
         assert bool((on_zero & live).any()), what + ": no gate exactly on 0 (data)"
     dfeat = _Out(D.px, D.c, D.dtype, layout)
     partial = _nan(rows + L.STATS_SCRATCH_ROWS, 2, D.c)
-    _call(D.dtype, "rv_meta_modulate_bwd_sums", *_ptrs(D.dgeo, D.pos, D.scale, D.shift, D.mean, D.invstd, feat), L.i32(ld_feat), L.i32(n), L.i32(h), L.i32(w),
-          L.i32(D.c), L.ptr(dfeat.view), L.i32(dfeat.ld), L.ptr(partial), L.stream_ptr())
+    _call(D.dtype, "rv_meta_modulate_bwd_sums", *_ptrs(D.dgeo, D.pos, D.scale, D.shift, D.mean, D.invstd, feat), ld_feat, n, h, w,
+          D.c, L.ptr(dfeat.view), dfeat.ld, L.ptr(partial), L.stream_ptr())
     _sync()
     dfeat.check(ref_dfeat, what + " dfeat (fused)")
     if sums_exact:
@@ -265,8 +265,8 @@ def _run_bwd_apply(D, layout, what):
     dy = _Out(D.px * 9, D.c, D.dtype)
     ref = S.modulate_bwd_apply(D.dgeo, D.pos, D.scale, D.shift, D.mean, D.invstd, D.coef, D.feat, D.dims)
     _fits_fp32(ref, what)
-    _call(D.dtype, "rv_meta_modulate_bwd_apply", *_ptrs(D.dgeo, D.pos, D.scale, D.shift, D.mean, D.invstd, D.coef, feat), L.i32(ld_feat), L.i32(n), L.i32(h),
-          L.i32(w), L.i32(D.c), L.ptr(dy.view), L.stream_ptr())
+    _call(D.dtype, "rv_meta_modulate_bwd_apply", *_ptrs(D.dgeo, D.pos, D.scale, D.shift, D.mean, D.invstd, D.coef, feat), ld_feat, n, h,
+          w, D.c, L.ptr(dy.view), L.stream_ptr())
     _sync()
     dy.check(ref, what + " dy")
     # a tap outside the image: dy = coef0 (0 - coef1 - xhat coef2), spelled out
@@ -340,7 +340,7 @@ def test_relative(dims, dtype):
     assert float(cart.abs().max()) * 2 < 6.0e4
     ref = S.relative(cart, dtype)
     rel = _Out(n * h * w * 9, 32, dtype)
-    _call(dtype, "rv_meta_relative", L.ptr(cart), L.i32(n), L.i32(h), L.i32(w), L.ptr(rel.view), L.stream_ptr())
+    _call(dtype, "rv_meta_relative", L.ptr(cart), n, h, w, L.ptr(rel.view), L.stream_ptr())
     _sync()
     rel.check(ref, f"relative {dims} {dtype}")
     if n * h * w > 1:
@@ -408,9 +408,9 @@ def _moments(D, v, ld_v, n, what, extra=0):
     cols = D.cin_pad + D.cin_pad ** 2
     m1, m2 = S.smallk_moments(v, D.cin_pad)
     _row_sums_exact(float(v[:, :D.cin_pad].abs().max()) ** 2, 257, 1.0, what)  # a moment block covers ceil(n / blocks) <= 257 pixels
-    ws = _ff_bytes(lib.rv_smallk_forward_workspace_bytes(L.i32(D.cin)))
+    ws = _ff_bytes(lib.rv_smallk_forward_workspace_bytes(D.cin))
     mom = _nan(cols + extra, dtype=torch.float64)
-    L.call("rv_smallk_moments", L.ptr(v), L.i32(ld_v), L.i64(n), L.i32(D.cin), L.ptr(mom), L.ptr(ws), L.stream_ptr())
+    L.call("rv_smallk_moments", L.ptr(v), ld_v, n, D.cin, L.ptr(mom), L.ptr(ws), L.stream_ptr())
     _sync()
     want = torch.cat([m1, m2.reshape(-1)])
     assert torch.equal(mom[:cols], want), f"{what}: moments differ at {(mom[:cols] != want).nonzero().flatten().tolist()[:8]}"
@@ -423,10 +423,10 @@ def _forward(D, v, ld_v, n, w, scale, shift, relu, layout, dtype=BF16, moments=N
     L = _L()
     h = _Out(n, D.c, dtype, layout) if want_h else None
     st = stats or {}
-    _call(dtype, "rv_smallk_forward", L.ptr(v), L.i32(ld_v), L.i64(n), L.i32(D.cin), L.ptr(w), L.i32(8), L.i32(D.c), L.ptr(moments), L.i64(count),
-          L.ptr(D.gamma if moments is not None else None), L.ptr(D.beta if moments is not None else None), L.f32(EPS), L.f32(MOM), L.ptr(st.get("rmean")),
-          L.ptr(st.get("rvar")), L.ptr(scale), L.ptr(shift), L.ptr(st.get("mean")), L.ptr(st.get("invstd")), L.i32(1 if relu else 0),
-          L.ptr(h.view) if h else None, L.i32(h.ld if h else D.c), L.stream_ptr())
+    _call(dtype, "rv_smallk_forward", L.ptr(v), ld_v, n, D.cin, L.ptr(w), 8, D.c, L.ptr(moments), count,
+          L.ptr(D.gamma if moments is not None else None), L.ptr(D.beta if moments is not None else None), EPS, MOM, L.ptr(st.get("rmean")),
+          L.ptr(st.get("rvar")), L.ptr(scale), L.ptr(shift), L.ptr(st.get("mean")), L.ptr(st.get("invstd")), 1 if relu else 0,
+          L.ptr(h.view) if h else None, h.ld if h else D.c, L.stream_ptr())
     _sync()
     return h
 
@@ -494,11 +494,11 @@ def _sums(D, n, ld_v, layout, flags, use_out, what):
     _row_sums_exact(float(g.abs().max()) * float(v[:, :D.cin_pad].abs().max()), 512, 1.0, what)
     assert rows_of(n) == (n + 511) // 512
     planes, cols = 2 + D.cin_pad, D.cin_pad + D.cin_pad ** 2
-    ws = _ff_bytes(lib.rv_bn_bwd_smallk_workspace_bytes(L.i64(n), L.i32(D.c), L.i32(D.cin)))
+    ws = _ff_bytes(lib.rv_bn_bwd_smallk_workspace_bytes(n, D.c, D.cin))
     sums, moms = _nan(planes * D.c, dtype=torch.float64), _nan(cols, dtype=torch.float64)
-    L.call("rv_bn_bwd_smallk_sums", L.i64(n), L.i32(D.c), L.ptr(dout), L.i32(ld_dout), L.ptr(out) if use_out else None, L.i32(ld_out if use_out else 0),
-           L.ptr(None if recomp else y), L.i32(0 if recomp else ld_y), *_ptrs(D.scale, D.shift, D.mean, D.invstd), L.i32(flags), L.ptr(v), L.i32(ld_v), L.i32(D.cin),
-           L.ptr(D.w if recomp else None), L.i32(8), L.ptr(sums), L.ptr(moms), L.ptr(ws), L.stream_ptr())
+    L.call("rv_bn_bwd_smallk_sums", n, D.c, L.ptr(dout), ld_dout, L.ptr(out) if use_out else None, ld_out if use_out else 0,
+           L.ptr(None if recomp else y), 0 if recomp else ld_y, *_ptrs(D.scale, D.shift, D.mean, D.invstd), flags, L.ptr(v), ld_v, D.cin,
+           L.ptr(D.w if recomp else None), 8, L.ptr(sums), L.ptr(moms), L.ptr(ws), L.stream_ptr())
     _sync()
     want = torch.cat([s0, s1, r[:D.cin].reshape(-1)])
     got = sums[: (2 + D.cin) * D.c]
@@ -510,7 +510,7 @@ def _sums(D, n, ld_v, layout, flags, use_out, what):
 
 def rows_of(n):
     L = _L()
-    return L.load().rv_bn_bwd_rows(L.i64(n))
+    return L.load().rv_bn_bwd_rows(n)
 
 
 def _grads(D, n, ld_v, what):
@@ -535,24 +535,24 @@ def _grads(D, n, ld_v, what):
         return torch.full((D.c,), SENTINEL, device=DEV), torch.full((D.c,), SENTINEL, device=DEV), torch.full((D.c + 1, D.cin), SENTINEL, device=DEV)
 
     dg, db, dw = outputs()
-    L.call("rv_bn_bwd_smallk_from_sums", L.i32(D.c), L.i32(D.cin), L.ptr(sums), L.ptr(moms), None, L.ptr(D.w_garbage), L.i32(8), *_ptrs(D.gamma, D.mean, D.invstd),
-           L.i64(n), L.ptr(dg), L.ptr(db), L.ptr(dw), L.stream_ptr())
+    L.call("rv_bn_bwd_smallk_from_sums", D.c, D.cin, L.ptr(sums), L.ptr(moms), None, L.ptr(D.w_garbage), 8, *_ptrs(D.gamma, D.mean, D.invstd),
+           n, L.ptr(dg), L.ptr(db), L.ptr(dw), L.stream_ptr())
     _sync()
     check(dg, db, dw[:D.c], None, n, "two calls")
     assert bool((dw[D.c:] == SENTINEL).all())
     # one call
-    ws = _ff_bytes(lib.rv_bn_bwd_smallk_workspace_bytes(L.i64(n), L.i32(D.c), L.i32(D.cin)))
+    ws = _ff_bytes(lib.rv_bn_bwd_smallk_workspace_bytes(n, D.c, D.cin))
     dg1, db1, dw1 = outputs()
-    L.call("rv_bn_bwd_smallk", L.i64(n), L.i32(D.c), L.ptr(D.dout[:n]), L.i32(D.c), None, L.i32(0), None, L.i32(0), *_ptrs(D.scale, D.shift, D.mean, D.invstd),
-           L.i32(flags), L.ptr(v), L.i32(ld_v), L.i32(D.cin), L.ptr(D.w), L.i32(8), L.ptr(D.gamma), None, None, L.i64(n), L.ptr(dg1), L.ptr(db1), L.ptr(dw1), L.ptr(ws),
+    L.call("rv_bn_bwd_smallk", n, D.c, L.ptr(D.dout[:n]), D.c, None, 0, None, 0, *_ptrs(D.scale, D.shift, D.mean, D.invstd),
+           flags, L.ptr(v), ld_v, D.cin, L.ptr(D.w), 8, L.ptr(D.gamma), None, None, n, L.ptr(dg1), L.ptr(db1), L.ptr(dw1), L.ptr(ws),
            L.stream_ptr())
     _sync()
     assert torch.equal(dg1, dg) and torch.equal(db1, db) and torch.equal(dw1, dw), what + ": the one-call form differs from the two-call form"
     # SyncBN: global sums = twice the local ones, the count 2 n read from the device
     gs = torch.cat([2 * s0, 2 * s1, torch.tensor([2.0 * n], dtype=torch.float64, device=DEV)])
     dg2, db2, dw2 = outputs()
-    L.call("rv_bn_bwd_smallk_from_sums", L.i32(D.c), L.i32(D.cin), L.ptr(sums), L.ptr(moms), L.ptr(gs), L.ptr(D.w), L.i32(8), *_ptrs(D.gamma, D.mean, D.invstd),
-           L.i64(-1), L.ptr(dg2), L.ptr(db2), L.ptr(dw2), L.stream_ptr())
+    L.call("rv_bn_bwd_smallk_from_sums", D.c, D.cin, L.ptr(sums), L.ptr(moms), L.ptr(gs), L.ptr(D.w), 8, *_ptrs(D.gamma, D.mean, D.invstd),
+           -1, L.ptr(dg2), L.ptr(db2), L.ptr(dw2), L.stream_ptr())
     _sync()
     check(dg2, db2, dw2[:D.c], torch.stack([2 * s0, 2 * s1]), 2 * n, "SyncBN")
 
@@ -668,7 +668,7 @@ def _run_pos_forward(D, p, cin, ld_rel, with_stats, what, kind="base"):
     h1s = S.stored(h1_ref, dtype)
     step = 2.0 ** -14 if kind == "fine" else 0.5
     assert bool(((h1s / step).frac() == 0).all()) and float((h1s @ D.w2.double().abs().t()).max()) / step < U24
-    rows = L.load().rv_pos_forward_rows(L.i64(p))
+    rows = L.load().rv_pos_forward_rows(p)
     ktm = 128 * 256 // c
     steps = (p + ktm - 1) // ktm
     assert rows == min(256, (p + 127) // 128)
@@ -677,7 +677,7 @@ def _run_pos_forward(D, p, cin, ld_rel, with_stats, what, kind="base"):
         _row_sums_exact(float(y2_ref.abs().max()) ** 2, min(p, per_row), step * step, what)
     h1, y2 = _Out(p, c, dtype), _Out(p, c, dtype)
     partial = _nan(rows + L.STATS_SCRATCH_ROWS, 2, c) if with_stats else None
-    _call(dtype, "rv_pos_forward", L.ptr(rel), L.i32(ld_rel), L.i32(cin), L.i64(p), L.ptr(w1), L.i32(8), L.ptr(D.s1), L.ptr(D.t1), L.ptr(D.w2), L.i32(c),
+    _call(dtype, "rv_pos_forward", L.ptr(rel), ld_rel, cin, p, L.ptr(w1), 8, L.ptr(D.s1), L.ptr(D.t1), L.ptr(D.w2), c,
           L.ptr(h1.view), L.ptr(y2.view), L.ptr(partial), L.stream_ptr())
     _sync()
     h1.check(h1_ref, what + " h1")
@@ -754,8 +754,8 @@ def test_pos_modulate_forward(c, dims, dtype):
     y2s = S.stored(S.pos_forward(rel, D.w1, cin, D.s1, D.t1, D.w2, dtype)[1], dtype)
     assert bool((((y2s * D.s2.double() + D.t2.double()) == 0) & (S.gather9(feat_t.double(), dims).reshape(px * 9, c) != 0)).any()), what + ": no second-layer gate on 0 (data)"
     geo = _Out(px, 9 * c, dtype)
-    _call(dtype, "rv_pos_modulate_forward", L.ptr(rel), L.i32(ld_rel), L.i32(cin), L.ptr(D.w1), L.i32(8), L.ptr(D.s1), L.ptr(D.t1), L.ptr(D.w2), L.i32(c),
-          L.ptr(D.s2), L.ptr(D.t2), L.ptr(feat), L.i32(ld_feat), L.i32(n), L.i32(h), L.i32(w), L.ptr(geo.view), L.stream_ptr())
+    _call(dtype, "rv_pos_modulate_forward", L.ptr(rel), ld_rel, cin, L.ptr(D.w1), 8, L.ptr(D.s1), L.ptr(D.t1), L.ptr(D.w2), c,
+          L.ptr(D.s2), L.ptr(D.t2), L.ptr(feat), ld_feat, n, h, w, L.ptr(geo.view), L.stream_ptr())
     _sync()
     geo.check(ref, what)
     inside = S.gather9(torch.ones(px, 1, dtype=torch.float64, device=DEV), dims) > 0
@@ -797,9 +797,9 @@ def test_pos_backward_sums(c, p):
     _row_sums_exact(float(g.abs().max()) * float(rel[:, :3].abs().max()), min(p, per_row), 1.0, what)
     _row_sums_exact(float(rel[:, :4].abs().max()) ** 2, 257, 1.0, what)
     assert float((dy2.double().abs() @ D.w2s.double().abs().t()).max()) < U24
-    ws = _ff_bytes(lib.rv_bn_bwd_smallk_workspace_bytes(L.i64(p), L.i32(c), L.i32(cin)))
+    ws = _ff_bytes(lib.rv_bn_bwd_smallk_workspace_bytes(p, c, cin))
     sums, moms = _nan(6 * c, dtype=torch.float64), _nan(20, dtype=torch.float64)
-    L.call("rv_pos_backward_sums", L.i64(p), L.i32(c), L.ptr(dy2), L.ptr(D.w2s), L.ptr(rel), L.i32(ld_rel), L.i32(cin), L.ptr(w1), L.i32(8), *_ptrs(D.s1, D.t1, D.mean1, D.invstd1),
+    L.call("rv_pos_backward_sums", p, c, L.ptr(dy2), L.ptr(D.w2s), L.ptr(rel), ld_rel, cin, L.ptr(w1), 8, *_ptrs(D.s1, D.t1, D.mean1, D.invstd1),
            L.ptr(sums), L.ptr(moms), L.ptr(ws), L.stream_ptr())
     _sync()
     want = torch.cat([s0, s1, r.reshape(-1)])
@@ -819,49 +819,49 @@ def test_argument_checks():
     n, h, w = G.dims
     geo, dfeat, dy = _Out(G.px, 72, BF16), _Out(G.px, 8, BF16), _Out(G.px * 9, 8, BF16)
     partial = torch.full((1 + L.STATS_SCRATCH_ROWS, 2, 8), SENTINEL, device=DEV)
-    i32, i64, p_, st = L.i32, L.i64, L.ptr, L.stream_ptr()
+    p_, st = L.ptr, L.stream_ptr()
 
     def modulate(c, ld_feat=8, pos=G.pos):
-        L.call("rv_meta_modulate", p_(pos), p_(G.scale), p_(G.shift), p_(G.feat), i32(ld_feat), i32(n), i32(h), i32(w), i32(c), p_(geo.view), st)
+        L.call("rv_meta_modulate", p_(pos), p_(G.scale), p_(G.shift), p_(G.feat), ld_feat, n, h, w, c, p_(geo.view), st)
 
     def bwd_sums(c, partial_=partial):
-        L.call("rv_meta_modulate_bwd_sums", *_ptrs(G.dgeo, G.pos, G.scale, G.shift, G.mean, G.invstd, G.feat), i32(8), i32(n), i32(h), i32(w), i32(c), p_(dfeat.view),
-               i32(8), p_(partial_), st)
+        L.call("rv_meta_modulate_bwd_sums", *_ptrs(G.dgeo, G.pos, G.scale, G.shift, G.mean, G.invstd, G.feat), 8, n, h, w, c, p_(dfeat.view),
+               8, p_(partial_), st)
 
     def bwd_apply(c, coef=G.coef):
-        L.call("rv_meta_modulate_bwd_apply", *_ptrs(G.dgeo, G.pos, G.scale, G.shift, G.mean, G.invstd, coef, G.feat), i32(8), i32(n), i32(h), i32(w), i32(c), p_(dy.view), st)
+        L.call("rv_meta_modulate_bwd_apply", *_ptrs(G.dgeo, G.pos, G.scale, G.shift, G.mean, G.invstd, coef, G.feat), 8, n, h, w, c, p_(dy.view), st)
 
     D = _SmallK(4, 8, 3, seed=2)
     hh = _Out(4, 8, BF16)
     sums, moms = torch.full((48,), SENTINEL, dtype=torch.float64, device=DEV), torch.full((20,), SENTINEL, dtype=torch.float64, device=DEV)
-    ws = _ff_bytes(L.load().rv_bn_bwd_smallk_workspace_bytes(i64(4), i32(8), i32(3)))
+    ws = _ff_bytes(L.load().rv_bn_bwd_smallk_workspace_bytes(4, 8, 3))
 
     def forward(cin, c=8, v=D.v8):
-        L.call("rv_smallk_forward", p_(v), i32(8), i64(4), i32(cin), p_(D.w), i32(8), i32(c), None, i64(0), None, None, L.f32(EPS), L.f32(MOM), None, None,
-               p_(D.scale), p_(D.shift), None, None, i32(1), p_(hh.view), i32(8), st)
+        L.call("rv_smallk_forward", p_(v), 8, 4, cin, p_(D.w), 8, c, None, 0, None, None, EPS, MOM, None, None,
+               p_(D.scale), p_(D.shift), None, None, 1, p_(hh.view), 8, st)
 
     def smallk_sums(cin, flags, w):
-        L.call("rv_bn_bwd_smallk_sums", i64(4), i32(8), p_(D.dout), i32(8), None, i32(0), p_(D.y), i32(8), *_ptrs(D.scale, D.shift, D.mean, D.invstd), i32(flags),
-               p_(D.v8), i32(8), i32(cin), p_(w), i32(8), p_(sums), p_(moms), p_(ws), st)
+        L.call("rv_bn_bwd_smallk_sums", 4, 8, p_(D.dout), 8, None, 0, p_(D.y), 8, *_ptrs(D.scale, D.shift, D.mean, D.invstd), flags,
+               p_(D.v8), 8, cin, p_(w), 8, p_(sums), p_(moms), p_(ws), st)
 
     def moments(cin, mom=moms):
-        L.call("rv_smallk_moments", p_(D.v8), i32(8), i64(4), i32(cin), p_(mom), p_(ws), st)
+        L.call("rv_smallk_moments", p_(D.v8), 8, 4, cin, p_(mom), p_(ws), st)
 
     P = _Pos(288, 256, 3, seed=3)
     h1, y2 = _Out(288, 256, BF16), _Out(288, 256, BF16)
     feat = torch.zeros(32, 256, dtype=BF16, device=DEV)
     sums_p = torch.full((6 * 256,), SENTINEL, dtype=torch.float64, device=DEV)
-    ws_p = _ff_bytes(L.load().rv_bn_bwd_smallk_workspace_bytes(i64(288), i32(256), i32(3)))
+    ws_p = _ff_bytes(L.load().rv_bn_bwd_smallk_workspace_bytes(288, 256, 3))
 
     def pos_forward(c, cin, rel=P.rel32):
-        L.call("rv_pos_forward", p_(rel), i32(32), i32(cin), i64(288), p_(P.w1), i32(8), p_(P.s1), p_(P.t1), p_(P.w2), i32(c), p_(h1.view), p_(y2.view), None, st)
+        L.call("rv_pos_forward", p_(rel), 32, cin, 288, p_(P.w1), 8, p_(P.s1), p_(P.t1), p_(P.w2), c, p_(h1.view), p_(y2.view), None, st)
 
     def pos_modulate(c, cin, width, feat_=feat):
-        L.call("rv_pos_modulate_forward", p_(P.rel32), i32(32), i32(cin), p_(P.w1), i32(8), p_(P.s1), p_(P.t1), p_(P.w2), i32(c), p_(P.s2), p_(P.t2), p_(feat_), i32(256),
-               i32(1), i32(1), i32(width), p_(y2.view), st)
+        L.call("rv_pos_modulate_forward", p_(P.rel32), 32, cin, p_(P.w1), 8, p_(P.s1), p_(P.t1), p_(P.w2), c, p_(P.s2), p_(P.t2), p_(feat_), 256,
+               1, 1, width, p_(y2.view), st)
 
     def pos_backward(c, cin, dy2=P.dy2):
-        L.call("rv_pos_backward_sums", i64(288), i32(c), p_(dy2), p_(P.w2s), p_(P.rel32), i32(32), i32(cin), p_(P.w1), i32(8), *_ptrs(P.s1, P.t1, P.mean1, P.invstd1),
+        L.call("rv_pos_backward_sums", 288, c, p_(dy2), p_(P.w2s), p_(P.rel32), 32, cin, p_(P.w1), 8, *_ptrs(P.s1, P.t1, P.mean1, P.invstd1),
                p_(sums_p), p_(moms), p_(ws_p), st)
 
     rejected = [

@@ -128,13 +128,13 @@ def _launch(geom, form, c_src, c_dst, N, H, Wu, gen, relu_z, ld_y_pad, seed):
     lib = L.load()
     info = (ctypes.c_int32 * 4)()
     assert lib.rv_tap_launch_info(ctypes.byref(layer.geom), ctypes.byref(shape), int(scatter), info) == 0
-    rows = lib.rv_tap_bnb_rows(ctypes.byref(layer.geom), ctypes.byref(shape), L.i32(int(scatter)))
+    rows = lib.rv_tap_bnb_rows(ctypes.byref(layer.geom), ctypes.byref(shape), int(scatter))
     assert info[0] == gen and rows > 0, (list(info), rows)
     partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, c_dst), NAN, dtype=torch.float32, device=DEV)
-    epi = L.BnbEpilogue(ya.ptr().value, ya.ld, L.BNB_RELU_Z if relu_z else 0, *[L.ptr(v).value for v in vec], L.ptr(partial).value)
+    epi = L.BnbEpilogue(ya.ptr(), ya.ld, L.BNB_RELU_Z if relu_z else 0, *[L.ptr(v) for v in vec], L.ptr(partial))
     wp = layer.packed(form)
     fused, plain = _nan_act(N, H, Wd, c_dst), _nan_act(N, H, Wd, c_dst)
-    L.call("rv_tap_data_grad_bnb", ctypes.byref(layer.geom), ctypes.byref(shape), L.i32(int(scatter)), src.ptr(), L.ptr(wp), fused.ptr(),
+    L.call("rv_tap_data_grad_bnb", ctypes.byref(layer.geom), ctypes.byref(shape), int(scatter), src.ptr(), L.ptr(wp), fused.ptr(),
            ctypes.byref(epi), L.stream_ptr())
     L.call("rv_tap_" + form, ctypes.byref(layer.geom), ctypes.byref(shape), src.ptr(), None, None, L.ptr(wp), None, plain.ptr(), None, L.stream_ptr())
     torch.cuda.synchronize()
@@ -258,8 +258,8 @@ def _refusal_setup(flags):
     partial = torch.full((16 + L.STATS_SCRATCH_ROWS, 2, c_dst), NAN, dtype=torch.float32, device=DEV)
 
     def call(ld_y):
-        epi = L.BnbEpilogue(ya.ptr().value, ld_y, L.BNB_RELU_Z, *[L.ptr(v).value for v in vec], L.ptr(partial).value)
-        L.call("rv_tap_data_grad_bnb", ctypes.byref(layer.geom), ctypes.byref(shape), L.i32(1), src.ptr(), L.ptr(layer.packed("scatter")), dx.ptr(),
+        epi = L.BnbEpilogue(ya.ptr(), ld_y, L.BNB_RELU_Z, *[L.ptr(v) for v in vec], L.ptr(partial))
+        L.call("rv_tap_data_grad_bnb", ctypes.byref(layer.geom), ctypes.byref(shape), 1, src.ptr(), L.ptr(layer.packed("scatter")), dx.ptr(),
                ctypes.byref(epi), L.stream_ptr())
 
     def untouched():
@@ -273,7 +273,7 @@ def test_an_accumulating_launch_is_refused_and_writes_nothing():
     from range_view_3d_detection_amd import _lib as L
 
     layer, shape, call, untouched, c_dst = _refusal_setup(L.OUT_ACCUM)
-    assert L.load().rv_tap_bnb_rows(ctypes.byref(layer.geom), ctypes.byref(shape), L.i32(1)) == 0
+    assert L.load().rv_tap_bnb_rows(ctypes.byref(layer.geom), ctypes.byref(shape), 1) == 0
     with pytest.raises(L.RvError, match="no fused BatchNorm-backward sums"):
         call(c_dst)
     assert untouched()
@@ -284,7 +284,7 @@ def test_a_bad_stride_of_y_is_rejected_before_any_launch(ld_y):
     from range_view_3d_detection_amd import _lib as L
 
     layer, shape, call, untouched, c_dst = _refusal_setup(0)
-    assert L.load().rv_tap_bnb_rows(ctypes.byref(layer.geom), ctypes.byref(shape), L.i32(1)) > 0
+    assert L.load().rv_tap_bnb_rows(ctypes.byref(layer.geom), ctypes.byref(shape), 1) > 0
     with pytest.raises(L.RvError, match="bad channel stride of y"):
         call(ld_y)
     assert untouched()

@@ -70,8 +70,8 @@ def _tap(layer, form, src, dst=None, flags=0, scale=None, shift=None, stats=Fals
         partial = torch.full((rows + L.STATS_SCRATCH_ROWS, 2, E.pad32(c_out)), float("nan"), dtype=torch.float32, device=src.data.device)
     wp = layer.packed(form)
     if residual is not None:
-        L.call("rv_tap_residual", ctypes.byref(g), ctypes.byref(shape), L.i32(1 if scatter else 0), src.ptr(), L.ptr(wp), L.ptr(bias),
-               residual.ptr(), L.i32(residual.ld), dst_ptr, L.stream_ptr())
+        L.call("rv_tap_residual", ctypes.byref(g), ctypes.byref(shape), 1 if scatter else 0, src.ptr(), L.ptr(wp), L.ptr(bias),
+               residual.ptr(), residual.ld, dst_ptr, L.stream_ptr())
     else:
         L.call("rv_tap_" + form, ctypes.byref(g), ctypes.byref(shape), src.ptr(), L.ptr(scale), L.ptr(shift), L.ptr(wp), L.ptr(bias),
                dst_ptr, L.ptr(partial), L.stream_ptr())
@@ -213,8 +213,8 @@ def test_combine_into_a_slice_leaves_the_other_half_alone(half):
     A, B = _act(a), _act(b)
     dst_buf = E.Act(torch.full((N, H, W, 128), SENTINEL, dtype=torch.bfloat16, device=DEV), 128)
     out = dst_buf.slice(64 * half, 64 * half + 64)
-    L.call("rv_ew_combine", L.i64(A.pixels), L.i32(C), A.ptr(), L.i32(A.ld), L.ptr(sa), L.ptr(ta), B.ptr(), L.i32(B.ld), L.ptr(sb), L.ptr(tb),
-           out.ptr(), L.i32(out.ld), L.i32(L.EW_RELU_A | L.EW_RELU_OUT), L.stream_ptr())
+    L.call("rv_ew_combine", A.pixels, C, A.ptr(), A.ld, L.ptr(sa), L.ptr(ta), B.ptr(), B.ld, L.ptr(sb), L.ptr(tb),
+           out.ptr(), out.ld, L.EW_RELU_A | L.EW_RELU_OUT, L.stream_ptr())
     torch.cuda.synchronize()
     v = lambda t: t.cpu().view(1, C, 1, 1)
     ref = F.relu(F.relu(a * v(sa) + v(ta)) + (b * v(sb) + v(tb)))
@@ -341,8 +341,8 @@ def _wgrad(geom, N, H, Wu, u, v, expect, flags=0, scale=None, shift=None, v_affi
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=DEV)
     cu, cv, taps = geom.cu, geom.cv, geom.kh * geom.kw
     out = torch.full((cu, cv, geom.kh, geom.kw) if torch_layout else (taps, E.pad32(cu), E.pad32(cv)), float("nan"), dtype=torch.float32, device=DEV)
-    L.call("rv_tap_wgrad", ctypes.byref(geom), ctypes.byref(shape), u.ptr(), L.i32(u.ld), v.ptr(), L.i32(v.ld if ld_v is None else ld_v), L.ptr(scale),
-           L.ptr(shift), L.i32(v_affine), L.ptr(out), L.ptr(ws), L.stream_ptr())
+    L.call("rv_tap_wgrad", ctypes.byref(geom), ctypes.byref(shape), u.ptr(), u.ld, v.ptr(), v.ld if ld_v is None else ld_v, L.ptr(scale),
+           L.ptr(shift), v_affine, L.ptr(out), L.ptr(ws), L.stream_ptr())
     torch.cuda.synchronize()
     out = out.cpu()
     if not torch_layout:  # packed [tap][cu_pad][cv_pad]: padding entries are zero, the rest is the torch layout transposed

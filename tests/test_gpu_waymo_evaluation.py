@@ -94,7 +94,7 @@ def test_pairwise_iou_against_float64_clipping():
 
     full = torch.empty((n_seg * per, n_seg * per), dtype=torch.float32, device=DEV)
     ra, rb = _dev(rect(dts32)), _dev(rect(gts32))
-    L.call("rv_rotated_iou", L.ptr(ra), L.i64(n_seg * per), L.ptr(rb), L.i64(n_seg * per), L.ptr(full), L.stream_ptr())
+    L.call("rv_rotated_iou", L.ptr(ra), n_seg * per, L.ptr(rb), n_seg * per, L.ptr(full), L.stream_ptr())
     full = full.cpu().numpy().reshape(n_seg, per, n_seg, per)
     worst, n_zero = 0.0, 0
     for s in range(n_seg):

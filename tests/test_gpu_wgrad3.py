@@ -237,7 +237,7 @@ def test_strided_layers_through_the_folded_view(kind, kernel, stride, pad, folde
     folded, _ = _wgrad(gf, N, H, Wu, u, v, 3, ld_v=stride * v.ld, nan_workspace=True)
     folded = folded.to(DEV)
     got = torch.full(tuple(m.weight.shape), NAN, dtype=torch.float32, device=DEV)
-    L.call("rv_unfold_weight_grad", ctypes.byref(layer.geom), L.ptr(folded), L.ptr(got), L.i32(0), L.stream_ptr())
+    L.call("rv_unfold_weight_grad", ctypes.byref(layer.geom), L.ptr(folded), L.ptr(got), 0, L.stream_ptr())
     torch.cuda.synchronize()
     _assert_exact(got.cpu(), ref, f"{kind} {kernel} stride {stride}")
 

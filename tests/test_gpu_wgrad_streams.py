@@ -37,7 +37,7 @@ def _wgrad_setup(cin, cout, k, N, H, W, seed):
     def run():
         ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)  # (allocated and dropped per launch, as the engine does)
         out = torch.empty((cout, cin, k, k), dtype=torch.float32, device=DEV)
-        L.call("rv_tap_wgrad", ctypes.byref(geom), ctypes.byref(shape), dy.ptr(), L.i32(dy.ld), x.ptr(), L.i32(x.ld), None, None, L.i32(1),
+        L.call("rv_tap_wgrad", ctypes.byref(geom), ctypes.byref(shape), dy.ptr(), dy.ld, x.ptr(), x.ld, None, None, 1,
                L.ptr(out), L.ptr(ws), L.stream_ptr())
         return out
 
@@ -97,9 +97,9 @@ def test_stem_weight_gradient_beside_the_batchnorm_backward_passes_is_exact():
     invstd = torch.rand(C, generator=g).to(DEV) + 0.5
     coef = torch.randn(3, C, generator=g).to(DEV)
     pixels = raw.pixels
-    rows = L.load().rv_bn_bwd_rows(L.i64(pixels))
+    rows = L.load().rv_bn_bwd_rows(pixels)
     partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, C), dtype=torch.float32, device=DEV)
-    common = (L.i64(pixels), L.i32(C), dout.ptr(), L.i32(dout.ld), None, L.i32(0), raw.ptr(), L.i32(raw.ld), L.ptr(scale), L.ptr(shift), L.ptr(mean),
+    common = (pixels, C, dout.ptr(), dout.ld, None, 0, raw.ptr(), raw.ld, L.ptr(scale), L.ptr(shift), L.ptr(mean),
               L.ptr(invstd))
     side = torch.cuda.Stream(device=DEV, priority=-1)
     outs = []
@@ -110,8 +110,8 @@ def test_stem_weight_gradient_beside_the_batchnorm_backward_passes_is_exact():
         side.wait_event(ev)
         with torch.cuda.stream(side):
             outs.append(wgrad())
-        L.call("rv_bn_bwd_reduce", *common, L.i32(L.BNB_RELU_Z), L.ptr(partial), L.stream_ptr())
-        L.call("rv_bn_bwd_apply", *common, L.ptr(coef), L.i32(L.BNB_RELU_Z), dy.ptr(), L.i32(dy.ld), None, L.i32(0), L.stream_ptr())
+        L.call("rv_bn_bwd_reduce", *common, L.BNB_RELU_Z, L.ptr(partial), L.stream_ptr())
+        L.call("rv_bn_bwd_apply", *common, L.ptr(coef), L.BNB_RELU_Z, dy.ptr(), dy.ld, None, 0, L.stream_ptr())
     torch.cuda.synchronize()
     wrong = [i for i, o in enumerate(outs) if not torch.equal(o, ref)]
     assert not wrong, f"{len(wrong)} of {rounds} weight gradients differ from the quiet result (first at round {wrong[0]})"

@@ -7,6 +7,7 @@ from __future__ import annotations
 import ctypes
 import math
 import os
+import re
 import subprocess
 import sys
 
@@ -122,6 +123,165 @@ def test_null_arguments_fail_with_message(lib):
     assert b"null" in h.rv_last_error()
     with pytest.raises(lib.RvError):
         lib.call("rv_yaw_to_quat", None, ctypes.c_int64(4), ctypes.c_int64(1), None, None)
+
+
+def _header_text():
+    """include/rv3d.h without its comments."""
+    from range_view_3d_detection_amd import _lib
+
+    return re.sub(r"/\*.*?\*/", "", open(_lib.HEADER_PATH).read(), flags=re.S)
+
+
+def _header_ctype(decl):
+    """ctypes type of a return type / struct field as the header spells it (pointers: ``c_void_p``)."""
+    scalars = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double}
+    decl = " ".join(decl.replace("*", " * ").split())
+    if decl == "const char *":
+        return ctypes.c_char_p
+    return ctypes.c_void_p if "*" in decl else scalars[decl]
+
+
+@pytest.mark.parametrize("tag", ["bf16", "f16"])
+def test_every_declared_symbol_is_typed_from_the_header(lib, tag):
+    """``load()`` sets ``restype`` and ``argtypes`` of every prototype of include/rv3d.h, on both builds."""
+    handle = lib.load(tag)
+    protos = re.findall(r"([A-Za-z_][\w\s*]*?)\b(rv_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", re.sub(r"^\s*#.*$", "", _header_text(), flags=re.M))
+    assert sorted(n for _, n, _ in protos) == lib.declared_symbols() and len(protos) == 121
+    returns = {}
+    for ret, name, params in protos:
+        fn = getattr(handle, name)
+        assert fn.argtypes is not None, name
+        assert len(fn.argtypes) == (0 if params.strip() == "void" else len(params.split(","))), name
+        assert fn.restype is _header_ctype(ret), name
+        returns.setdefault(fn.restype, []).append(name)
+    assert {t: len(v) for t, v in returns.items()} == {ctypes.c_int32: 97 + 9, ctypes.c_int64: 14, ctypes.c_char_p: 1}
+    assert sum(len(getattr(handle, n).argtypes) for _, n, _ in protos) == 1160
+
+
+def test_plain_int_reaches_an_int64_parameter(lib):
+    """A bare Python int for an ``int64_t`` parameter is passed in 64 bits (untyped, ctypes truncates it to a C ``int``)."""
+    h = lib.load()
+    assert h.rv_bn_bwd_rows(2 ** 33) == 2 ** 24  # host only: 512 pixels per row
+    assert h.rv_pad_channels(5) == 32
+
+
+def test_wrong_arity_and_wrong_struct_are_refused_in_python(lib):
+    """None of these reaches C code (all but the last are host-only entry points anyway)."""
+    h = lib.load()
+    with pytest.raises(TypeError):
+        h.rv_pad_channels(5, 5)
+    g, s = lib.TapGeom(3, 3, 1, 1, 1, 256, 256), lib.TapShape(4, 64, 2048, 2048, 256, 256, 0)
+    assert h.rv_packed_weight_bytes(g) == h.rv_packed_weight_bytes(ctypes.byref(g)) == 9 * 256 * 256 * 2
+    with pytest.raises(ctypes.ArgumentError):
+        h.rv_packed_weight_bytes(s)
+    with pytest.raises(ctypes.ArgumentError):
+        h.rv_packed_weight_bytes(ctypes.byref(s))
+    args = [1024, 32, None, 32, None, 32, None, 32, None, None, None, None, 0, None, None]
+    assert len(args) == len(h.rv_bn_bwd_reduce.argtypes)
+    with pytest.raises(TypeError):
+        lib.call("rv_bn_bwd_reduce", *args[:-1])
+    with pytest.raises(ctypes.ArgumentError):
+        lib.call("rv_bn_bwd_reduce", 1024.0, *args[1:])  # (and a float is no pixel count)
+
+
+def test_unmappable_prototype_is_an_error_that_names_the_symbol(lib, tmp_path, monkeypatch):
+    """A declaration the header parser cannot type is refused when the table is built: nothing stays untyped silently."""
+    text = open(lib.HEADER_PATH).read()
+    for bad in ("int32_t rv_pad_channels(size_t c);", "unsigned rv_pad_channels(int32_t c);", "int32_t rv_pad_channels(int32_t (*c)(void));"):
+        (tmp_path / "rv3d.h").write_text(text.replace("int32_t rv_pad_channels(int32_t c);", bad))
+        monkeypatch.setattr(lib, "HEADER_PATH", str(tmp_path / "rv3d.h"))
+        lib.prototypes.cache_clear()
+        try:
+            with pytest.raises(lib.RvError, match="rv_pad_channels"):
+                lib.prototypes()
+        finally:
+            monkeypatch.undo()
+            lib.prototypes.cache_clear()
+    assert len(lib.prototypes()) == 121
+
+
+def test_python_mirrors_agree_with_the_header(lib):
+    """The flag / limit constants and the nine ctypes Structures of ``_lib`` against the ``#define`` s and ``typedef struct`` s."""
+    text = _header_text()
+    defines = re.findall(r"^\s*#define\s+RV_(\w+)[ \t]+(\(?[-\d][\d <()]*\)?)[ \t]*$", text, flags=re.M)
+    assert len(defines) == len(re.findall(r"^\s*#define\s+RV_\w+", text, flags=re.M)) >= 57  # (every one is an integer)
+    mirrored = [(name, int(eval(value, {"__builtins__": {}}))) for name, value in defines if hasattr(lib, name)]
+    assert len(mirrored) >= 55 and {"SEL_SMALL_GRIDS", "OUT_STATS", "WAYMO_MAX_SWEEPS"} <= {n for n, _ in mirrored}
+    for name, value in mirrored:
+        assert getattr(lib, name) == value, name
+    structs = dict((name, body) for body, name in re.findall(r"typedef\s+struct\s*\w*\s*\{(.*?)\}\s*(\w+)\s*;", text, flags=re.S))
+    mirrors = {"rvTapGeom": lib.TapGeom, "rvTapShape": lib.TapShape, "rvBnbEpilogue": lib.BnbEpilogue, "rvTargetLevel": lib.TargetLevel,
+               "rvTargetOut": lib.TargetOut, "rvLossEntry": lib.LossEntry, "rvLossParams": lib.LossParams, "rvLossKinds": lib.LossKinds,
+               "rvRoiLayer": lib.RoiLayer}
+    assert set(structs) == set(mirrors)
+    for cname, cls in mirrors.items():
+        fields = []
+        for decl in filter(None, (d.strip() for d in structs[cname].split(";"))):
+            ctype_decl, first = re.fullmatch(r"(.*?)(\w+(?:\[\d+\])?)", decl.split(",")[0], flags=re.S).groups()
+            for field in [first] + [f.strip() for f in decl.split(",")[1:]]:
+                m = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", field)
+                base = _header_ctype(ctype_decl)
+                fields.append((m.group(1), base * int(m.group(2)) if m.group(2) else base))
+        assert [n for n, _ in cls._fields_] == [n for n, _ in fields], cname
+        for (n, have), (_, want) in zip(cls._fields_, fields):
+            if isinstance(want, type(ctypes.c_float * 8)):  # an array: element type and length
+                assert (have._type_, have._length_) == (want._type_, want._length_), (cname, n)
+            else:
+                assert have is want, (cname, n)
+
+
+# (entry point, the optional pointers passed as NULL, bytes): recorded from the positional table this one replaces, scalar parameter i = 3 + i
+_HBM_RECORDED = [
+    ("rv_ew_combine", (), 72.0),
+    ("rv_ew_combine", ("b",), 48.0),
+    ("rv_bn_bwd_reduce", (), 72.0),
+    ("rv_bn_bwd_reduce", ("out",), 48.0),
+    ("rv_bn_bwd_apply", (), 144.0),
+    ("rv_bn_bwd_apply", ("out",), 120.0),
+    ("rv_bn_bwd_apply", ("dres",), 96.0),
+    ("rv_bn_bwd_apply", ("out", "dres"), 72.0),
+    ("rv_bn_bwd_reduce_pair", (), 96.0),
+    ("rv_bn_bwd_apply_pair", (), 144.0),
+    ("rv_meta_modulate", (), 300960.0),
+    ("rv_meta_modulate_bwd_sums", (), 960960.0),
+    ("rv_meta_modulate_bwd_apply", (), 1834560.0),
+    ("rv_pos_forward", (), 384.0),
+    ("rv_pos_backward_sums", (), 72.0),
+    ("rv_head_final_bwd_sums", (), 216.0),
+    ("rv_head_final_bwd_apply", (), 240.0),
+]
+
+
+def test_hbm_bytes_by_parameter_name(lib):
+    """Every ``HBM_BYTES`` formula reads parameters of its own entry point by their header names and prices a call as before; the hook
+    of ``call`` receives that number."""
+    protos = lib.prototypes()
+    assert set(lib.HBM_BYTES) == {name for name, _, _ in _HBM_RECORDED} <= set(lib.declared_symbols())
+
+    class Recording(dict):
+        def __getitem__(self, key):
+            read.add(key)
+            return dict.__getitem__(self, key)  # (KeyError: not a parameter of this entry point)
+
+    for name, absent, nbytes in _HBM_RECORDED:
+        params = protos[name][1]
+        assert set(absent) <= {p for _, p in params}
+        args = [(None if p in absent else 1) if t is ctypes.c_void_p else 3 + i for i, (t, p) in enumerate(params)]
+        read = set()
+        assert lib.HBM_BYTES[name](Recording(zip((p for _, p in params), args))) == nbytes, (name, absent)
+        assert read and read <= {p for _, p in params}
+    params = protos["rv_bn_bwd_apply"][1]
+    both = {p: (1000 if p == "pixels" else 64 if p == "c" else 1) for _, p in params}
+    assert lib.HBM_BYTES["rv_bn_bwd_apply"](both) == 768000
+    assert lib.HBM_BYTES["rv_bn_bwd_apply"]({**both, "out": None, "dres": None}) == 384000
+    seen = []
+    lib.HBM_HOOK = lambda name, nbytes, launch: seen.append((name, nbytes))  # (never launches)
+    try:
+        lib.call("rv_bn_bwd_apply", *[both[p] for _, p in params])
+        lib.call("rv_bn_bwd_apply", *[None if p in ("out", "dres") else both[p] for _, p in params])
+    finally:
+        lib.HBM_HOOK = None
+    assert seen == [("rv_bn_bwd_apply", 768000.0), ("rv_bn_bwd_apply", 384000.0)]
 
 
 def test_modules_fail_loudly_without_gpu():

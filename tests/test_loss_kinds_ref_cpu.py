@@ -120,7 +120,7 @@ def test_classification_elements_are_the_packages(cls_kind, alpha, gamma):
 def test_default_kinds_are_loss_ref_exactly(option, form):
     """Rows, tensors and units, bit for bit; one entry, a table with factors, and the affinity-map form."""
     p = R.OPTIONS[option]
-    quarter = R.f32(p.sigma) == 0.25
+    quarter = R.fp32(p.sigma) == 0.25
     entries = [R.make_entry(4000 + form[0], 2, 5, 67, *form, underflow=quarter), R.make_entry(4001 + form[0], 1, 3, 40, *form, underflow=quarter)]
     maps = [R.make_affinity_map(e, 4100 + k) for k, e in enumerate(entries)]
     for ents, kw in (([entries[0]], {}), (entries, dict(grad_scale=-2.5, device_factor=0.125)), (entries, dict(aff_maps=maps))):

@@ -89,7 +89,7 @@ def test_reference_agrees_with_the_fp64_oracle(name, n_cls, ld):
     er, row = ref.entries[0], ref.rows[0]
     assert torch.equal(out["foreground"][:, 0], er.foreground) and float(out["total_fg"]) == float(row[13]) and float(out["total_objects"]) == float(row[12])
     assert int(row[3]) > 20 and bool(e.planted["exact"].any())
-    tol_t = math.sqrt(3.0) * 2.0 ** -17 / R.f32(p.sigma) ** 2
+    tol_t = math.sqrt(3.0) * 2.0 ** -17 / R.fp32(p.sigma) ** 2
     t = er.soft
     assert bool(((out["targets"] - t).abs() <= tol_t * t).all())
     assert bool((t.permute(0, 2, 3, 1)[e.planted["exact"] & (e.panoptics > 0)].sum(-1) == 1.0).all()) or not p.az_inv
@@ -97,8 +97,8 @@ def test_reference_agrees_with_the_fp64_oracle(name, n_cls, ld):
     # oracle's own bce cancels there (module docstring) by up to ulp64(|x|) = 2^-46 at |x| <= 90, absolutely
     x = e.logits[..., :n_cls].permute(0, 3, 1, 2).double()
     sp, prob, m = R._softplus(x), torch.sigmoid(x), (e.mask != 0).double()[:, None]
-    cls_w, total_fg = R.f32(p.cls_weight), float(row[13])
-    bce_abs = R.f32(p.alpha) * 2.0 ** -46
+    cls_w, total_fg = R.fp32(p.cls_weight), float(row[13])
+    bce_abs = R.fp32(p.alpha) * 2.0 ** -46
     el = cls_w * m * (tol_t * t * (sp + 2 * x.abs() * t) + (t == 0) * bce_abs) / total_fg
     fg, bg = er.foreground[:, None], (1 - er.foreground[:, None]) * m
     for key, j, w in (("classification_loss", 17, 1.0), ("foreground_loss", 18, fg), ("background_loss", 19, bg)):
@@ -106,7 +106,7 @@ def test_reference_agrees_with_the_fp64_oracle(name, n_cls, ld):
     el_g = (cls_w * m * (tol_t * t * (prob + 2 * t) + (t == 0) * bce_abs * 3) / total_fg).permute(0, 2, 3, 1)
     assert bool(((d_l - er.d_logits).abs() <= el_g + 1e-9 * er.d_logits.abs()).all())
     # regression: 2^-23 relative on every term of the sums (all of one sign); the gradient has no fp32 step
-    if R.f32(p.smoothing) != 0:  # (smoothing 0: the oracle's regression part is 0 x inf off the instances)
+    if R.fp32(p.smoothing) != 0:  # (smoothing 0: the oracle's regression part is 0 x inf off the instances)
         for key, j in (("coordinate_loss", 20), ("dimension_loss", 21), ("rotation_loss", 22), ("regression_loss", 23)):
             assert abs(float(out[key]) - float(row[j])) <= 2.0 ** -22 * float(row[j]), key
         assert abs(float(out["loss"]) - float(row[16])) <= float(el.sum()) + 2.0 ** -22 * float(row[16])
@@ -126,7 +126,7 @@ def test_fp32_oracle_yardstick(capsys):
         assert int(ref.rows[0, 3]) > 20 and e.num_objects >= 3
         if p.az_inv:
             assert bool((er.soft.sum(1)[e.planted["exact"]] == 1.0).all()) and bool(e.planted["exact"].any())
-        if R.f32(p.sigma) == 0.25:
+        if R.fp32(p.sigma) == 0.25:
             far = e.planted["far"]
             assert int(far.sum()) >= 3 and bool((er.foreground[far] == 0).all()) and bool((er.affinity_arg[far] > 125).all())
         assert bool((er.affinity_arg[inst & ~e.planted["far"]] < 60).all())

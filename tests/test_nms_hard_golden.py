@@ -149,7 +149,7 @@ def test_both_libraries_export_the_hard_entries_and_kernels():
     for tag, path in (("bf16", L.LIB_PATH), ("f16", L.LIB_PATH_F16)):
         lib = L.load(tag)
         assert all(hasattr(lib, n) for n in NEW_ENTRIES), tag
-        assert lib.rv_nms_rotated_workspace_bytes(L.i64(1000)) >= 1000 * 16 * 8 + 1000 * 8
+        assert lib.rv_nms_rotated_workspace_bytes(1000) >= 1000 * 16 * 8 + 1000 * 8
         blob = b"".join(_gfx950_code_objects(path))
         for kernel in (b"k_post_hard", b"k_scanILb1E", b"k_iouILb1E", b"k_gatherILb1E", b"scan_kernelILb1E", b"iou_mask_kernelILb1E",
                        b"k_scanILb0E", b"k_iouILb0E", b"scan_kernelILb0E"):

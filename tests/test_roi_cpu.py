@@ -123,8 +123,8 @@ def test_both_builds_export_the_roi_entry_points(tag):
     assert all(hasattr(handle, s) for s in ROI_SYMBOLS)
     assert ctypes.sizeof(_lib.RoiLayer) == 40
     # 32 bytes per polygon + 4 bytes per pixel, each part rounded up to 256 bytes
-    assert handle.rv_roi_rasterize_workspace_bytes(_lib.i32(2), _lib.i32(80), _lib.i32(96)) == 256 + 80 * 96 * 4
-    assert handle.rv_roi_rasterize_workspace_bytes(_lib.i32(2), _lib.i32(0), _lib.i32(96)) == 0
+    assert handle.rv_roi_rasterize_workspace_bytes(2, 80, 96) == 256 + 80 * 96 * 4
+    assert handle.rv_roi_rasterize_workspace_bytes(2, 0, 96) == 0
 
 
 def test_atlas_is_built_and_checked_on_the_host():
@@ -147,12 +147,12 @@ def test_atlas_is_built_and_checked_on_the_host():
         RoiAtlas.from_rasters(["a"], arrays[:1], [(0.0, 1.0, 1.0)])
     # a table whose layer reaches beyond the buffer is refused before any kernel could read through it
     table = (L.RoiLayer * 2)(L.RoiLayer(0, 4, 5, 1.0, 0.0, 0.0), L.RoiLayer(20, 3, 3, 1.0, 0.0, 0.0))
-    L.call("rv_roi_atlas_check", table, L.i32(2), L.i64(29))
+    L.call("rv_roi_atlas_check", table, 2, 29)
     with pytest.raises(RvError, match="reaches beyond"):
-        L.call("rv_roi_atlas_check", table, L.i32(2), L.i64(28))
+        L.call("rv_roi_atlas_check", table, 2, 28)
     table[1].offset = -1
     with pytest.raises(RvError, match="reaches beyond"):
-        L.call("rv_roi_atlas_check", table, L.i32(2), L.i64(29))
+        L.call("rv_roi_atlas_check", table, 2, 29)
 
 
 def test_argument_checks_need_no_device():
@@ -160,13 +160,13 @@ def test_argument_checks_need_no_device():
 
     null, one = ctypes.c_void_p(0), ctypes.c_void_p(8)
     with pytest.raises(L.RvError, match="sweeps"):
-        L.call("rv_roi_points", null, L.i32(0), L.i64(0), one, L.i32(0), one, one, null, L.i64(0), null, L.i32(0), null, one, null)
+        L.call("rv_roi_points", null, 0, 0, one, 0, one, one, null, 0, null, 0, null, one, null)
     with pytest.raises(L.RvError, match="null sweep table"):
-        L.call("rv_roi_boxes", null, null, L.i64(0), L.i32(1), null, one, null, L.i64(0), null, L.i32(0), null, one, null)
+        L.call("rv_roi_boxes", null, null, 0, 1, null, one, null, 0, null, 0, null, one, null)
     with pytest.raises(L.RvError, match="dilation radius"):
-        L.call("rv_roi_rasterize", one, one, L.i64(0), L.i32(0), L.f64(1.0), L.f64(0.0), L.f64(0.0), L.i32(4), L.i32(4), L.f64(-1.0), one, one, one, null)
+        L.call("rv_roi_rasterize", one, one, 0, 0, 1.0, 0.0, 0.0, 4, 4, -1.0, one, one, one, null)
     with pytest.raises(L.RvError, match="raster of"):
-        L.call("rv_roi_rasterize", one, one, L.i64(0), L.i32(0), L.f64(1.0), L.f64(0.0), L.f64(0.0), L.i32(65536), L.i32(65536), L.f64(1.0), one, one, one,
+        L.call("rv_roi_rasterize", one, one, 0, 0, 1.0, 0.0, 0.0, 65536, 65536, 1.0, one, one, one,
                null)
 
 

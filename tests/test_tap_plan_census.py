@@ -98,16 +98,10 @@ def census():
     return calls
 
 
-class _Geom(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("kh", "kw", "stride_w", "pad_h", "pad_w", "cu", "cv")]
-
-
-class _Shape(ctypes.Structure):
-    _fields_ = [(n, ctypes.c_int32) for n in ("N", "H", "Wu", "Wv", "ld_src", "ld_dst", "flags")]
-
-
 def answers(handle):
     """One string per call: "rc info[0..3] | stats_rows | bnb_rows | error strings of the calls that failed"."""
+    from range_view_3d_detection_amd._lib import TapGeom as _Geom, TapShape as _Shape  # (the typed binding takes no other struct)
+
     handle.rv_last_error.restype = ctypes.c_char_p
     out = []
     for geom, shape, scatter in census():

@@ -200,11 +200,11 @@ def test_argument_checks_reject_before_anything_is_launched():
         assert match in lib.rv_last_error().decode(), lib.rv_last_error()
 
     def common(k):
-        return [k.get("ri", p), k.get("ext", p), k.get("incl", p), k.get("pp", null), k.get("inv", null), L.i32(k.get("B", 1)), L.i32(k.get("H", 2)),
-                L.i32(k.get("W", 8))]
+        return [k.get("ri", p), k.get("ext", p), k.get("incl", p), k.get("pp", null), k.get("inv", null), k.get("B", 1), k.get("H", 2),
+                k.get("W", 8)]
 
     sweep = lambda **k: common(k) + [k.get("sweep", p), k.get("num_pts", p), null]
-    batch = lambda **k: common(k) + [L.i32(k.get("n_feat", 6)), k.get("src", src), k.get("op", op), L.i32(k.get("pad", 3)), L.i32(k.get("circular", 0)),
+    batch = lambda **k: common(k) + [k.get("n_feat", 6), k.get("src", src), k.get("op", op), k.get("pad", 3), k.get("circular", 0),
                                      k.get("features", p), k.get("cart", p), k.get("mask", p), k.get("num_pts", p), null]
     for name, make in (("rv_waymo_range_image_to_sweep", sweep), ("rv_waymo_range_image_to_batch", batch)):
         rejected(name, make(ri=null), "null")

@@ -120,8 +120,8 @@ def test_both_builds_export_the_entries_and_the_limits_agree():
                       "RV_WAYMO_NUM_RESULT_ROWS": L.WAYMO_NUM_RESULT_ROWS}
     assert L.WAYMO_MAX_DTS >= 1024 and L.WAYMO_MAX_GTS >= 1024  # RangeDecoder emits up to 1000 rows per class and sweep
     lib = L.load()
-    assert lib.rv_waymo_match_workspace_bytes(L.i64(-1), L.i64(1), L.i32(4)) == 0 and lib.rv_waymo_match_workspace_bytes(L.i64(1), L.i64(1), L.i32(0)) == 0
-    small, capped = (lib.rv_waymo_match_workspace_bytes(L.i64(100), L.i64(m), L.i32(8)) for m in (10, 5000))
+    assert lib.rv_waymo_match_workspace_bytes(-1, 1, 4) == 0 and lib.rv_waymo_match_workspace_bytes(1, 1, 0) == 0
+    small, capped = (lib.rv_waymo_match_workspace_bytes(100, m, 8) for m in (10, 5000))
     assert small >= 9 * 8 + 100 * 10 * 8 and capped >= 100 * L.WAYMO_MAX_GTS * 8 and capped < 100 * 5000 * 8
 
 
@@ -130,15 +130,15 @@ def test_argument_checks_reject_before_anything_is_launched():
 
     lib = L.load()
     buf = (ctypes.c_int64 * 64)()  # (a host buffer: only ever checked for null / alignment, never dereferenced by a rejected call)
-    p, null, thr = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_void_p(0), (L.f32 * 5)(0.0, 0.7, 0.5, 0.5, 0.5)
+    p, null, thr = ctypes.cast(buf, ctypes.c_void_p), ctypes.c_void_p(0), (ctypes.c_float * 5)(0.0, 0.7, 0.5, 0.5, 0.5)
     odd = ctypes.c_void_p(ctypes.addressof(buf) + 4)
 
     def rejected(name, *args, match):
         assert getattr(lib, name)(*args) == 1, name
         assert match in lib.rv_last_error().decode(), lib.rv_last_error()
 
-    iou = lambda **k: [k.get("dts", p), k.get("dt_order", p), k.get("dt_off", p), L.i64(k.get("n_dt", 4)), k.get("gts", p), k.get("gt_order", p),
-                       k.get("gt_off", p), L.i64(k.get("n_gt", 4)), L.i32(k.get("n_seg", 4)), k.get("ws", p), null]
+    iou = lambda **k: [k.get("dts", p), k.get("dt_order", p), k.get("dt_off", p), k.get("n_dt", 4), k.get("gts", p), k.get("gt_order", p),
+                       k.get("gt_off", p), k.get("n_gt", 4), k.get("n_seg", 4), k.get("ws", p), null]
     rejected("rv_waymo_iou", *iou(n_dt=-1), match="n_dt")
     rejected("rv_waymo_iou", *iou(n_seg=0), match="segments")
     rejected("rv_waymo_iou", *iou(dt_off=null), match="null")
@@ -146,8 +146,8 @@ def test_argument_checks_reject_before_anything_is_launched():
     rejected("rv_waymo_iou", *iou(ws=odd), match="aligned")
     rejected("rv_waymo_iou", *iou(dts=null), match="null detection")
     rejected("rv_waymo_iou", *iou(gt_order=null), match="null ground-truth")
-    match = lambda **k: [k.get("dts", p), k.get("scores", p), p, k.get("dt_off", p), L.i64(k.get("n_dt", 4)), p, k.get("level", p), p, p,
-                         L.i64(k.get("n_gt", 4)), null, L.i32(k.get("n_sweeps", 1)), k.get("thr", thr), k.get("ws", p), k.get("tables", p),
+    match = lambda **k: [k.get("dts", p), k.get("scores", p), p, k.get("dt_off", p), k.get("n_dt", 4), p, k.get("level", p), p, p,
+                         k.get("n_gt", 4), null, k.get("n_sweeps", 1), k.get("thr", thr), k.get("ws", p), k.get("tables", p),
                          k.get("errors", p), null]
     rejected("rv_waymo_match", *match(n_gt=-3), match="n_gt")
     rejected("rv_waymo_match", *match(n_sweeps=0), match="sweeps")
@@ -157,7 +157,7 @@ def test_argument_checks_reject_before_anything_is_launched():
     rejected("rv_waymo_match", *match(thr=null), match="null")
     rejected("rv_waymo_match", *match(scores=null), match="null detection")
     rejected("rv_waymo_match", *match(level=null), match="null ground-truth")
-    rejected("rv_waymo_match", *match(thr=(L.f32 * 5)(0.0, 1.7, 0.5, 0.5, 0.5)), match="threshold")
+    rejected("rv_waymo_match", *match(thr=(ctypes.c_float * 5)(0.0, 1.7, 0.5, 0.5, 0.5)), match="threshold")
     rejected("rv_waymo_summarize", null, p, null, match="null")
     rejected("rv_waymo_summarize", p, null, null, match="null")
 
