@@ -18,12 +18,11 @@ reference tree, parity unpinned).  No CPU fallback: host tensors for boxes/data 
 
 from __future__ import annotations
 
-import ctypes
-
 import torch
 from torch import Tensor
 
 from range_view_3d_detection_amd import _lib as L
+from range_view_3d_detection_amd.math.ops.nms import wnms_sorted
 
 
 def wnms_gpu(boxes: Tensor, data2merge_score: Tensor, output: Tensor, keep: Tensor, count: Tensor, nms_thresh: float,
@@ -46,10 +45,6 @@ def wnms_gpu(boxes: Tensor, data2merge_score: Tensor, output: Tensor, keep: Tens
         return 0
     with torch.cuda.device(boxes.device):
         keep_dev = torch.empty(n, dtype=torch.int64, device=boxes.device)
-        ws = torch.empty(L.load().rv_wnms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
-        num_out = ctypes.c_int64(0)
-        L.call("rv_wnms", L.ptr(boxes), L.ptr(data2merge_score), n, d, nms_thresh, merge_thresh,
-               L.ptr(output), L.ptr(keep_dev), L.ptr(count), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
-        k = int(num_out.value)
+        k = wnms_sorted(boxes, data2merge_score, output, keep_dev, count, nms_thresh, merge_thresh)
         keep[:k].copy_(keep_dev[:k])  # device -> host, synchronous
     return k

@@ -106,23 +106,15 @@ __global__ __launch_bounds__(THREADS) void waymo_offsets_kernel(const Segments s
     }
 }
 
-// [x1, y1, x2, y2, ry] of a box [x, y, z, l, w, h, yaw]: the rectangle rv_rotated_iou takes, length axis at +yaw
-__device__ __forceinline__ void rect_of(const float* box, float* r) {
-    const float hl = 0.5f * box[3], hw = 0.5f * box[4];
-    r[0] = box[0] - hl, r[1] = box[1] - hw, r[2] = box[0] + hl, r[3] = box[1] + hw, r[4] = box[6];
-}
-
 __device__ float2 waymo_iou_pair(const float* a, const float* b) {
     float2 out = make_float2(0.0f, 0.0f);
     // circumscribed circles of the footprints apart (with a margin far above the rounding of the clip): the intersection is empty
     const float dx = a[0] - b[0], dy = a[1] - b[1];
     const float reach = 0.5f * (sqrtf(a[3] * a[3] + a[4] * a[4]) + sqrtf(b[3] * b[3] + b[4] * b[4]));
     if (dx * dx + dy * dy > reach * reach * 1.001f + 1e-6f) return out;
-    float ra[5], rb[5];
-    rect_of(a, ra), rect_of(b, rb);
-    const float sa = (float)sin((double)ra[4]), ca = (float)cos((double)ra[4]);
-    const float sb = (float)sin((double)rb[4]), cb = (float)cos((double)rb[4]);
-    float area;
+    float ra[5], rb[5], sa, ca, sb, cb, area;  // boxes are [x, y, z, l, w, h, yaw]; the rectangles rv_rotated_iou takes
+    rect_of_box(a[0], a[1], a[3], a[4], a[6], ra), rect_of_box(b[0], b[1], b[3], b[4], b[6], rb);
+    yaw_sincos(a[6], sa, ca), yaw_sincos(b[6], sb, cb);
     out.x = rotated_iou_inter(ra, sa, ca, rb, sb, cb, area);
     const float hha = 0.5f * a[5], hhb = 0.5f * b[5];
     const float top_a = a[2] + hha, top_b = b[2] + hhb, bot_a = a[2] - hha, bot_b = b[2] - hhb;

@@ -40,8 +40,11 @@
 //                  position = class base + index among the class's kept boxes, dropped at >= num_post_nms -- no ranking pass;
 //                  the 7 floats and the score are copied from the caller's `cuboids` / `scores` rows (order -> cand), so every
 //                  output row is an input row bit for bit (the yaw never passes through sin / cos / atan2).
+// The pair loop of stage 4, the word scan of stage 5 and the cluster sum of stage 7 are nms_core.h's, shared with the list path
+// (nms.hip); the kernels here load rows and tiles from the sweep's sorted arrays, address the class-relative masks (`mword`) and
+// record kept boxes as flags.
 #include "common.h"
-#include "nms_geom.h"
+#include "nms_core.h"
 
 namespace {
 
@@ -200,16 +203,13 @@ __global__ __launch_bounds__(256) void k_gather(const Args a) {
         const int64_t src = p.cand[p.order[r]];
         const float* q = a.cuboids + ((int64_t)b * a.K + src) * 7;
         const float x = q[0], y = q[1], l = q[3], w = q[4], yaw = q[6];
-        const float hl = l / 2, hw = w / 2;
-        float* rc = p.rect + (int64_t)r * 5;
-        rc[0] = x - hl; rc[1] = y - hw; rc[2] = x + hl; rc[3] = y + hw; rc[4] = yaw;
+        rect_of_box(x, y, l, w, yaw, p.rect + (int64_t)r * 5);
         if constexpr (!HARD) {
             float* d = p.data + (int64_t)r * 9;
             d[0] = x; d[1] = y; d[2] = q[2]; d[3] = l; d[4] = w; d[5] = q[5];
             d[6] = sinf(yaw); d[7] = cosf(yaw); d[8] = s[src];
         }
-        p.sc[2 * r] = (float)sin((double)yaw);
-        p.sc[2 * r + 1] = (float)cos((double)yaw);
+        yaw_sincos(yaw, p.sc[2 * r], p.sc[2 * r + 1]);
         p.cats[r] = (int32_t)c[src];
         p.kept[r] = 0;
     }
@@ -251,15 +251,14 @@ __global__ __launch_bounds__(256) void k_unkeep(const Args a) {
 template <bool HARD>
 __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, int col) {
     const int64_t j0 = (int64_t)col * 64, i0 = (int64_t)row * 64;
-    __shared__ float cbox[64][7];
-    __shared__ int32_t ccat[64];
+    __shared__ ColTile tile;
     const int t = threadIdx.x;
     if (j0 + t < n) {
-        ccat[t] = p.cats[j0 + t];
+        tile.cat[t] = p.cats[j0 + t];
 #pragma unroll
-        for (int k = 0; k < 5; ++k) cbox[t][k] = p.rect[(j0 + t) * 5 + k];
-        cbox[t][5] = p.sc[2 * (j0 + t)];
-        cbox[t][6] = p.sc[2 * (j0 + t) + 1];
+        for (int k = 0; k < 5; ++k) tile.box[t][k] = p.rect[(j0 + t) * 5 + k];
+        tile.box[t][5] = p.sc[2 * (j0 + t)];
+        tile.box[t][6] = p.sc[2 * (j0 + t) + 1];
     }
     __syncthreads();
     const int64_t i = i0 + t;
@@ -271,23 +270,9 @@ __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, i
 #pragma unroll
     for (int k = 0; k < 5; ++k) bx[k] = p.rect[i * 5 + k];
     const float sa = p.sc[2 * i], ca = p.sc[2 * i + 1];
-    // bounding circle of box i: boxes whose circles are apart cannot intersect -- their IoU is 0 in the clipping arithmetic
-    // too, so skipping them changes no bit of the masks (thresholds are positive) and skips ~all pairs of a spread-out scene
-    const float cxi = 0.5f * (bx[0] + bx[2]), cyi = 0.5f * (bx[1] + bx[3]);
-    const float ri = 0.5f * sqrtf((bx[2] - bx[0]) * (bx[2] - bx[0]) + (bx[3] - bx[1]) * (bx[3] - bx[1]));
-    const bool skip_far = a.nms_t >= 0.f && (HARD || a.merge_t >= 0.f);
-    unsigned long long bits_n = 0ull, bits_m = 0ull;
-    const int jn = (int)((n - j0) < 64 ? (n - j0) : 64);
-    for (int j = 0; j < jn; ++j) {
-        if (j0 + j <= i || ccat[j] != cat_i || j0 + j >= send_i) continue;
-        const float dx = 0.5f * (cbox[j][0] + cbox[j][2]) - cxi, dy = 0.5f * (cbox[j][1] + cbox[j][3]) - cyi;
-        const float rj = 0.5f * sqrtf((cbox[j][2] - cbox[j][0]) * (cbox[j][2] - cbox[j][0]) + (cbox[j][3] - cbox[j][1]) * (cbox[j][3] - cbox[j][1]));
-        if (skip_far && dx * dx + dy * dy > (ri + rj) * (ri + rj) * 1.001f + 1e-4f) continue;
-        const float iou = rotated_iou(bx, sa, ca, cbox[j], cbox[j][5], cbox[j][6]);
-        if (iou > a.nms_t) bits_n |= 1ull << j;
-        if constexpr (!HARD)
-            if (iou > a.merge_t) bits_m |= 1ull << j;
-    }
+    unsigned long long bits_n, bits_m;
+    // (columns end at the pre-NMS cut)
+    pair_bits<HARD>(tile, (int)(n - j0 < 64 ? n - j0 : 64), bx, sa, ca, cat_i, i, j0, send_i, a.nms_t, a.merge_t, bits_n, bits_m);
     const int64_t mw = mword(p, cat_i, (int)i, col);
     p.nms_mask[mw] = bits_n;
     if constexpr (!HARD) p.merge_mask[mw] = bits_m;
@@ -320,12 +305,9 @@ __global__ __launch_bounds__(64) void k_iou(const Args a) {
 
 // 5. suppression scan: grid (class, sweep).  Words of the masks outside [first, last] word of the segment are never read
 // (k_iou may not have written them).
-// The scan walks the segment in blocks of 64 boxes (one mask word).  Inside a block the chain "is box b still alive?" is
-// resolved by ONE wave from the 64 diagonal words held one per lane (64 register-only steps); then every thread owning a later
-// word w folds the rows of the block's kept boxes into remv[w] (and masks their merge rows with the boxes alive at their
-// visit) -- one round of global loads per 64 boxes instead of one per kept box.
-// HARD: there is no merge mask -- a later word of a kept box is one read of nms_mask (weighted: that read plus a
-// read-modify-write of merge_mask), and a kept box writes its flag only.
+// The scan walks the segment in blocks of 64 boxes (one mask word): one wave resolves the block (scan_diagonal), then every thread
+// owning a later word w folds the rows of the block's kept boxes into remv[w] (scan_fold) -- one round of global loads per 64 boxes
+// instead of one per kept box.  HARD: a kept box writes its flag only.
 template <bool HARD>
 __global__ __launch_bounds__(256) void k_scan(const Args a) {
     const SweepPtrs p = sweep(a, blockIdx.y);
@@ -343,17 +325,8 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
             const int i = wi * 64 + b;
             const bool in_seg = i >= s0 && i < s1;
             const unsigned long long diag = in_seg ? p.nms_mask[mword(p, cls, i, wi)] : 0ull;
-            const unsigned long long seg_bits = __ballot(in_seg);
-            const uint32_t dlo = (uint32_t)diag, dhi = (uint32_t)(diag >> 32);
-            unsigned long long rem = remv[wi - w0], kept = 0ull;
-            [[maybe_unused]] unsigned long long alive_mine = 0ull;
-            for (int q = 0; q < 64; ++q) {  // uniform loop; lane q's diagonal word through readlane
-                if (!((seg_bits >> q) & 1ull) || ((rem >> q) & 1ull)) continue;
-                kept |= 1ull << q;
-                if constexpr (!HARD)
-                    if (b == q) alive_mine = ~rem;
-                rem |= ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)dhi, q) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)dlo, q);
-            }
+            unsigned long long rem = remv[wi - w0], kept, alive_mine;
+            scan_diagonal<HARD>(diag, __ballot(in_seg), b, rem, kept, alive_mine);
             if ((kept >> b) & 1ull) {
                 p.kept[i] = 1;
                 if constexpr (!HARD) p.merge_mask[mword(p, cls, i, wi)] &= alive_mine;  // cluster = merge candidates not suppressed before i was visited
@@ -365,18 +338,9 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
         }
         __syncthreads();
         const unsigned long long kept = kept_word;
-        for (int w = wi + 1 + threadIdx.x; w <= w1; w += blockDim.x) {
-            // a word at the segment's edge may hold bits of the neighbouring class: k_iou never sets those (class check)
-            unsigned long long r = remv[w - w0], bits = kept;
-            while (bits) {
-                const int q = __ffsll((long long)bits) - 1;
-                bits &= bits - 1;
-                const int64_t mw = mword(p, cls, wi * 64 + q, w);
-                if constexpr (!HARD) p.merge_mask[mw] &= ~r;
-                r |= p.nms_mask[mw];
-            }
-            remv[w - w0] = r;
-        }
+        // (a word at the segment's edge may hold bits of the neighbouring class: k_iou never sets those -- class check)
+        for (int w = wi + 1 + threadIdx.x; w <= w1; w += blockDim.x)
+            remv[w - w0] = scan_fold<HARD>(remv[w - w0], kept, p.nms_mask, p.merge_mask, [&](int q) { return mword(p, cls, wi * 64 + q, w); });
         __syncthreads();
     }
 }
@@ -412,22 +376,10 @@ __global__ __launch_bounds__(64) void k_merge(const Args a) {
     const int cls = p.cats[i];
     const int w1 = (p.send[cls] - 1) >> 6;  // last mask word of the box's class segment
     const int c = threadIdx.x;
-    const bool active = c < 9;
-    const float wi = p.data[(int64_t)i * 9 + 8];
-    float acc = active ? wi * p.data[(int64_t)i * 9 + c] : 0.f;
-    float wsum = wi;
-    for (int w = i >> 6; w <= w1; ++w) {
-        unsigned long long bits = p.merge_mask[mword(p, cls, i, w)];
-        while (bits) {
-            const int bb = __ffsll((long long)bits) - 1;
-            bits &= bits - 1;
-            const int64_t j = (int64_t)w * 64 + bb;
-            const float wj = p.data[j * 9 + 8];
-            if (active) acc += wj * p.data[j * 9 + c];
-            wsum += wj;
-        }
-    }
-    if (active) p.merged[(int64_t)o * 9 + c] = acc / wsum;
+    float acc, wsum;
+    long long members;  // (not reported on this path)
+    cluster_sum(p.data, 9, c, i, i >> 6, w1, [&](int w) { return p.merge_mask[mword(p, cls, i, w)]; }, acc, wsum, members);
+    if (c < 9) p.merged[(int64_t)o * 9 + c] = acc / wsum;
     }
 }
 

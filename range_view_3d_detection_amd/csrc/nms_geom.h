@@ -1,5 +1,7 @@
-// Rotated-BEV-IoU of two boxes [x1, y1, x2, y2, ry] (shared by nms.hip, nms2.hip, softassign.hip and evaluate_waymo.hip; all are
-// compiled without fused multiply-add contraction so that the result matches oracle/c/oracle.c bit for bit).
+// Rotated-BEV-IoU of two boxes [x1, y1, x2, y2, ry], the rectangle of a box and the sin / cos the IoU takes.  Users: nms_core.h (the
+// pair masks of nms.hip and nms2.hip), nms.hip (sin / cos pass, rv_rotated_iou), nms2.hip (gather), softassign.hip (BEV affinity) and
+// evaluate_waymo.hip (BEV / 3-D IoU); all include it where fused multiply-add contraction is off, so that the result matches
+// oracle/c/oracle.c bit for bit.
 #pragma once
 #include "common.h"
 
@@ -8,6 +10,18 @@ namespace {
 struct Pt {
     float x, y;
 };
+
+// [x1, y1, x2, y2, ry] of the BEV footprint of a box at (x, y), length l along +yaw, width w
+__device__ __forceinline__ void rect_of_box(float x, float y, float l, float w, float yaw, float* r) {
+    const float hl = 0.5f * l, hw = 0.5f * w;
+    r[0] = x - hl, r[1] = y - hw, r[2] = x + hl, r[3] = y + hw, r[4] = yaw;
+}
+
+// the sin / cos of the IoU arithmetic: fp32 roundings of the fp64 values
+__device__ __forceinline__ void yaw_sincos(float yaw, float& s, float& c) {
+    s = (float)sin((double)yaw);
+    c = (float)cos((double)yaw);
+}
 
 __device__ __forceinline__ float cross2(Pt a, Pt b, Pt p) { return (b.x - a.x) * (p.y - a.y) - (b.y - a.y) * (p.x - a.x); }
 

@@ -62,13 +62,14 @@ __device__ __forceinline__ int entry_of(const SaTable& t) {
     return k;
 }
 
-// [x1, y1, x2, y2] of the BEV rectangle (x, y, l, w): the layout of nms_geom.h / oracle.nms.pairwise_iou
-__device__ __forceinline__ void bev_box(float x, float y, float l, float w, float* b) {
-    const float hl = 0.5f * l, hw = 0.5f * w;
-    b[0] = x - hl;
-    b[1] = y - hw;
-    b[2] = x + hl;
-    b[3] = y + hw;
+// BEV IoU of two boxes (x, y) / (l, w, yaw): oracle.nms.pairwise_iou on their rectangles; above the pragma, so not contracted
+__device__ __forceinline__ float bev_iou(const float* cp, const float* lp, const float* cg, const float* lg) {
+    float bp[5], bg[5], sp, cpn, sg, cgn;
+    rect_of_box(cp[0], cp[1], lp[0], lp[1], lp[2], bp);
+    rect_of_box(cg[0], cg[1], lg[0], lg[1], lg[2], bg);
+    yaw_sincos(lp[2], sp, cpn);
+    yaw_sincos(lg[2], sg, cgn);
+    return rotated_iou(bp, sp, cpn, bg, sg, cgn);
 }
 
 #pragma clang fp contract(fast)
@@ -125,14 +126,10 @@ __global__ __launch_bounds__(256) void sa_affinity_kernel(const SaTable t) {
         decode_centre(r, px, py, pz, 1, cp);  // predictions are always decoded azimuth-invariantly (assignment.py:112)
         decode_centre(tg, px, py, pz, t.az_inv, cg);
         if (BEV) {
-            float lp[3], lg[3], bp[4], bg[4];
+            float lp[3], lg[3];
             decode_lwa(r, px, py, 1, lp);
             decode_lwa(tg, px, py, t.az_inv, lg);
-            bev_box(cp[0], cp[1], lp[0], lp[1], bp);
-            bev_box(cg[0], cg[1], lg[0], lg[1], bg);
-            const float sp = (float)sin((double)lp[2]), cpn = (float)cos((double)lp[2]);
-            const float sg = (float)sin((double)lg[2]), cgn = (float)cos((double)lg[2]);
-            const float iou = rotated_iou(bp, sp, cpn, bg, sg, cgn);
+            const float iou = bev_iou(cp, lp, cg, lg);
             e.map[i] = fminf(fmaxf(iou, 0.f), 1.f);  // (.clamp(0, 1), assignment.py:70)
         } else {
             const float dx = cp[0] - cg[0], dy = cp[1] - cg[1], dz = cp[2] - cg[2];

@@ -24,21 +24,27 @@ from ... import _lib as L
 from ...engine import _require_cuda
 
 
+def wnms_sorted(boxes: Tensor, data: Tensor, output: Tensor, keep: Tensor, count: Tensor, nms_threshold: float, merge_thresh: float) -> int:
+    """The ``rv_wnms`` call: score-sorted contiguous f32 device ``boxes`` (N,5) and ``data`` (N,C+1, last column the score); fills
+    rows ``[0, k)`` of ``output`` (N,C+1), ``keep`` and ``count`` (int64, device) and returns k (synchronous)."""
+    n, d = data.shape
+    ws = torch.empty(L.load().rv_wnms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
+    num_out = ctypes.c_int64(0)
+    L.call("rv_wnms", L.ptr(boxes), L.ptr(data), n, d, nms_threshold, merge_thresh, L.ptr(output),
+           L.ptr(keep), L.ptr(count), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
+    return int(num_out.value)
+
+
 def weighted_nms(boxes: Tensor, data2merge: Tensor, scores: Tensor, nms_threshold: float, merge_thresh: float) -> Tuple[Tensor, Tensor, Tensor]:
     """boxes (N,5) [x1,y1,x2,y2,ry], data2merge (N,C), scores (N,) -> (keep indices, merged rows (K,C+1), counts (K,))."""
     _require_cuda(boxes, "boxes")
     sorted_scores, order = scores.sort(0, descending=True)
     boxes = boxes[order].contiguous().float()
     data = torch.cat([data2merge[order].float(), sorted_scores[:, None].float()], 1).contiguous()
-    n, d = data.shape
     output = torch.zeros_like(data)
-    keep = torch.zeros(n, dtype=torch.long, device=boxes.device)
-    count = torch.zeros(n, dtype=torch.long, device=boxes.device)
-    ws = torch.empty(L.load().rv_wnms_workspace_bytes(n), dtype=torch.uint8, device=boxes.device)
-    num_out = ctypes.c_int64(0)
-    L.call("rv_wnms", L.ptr(boxes), L.ptr(data), n, d, nms_threshold, merge_thresh, L.ptr(output),
-           L.ptr(keep), L.ptr(count), L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
-    k = int(num_out.value)
+    keep = torch.zeros(data.shape[0], dtype=torch.long, device=boxes.device)
+    count = torch.zeros(data.shape[0], dtype=torch.long, device=boxes.device)
+    k = wnms_sorted(boxes, data, output, keep, count, nms_threshold, merge_thresh)
     return order[keep[:k]].contiguous(), output[:k], count[:k]
 
 
@@ -103,38 +109,6 @@ def _capacity(k: int) -> int:
     return max(64, (min(k, FUSED_CLASSES_MAX) + 63) // 64 * 64)
 
 
-def weighted_multiclass_nms(cuboids_i: Tensor, scores_i: Tensor, categories_i: Tensor, iou_threshold: float, num_pre_nms: int,
-                            num_post_nms: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """Per class (ascending ``unique``): top-k pre, weighted NMS with merge threshold 0.5 (``nms.py:105-106``), top-k post."""
-    n = scores_i.shape[0]
-    if 0 < n <= FUSED_CLASSES_MAX:
-        n_cls = int(categories_i.max().item()) + 1
-        if n_cls <= 64:
-            b, s, c, cnt = nms_sweeps(cuboids_i[None], scores_i[None], categories_i[None], n_cls, iou_threshold, -math.inf, num_post_nms, _capacity(n),
-                                      num_pre_nms)
-            return b[0, : cnt[0]], s[0, : cnt[0]], c[0, : cnt[0]].to(s.dtype)
-    out_b: List[Tensor] = []
-    out_s: List[Tensor] = []
-    out_c: List[Tensor] = []
-    for j in categories_i.unique():
-        sel = categories_i == j
-        s, b = scores_i[sel], cuboids_i[sel]
-        s, rank = s.topk(k=min(len(s), num_pre_nms), dim=0)
-        b = b[rank]
-        half = b[:, 3:5] / 2
-        rect = torch.cat([b[:, :2] - half, b[:, :2] + half, b[:, 6:7]], dim=-1)
-        data = torch.cat([b[:, :6], b[:, 6:7].sin(), b[:, 6:7].cos()], dim=1)
-        _, merged, _ = weighted_nms(rect, data, s, nms_threshold=iou_threshold, merge_thresh=0.5)
-        box6, sn, cs, sc = merged.split([6, 1, 1, 1], dim=1)
-        b = torch.cat([box6, torch.atan2(sn, cs)], dim=1)
-        sc = sc.flatten()
-        sc, rank = sc.topk(k=min(len(b), num_post_nms), dim=0)
-        out_b.append(b[rank])
-        out_s.append(sc)
-        out_c.append(torch.full_like(sc, fill_value=float(j)))
-    return torch.cat(out_b), torch.cat(out_s), torch.cat(out_c)
-
-
 def nms_rotated_sorted(boxes: Tensor, iou_threshold: float, cats: Tensor = None) -> Tensor:
     """``rv_nms_rotated``: rectangles (n,5) [x1,y1,x2,y2,ry] SORTED by score descending (``cats``: optional class per box, boxes of
     different classes do not interact) -> sorted positions of the kept boxes, ascending, int64 on the device."""
@@ -149,33 +123,55 @@ def nms_rotated_sorted(boxes: Tensor, iou_threshold: float, cats: Tensor = None)
     return keep[: int(num_out.value)]
 
 
-def hard_multiclass_nms(cuboids_i: Tensor, scores_i: Tensor, categories_i: Tensor, iou_threshold: float, num_pre_nms: int,
-                        num_post_nms: int) -> Tuple[Tensor, Tensor, Tensor]:
-    """Per class (ascending ``unique``): top-k pre, hard rotated NMS, top-k post (``nms.py:10-61``); rows are input rows."""
+def _multiclass_nms(mode: str, cuboids_i: Tensor, scores_i: Tensor, categories_i: Tensor, iou_threshold: float, num_pre_nms: int,
+                    num_post_nms: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """One sweep: the device-resident path when it fits, else per class (ascending ``unique``) top-k pre, NMS over the list FFI,
+    top-k post."""
     n = scores_i.shape[0]
     if 0 < n <= FUSED_CLASSES_MAX:
         n_cls = int(categories_i.max().item()) + 1
         if n_cls <= 64:
             b, s, c, cnt = nms_sweeps(cuboids_i[None], scores_i[None], categories_i[None], n_cls, iou_threshold, -math.inf, num_post_nms, _capacity(n),
-                                      num_pre_nms, mode="HARD")
+                                      num_pre_nms, mode=mode)
             return b[0, : cnt[0]], s[0, : cnt[0]], c[0, : cnt[0]].to(s.dtype)
-    out_b: List[Tensor] = []
-    out_s: List[Tensor] = []
-    out_c: List[Tensor] = []
+    rows: List[Tuple[Tensor, Tensor, Tensor]] = []
     for j in categories_i.unique():
         sel = categories_i == j
         s, b = scores_i[sel], cuboids_i[sel]
-        # (``topk`` leaves the order of equal scores open; the declared rule is ascending index: a stable sort)
-        s, rank = s.sort(dim=0, descending=True, stable=True)
         k = min(len(s), num_pre_nms)
-        s, b = s[:k], b[rank[:k]]
+        if mode == "HARD":
+            # (``topk`` leaves the order of equal scores open; the declared rule is ascending index: a stable sort)
+            s, rank = s.sort(dim=0, descending=True, stable=True)
+            s, rank = s[:k], rank[:k]
+        else:
+            s, rank = s.topk(k=k, dim=0)
+        b = b[rank]
         half = b[:, 3:5] / 2
         rect = torch.cat([b[:, :2] - half, b[:, :2] + half, b[:, 6:7]], dim=-1)
-        keep = nms_rotated_sorted(rect, iou_threshold)[:num_post_nms]  # kept rows are in descending score order: top-k = prefix
-        out_b.append(b[keep])
-        out_s.append(s[keep])
-        out_c.append(torch.full_like(out_s[-1], fill_value=float(j)))
-    return torch.cat(out_b), torch.cat(out_s), torch.cat(out_c)
+        if mode == "HARD":
+            keep = nms_rotated_sorted(rect, iou_threshold)[:num_post_nms]  # kept rows are in descending score order: top-k = prefix
+            b, s = b[keep], s[keep]
+        else:
+            data = torch.cat([b[:, :6], b[:, 6:7].sin(), b[:, 6:7].cos()], dim=1)
+            _, merged, _ = weighted_nms(rect, data, s, nms_threshold=iou_threshold, merge_thresh=0.5)
+            box6, sn, cs, sc = merged.split([6, 1, 1, 1], dim=1)
+            b = torch.cat([box6, torch.atan2(sn, cs)], dim=1)
+            s, rank = sc.flatten().topk(k=min(len(b), num_post_nms), dim=0)
+            b = b[rank]
+        rows.append((b, s, torch.full_like(s, fill_value=float(j))))
+    return tuple(torch.cat(col) for col in zip(*rows))
+
+
+def weighted_multiclass_nms(cuboids_i: Tensor, scores_i: Tensor, categories_i: Tensor, iou_threshold: float, num_pre_nms: int,
+                            num_post_nms: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Per class (ascending ``unique``): top-k pre, weighted NMS with merge threshold 0.5 (``nms.py:105-106``), top-k post."""
+    return _multiclass_nms("WEIGHTED", cuboids_i, scores_i, categories_i, iou_threshold, num_pre_nms, num_post_nms)
+
+
+def hard_multiclass_nms(cuboids_i: Tensor, scores_i: Tensor, categories_i: Tensor, iou_threshold: float, num_pre_nms: int,
+                        num_post_nms: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """Per class (ascending ``unique``): top-k pre, hard rotated NMS, top-k post (``nms.py:10-61``); rows are input rows."""
+    return _multiclass_nms("HARD", cuboids_i, scores_i, categories_i, iou_threshold, num_pre_nms, num_post_nms)
 
 
 def batched_multiclass_nms(cuboids: Tensor, scores: Tensor, categories: Tensor, num_pre_nms: int, num_post_nms: int,

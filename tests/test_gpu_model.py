@@ -8,6 +8,7 @@ Tolerances: see test_gpu_forward.py / test_gpu_backward.py; additionally
 
 from __future__ import annotations
 
+import functools
 import math
 
 import numpy as np
@@ -427,8 +428,9 @@ def test_batched_multiclass_nms_matches_oracle():
 
 
 def test_fused_multiclass_nms_equals_per_class_loop():
-    """One class-aware launch (rv_wnms_classes) == the reference-shaped per-class loop, row for row and bit for bit
-    (classes do not interact; within a class the score order and therefore every merge sum is the same)."""
+    """The device-resident path (rv_nms_sweeps, all classes of the sweep in one set of launches) == the reference-shaped per-class
+    loop over rv_wnms, row for row and bit for bit (classes do not interact; within a class the score order and therefore every
+    merge sum is the same)."""
     from range_view_3d_detection_amd.math.ops import nms as hnms
 
     cub, s = _random_boxes(6000, 77, 60.0)
@@ -444,6 +446,67 @@ def test_fused_multiclass_nms_equals_per_class_loop():
     assert fused[0].shape == loop[0].shape and fused[0].shape[0] > 26 * 20
     for a, b in zip(fused, loop):
         assert torch.equal(a, b)
+
+
+@functools.lru_cache(maxsize=None)
+def _class_list_case(n, seed, spread):
+    """A score-sorted list of three classes (rectangles, merge rows with the score last, class ids) and what the C oracle keeps when
+    it is run class by class: list position -> (merged row, cluster size)."""
+    from oracle import nms as onms
+
+    cub, scores = _random_boxes(n, seed, spread)
+    cat = torch.randint(0, 3, (n,), generator=torch.Generator().manual_seed(seed))
+    scores, order = scores.sort(0, descending=True)
+    cub, cat = cub[order], cat[order].to(torch.int32)
+    half = cub[:, 3:5] / 2
+    rect = torch.cat([cub[:, :2] - half, cub[:, :2] + half, cub[:, 6:7]], dim=-1).contiguous()
+    data = torch.cat([cub[:, :6], cub[:, 6:7].sin(), cub[:, 6:7].cos(), scores[:, None]], dim=1).contiguous()
+    want = {}
+    for c in range(3):
+        idx = (cat == c).nonzero().flatten()
+        keep, out, cnt = onms.weighted_nms(rect[idx], data[idx, :-1], scores[idx], 0.3, 0.5)
+        want.update({int(i): (row, int(m)) for i, row, m in zip(idx[keep], out, cnt)})
+    return rect, data, cat, want
+
+
+@pytest.mark.parametrize("n,seed,spread,operand", [(65, 11, 8.0, "bf16"), (200, 12, 12.0, "bf16"), (200, 12, 12.0, "f16")])
+def test_wnms_classes_equals_rv_wnms_per_class_and_the_oracle(n, seed, spread, operand):
+    """One ``rv_wnms_classes`` launch over a list of three classes == ``rv_wnms`` run once per class on that class's rows in the same
+    order == the C oracle per class: the kept set is the union of the per-class kept boxes (as list positions) and every kept box has
+    its class's merged row and cluster size, bit for bit.  n = 65 is the smallest list with a column block beyond the diagonal;
+    n = 200 has four mask words (the later-word fold of the scan).  Both inputs suppress and merge (oracle: 39 of 65 kept, largest
+    cluster 2; 105 of 200, largest cluster 4)."""
+    import ctypes
+
+    from range_view_3d_detection_amd import _lib as L
+    from range_view_3d_detection_amd.math.ops import nms as hnms
+
+    rect, data, cat, want = _class_list_case(n, seed, spread)
+    assert len(want) < n and max(m for _, m in want.values()) > 1  # the inputs suppress and merge
+    rect_d, data_d, cat_d = rect.to(DEV), data.to(DEV), cat.to(DEV)
+
+    def buffers(rows):
+        return (torch.zeros((rows, 9), dtype=torch.float32, device=DEV), torch.zeros(rows, dtype=torch.long, device=DEV),
+                torch.zeros(rows, dtype=torch.long, device=DEV))
+
+    with L.operand(operand):
+        out, keep, count = buffers(n)
+        ws = torch.empty(L.load().rv_wnms_workspace_bytes(n), dtype=torch.uint8, device=DEV)
+        num_out = ctypes.c_int64(0)
+        L.call("rv_wnms_classes", L.ptr(rect_d), L.ptr(data_d), L.ptr(cat_d), n, 9, 0.3, 0.5, L.ptr(out), L.ptr(keep), L.ptr(count),
+               L.ptr(ws), ctypes.byref(num_out), L.stream_ptr())
+        k = int(num_out.value)
+        per_class = {}
+        for c in range(3):
+            idx = (cat_d == c).nonzero().flatten()
+            out_c, keep_c, count_c = buffers(len(idx))
+            k_c = hnms.wnms_sorted(rect_d[idx].contiguous(), data_d[idx].contiguous(), out_c, keep_c, count_c, 0.3, 0.5)
+            per_class.update({int(i): (row, int(m)) for i, row, m in zip(idx[keep_c[:k_c]].tolist(), out_c[:k_c].cpu(), count_c[:k_c].tolist())})
+    assert keep[:k].tolist() == sorted(per_class) == sorted(want) and 0 < k < n
+    assert (out[k:] == 0).all() and (count[k:] == 0).all()
+    for i, row, m in zip(keep[:k].tolist(), out[:k].cpu(), count[:k].tolist()):
+        assert m == per_class[i][1] == want[i][1], i
+        assert torch.equal(row, per_class[i][0]) and torch.equal(row, want[i][0]), i
 
 
 def test_detections_wire_format_from_device_decode(golden, tmp_path):
