@@ -529,6 +529,34 @@ int rv_wnms(const float* boxes, const float* data, int64_t n, int32_t d, float n
 int rv_wnms_classes(const float* boxes, const float* data, const int32_t* cats, int64_t n, int32_t d, float nms_thresh,
                     float merge_thresh, float* output, int64_t* keep, int64_t* count, void* workspace,
                     int64_t* host_num_out, rvStream stream);
+/* The declared choices as PER-CALL options (the library keeps no option state).  oracle/nms.py declares the semantics because the
+ * third-party kernel's source is absent; the declaration contains four free choices, and these four are the axes along which a
+ * third-party `wnms_gpu` may differ from the declaration.  A clear bit is the declaration (what rv_wnms / rv_wnms_classes /
+ * rv_nms_sweeps compute); a set bit is the other reading:
+ *   RV_WNMS_MERGE_SUPPRESSED  merge set: the cluster of kept box i is i plus EVERY later box j > i of its class whose IoU with i
+ *                             passes the merge test, whether or not j was suppressed before i was visited -- a box may be a
+ *                             member of several clusters, and `count` follows the cluster.  Clear: only the boxes not yet
+ *                             suppressed at i's visit.  Suppression itself is the same.
+ *   RV_WNMS_SCORE_KEEPER      score column: the LAST column of an output row is the kept box's own score, data[i][d-1], copied bit
+ *                             for bit; the other d-1 columns stay the score-weighted means.  Clear: the last column is the weighted
+ *                             mean too (sum s^2 / sum s).  In the batch entry the per-class top-k then ranks by the kept scores.
+ *   RV_WNMS_NMS_GE            a kept box suppresses a later box when iou >= nms_thresh.  Clear: iou > nms_thresh.
+ *   RV_WNMS_MERGE_GE          a box joins a cluster when iou >= merge_thresh.  Clear: iou > merge_thresh.
+ * Members are visited in ascending index order under every setting (fixed summation order).  With a `>=` test against a threshold
+ * <= 0 every pair of a class passes, far-apart pairs (IoU 0) included.  Which setting a given third-party build is stays unpinned
+ * until its `wnms_gpu` is run through tests/tools/pin_wnms.py.
+ *
+ * rv_wnms_opt: the arguments of rv_wnms_classes (cats may be NULL) and `flags`; rv_nms_sweeps_opt (below): those of rv_nms_sweeps
+ * and `flags`.  Same workspaces, same `resume` / `out_counts` protocol, same launches; flags = 0 is rv_wnms_classes /
+ * rv_nms_sweeps bit for bit (those entries are calls of these).  A bit outside the four fails (rv_last_error). */
+#define RV_WNMS_MERGE_SUPPRESSED 1
+#define RV_WNMS_SCORE_KEEPER 2
+#define RV_WNMS_NMS_GE 4
+#define RV_WNMS_MERGE_GE 8
+/* The two prototypes live in include/rv3d_wnms.h, which this line makes part of this header (a C / C++ caller needs rv3d.h only):
+ * this file's own list of prototypes stays the list that the binding's census counts, and the binding (`_lib.py`) types the entries
+ * of an included header exactly as it types this file's. */
+#include "rv3d_wnms.h"
 /* pairwise rotated BEV IoU (n x m), exposed for tests */
 /* The whole post-decode path of a BATCH of sweeps, device-resident from end to end (csrc/nms2.hip): confidence filter +
  * compaction, (class, score) ordering, class-segmented weighted NMS (one scan workgroup per class), per-class top-k by

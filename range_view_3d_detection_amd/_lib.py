@@ -1,7 +1,8 @@
 """ctypes binding of ``librv3d_hip.so`` (the C ABI declared in ``include/rv3d.h``).
 
-``include/rv3d.h`` is the single source of the binding's types: ``prototypes()`` parses its declarations once per process and
-``load()`` sets ``restype`` / ``argtypes`` of every declared symbol from them.  Call sites pass plain Python values (``int``,
+``include/rv3d.h`` is the single source of the binding's types: ``prototypes()`` parses the declarations in its own text once per
+process, ``included_prototypes()`` those of the headers it includes (``rv3d_wnms.h``), and ``load()`` sets ``restype`` / ``argtypes`` of
+every symbol of both tables.  Call sites pass plain Python values (``int``,
 ``float``, ``None``, ``ptr(t)``, a ctypes Structure or array); a wrong argument count or a wrong struct raises in Python.
 
 There is deliberately no CPU fallback: if the library is missing or a call fails the host
@@ -35,6 +36,7 @@ SEL_SMALL_GRIDS, SEL_SMALL_GRIDS6, SEL_NO_GEN6, SEL_NO_GEN5, SEL_NO_POINTWISE, S
 SELECT = 0
 EW_RELU_A, EW_RELU_B, EW_RELU_OUT = 1, 2, 4
 BNB_RELU_Z, BNB_RES_ACCUM, BNB_Y_FROM_INPUT = 1, 2, 4
+WNMS_MERGE_SUPPRESSED, WNMS_SCORE_KEEPER, WNMS_NMS_GE, WNMS_MERGE_GE = 1, 2, 4, 8  # RV_WNMS_* (rv_wnms_opt / rv_nms_sweeps_opt: per call)
 # rv_ew_pass_info: passes and kernel forms (RV_EW_PASS_* / RV_EW_FORM_*)
 EW_PASS_COMBINE, EW_PASS_MASK_GRAD, EW_PASS_BN_FINALIZE, EW_PASS_BWD_REDUCE, EW_PASS_BWD_REDUCE_PAIR, EW_PASS_BWD_FINALIZE, EW_PASS_BWD_APPLY, EW_PASS_BWD_APPLY_PAIR = range(8)
 EW_FORM_COMB, EW_FORM_ROWS, EW_FORM_OCTET, EW_FORM_LEAN, EW_FORM_FUSED_FINALIZE, EW_FORM_TWO_STAGE = range(1, 7)
@@ -193,10 +195,8 @@ def _ctype(decl: str, symbol: str):
     raise RvError(f"include/rv3d.h: cannot map the type {decl!r} in the declaration of {symbol}")
 
 
-@functools.lru_cache(maxsize=None)
-def prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
-    """``name -> (restype, ((ctype, parameter name), ...))`` of every function declared in include/rv3d.h."""
-    text = open(HEADER_PATH).read()
+def _parse_header(path: str) -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    text = open(path).read()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
     text = re.sub(r"typedef\s+struct\b[^{;]*\{.*?\}[^;]*;", "", text, flags=re.S)
@@ -211,7 +211,28 @@ def prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
         table[name] = (_ctype(ret, name), tuple(plist))
     unparsed = set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", text)) - set(table)
     if unparsed:
-        raise RvError(f"include/rv3d.h: cannot parse the declaration of {sorted(unparsed)}")
+        raise RvError(f"include/{os.path.basename(path)}: cannot parse the declaration of {sorted(unparsed)}")
+    return table
+
+
+@functools.lru_cache(maxsize=None)
+def prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    """``name -> (restype, ((ctype, parameter name), ...))`` of every function declared in include/rv3d.h itself."""
+    return _parse_header(HEADER_PATH)
+
+
+@functools.lru_cache(maxsize=None)
+def included_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    """The same table for the headers that include/rv3d.h pulls in with ``#include "name.h"`` (``rv3d_wnms.h``: the weighted-NMS
+    entries with per-call choices), from the directory of the header.  ``load()`` types these entries like the header's own; a
+    header that is named but missing is an error."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER_PATH).read(), flags=re.S)
+    table = {}
+    for name in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', text, flags=re.M):
+        path = os.path.join(os.path.dirname(HEADER_PATH), name)
+        if not os.path.exists(path):
+            raise RvError(f"{HEADER_PATH} includes {name!r}, which is missing")
+        table.update(_parse_header(path))
     return table
 
 
@@ -247,11 +268,11 @@ def _dlopen(path: str) -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     # restype / argtypes of every declared symbol; the parameter names make ctypes refuse extra arguments too (a bare cdecl
     # function pointer ignores them) and accept them as keywords
-    for name, (restype, params) in prototypes().items():
+    for name, (restype, params) in {**prototypes(), **included_prototypes()}.items():
         try:
             fn = ctypes.CFUNCTYPE(restype, *[t for t, _ in params])((name, lib), tuple((1, p) for _, p in params))
         except AttributeError:
-            raise RvError(f"{path} does not export {name}, which include/rv3d.h declares") from None
+            raise RvError(f"{path} does not export {name}, which include/rv3d.h (or a header it includes) declares") from None
         setattr(lib, name, fn)
     return lib
 

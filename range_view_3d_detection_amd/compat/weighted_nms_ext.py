@@ -14,6 +14,10 @@ Post-conditions the caller asserts (``nms.py:173-174``): ``output[num_out:] == 0
 
 The arithmetic is ``rv_wnms`` (csrc/nms.hip; declared semantics in oracle/nms.py -- the TorchEx source is not part of the
 reference tree, parity unpinned).  No CPU fallback: host tensors for boxes/data raise.
+
+``wnms_gpu`` keeps TorchEx's fixed signature, so the declaration's free choices (``WnmsSemantics``) cannot be an argument:
+``with weighted_nms_ext.semantics(s):`` governs the calls inside the block.  That is module-level state, acceptable only here -- in a
+module that imitates a third-party one; everywhere else the setting is a per-call argument.  Outside any block the declaration applies.
 """
 
 from __future__ import annotations
@@ -22,7 +26,27 @@ import torch
 from torch import Tensor
 
 from range_view_3d_detection_amd import _lib as L
-from range_view_3d_detection_amd.math.ops.nms import wnms_sorted
+from range_view_3d_detection_amd.math.ops.nms import WnmsSemantics, wnms_sorted
+
+_SEMANTICS = None  # the setting of the innermost `semantics(...)` block; None: the declaration
+
+
+class semantics:
+    """``with semantics(WnmsSemantics(...)):`` -- ``wnms_gpu`` inside the block computes under that setting."""
+
+    def __init__(self, setting: WnmsSemantics) -> None:
+        if not isinstance(setting, WnmsSemantics):
+            raise L.RvError(f"semantics() takes a WnmsSemantics, got {type(setting).__name__}")
+        self.setting = setting
+
+    def __enter__(self):
+        global _SEMANTICS
+        self.old, _SEMANTICS = _SEMANTICS, self.setting
+        return self
+
+    def __exit__(self, *exc):
+        global _SEMANTICS
+        _SEMANTICS = self.old
 
 
 def wnms_gpu(boxes: Tensor, data2merge_score: Tensor, output: Tensor, keep: Tensor, count: Tensor, nms_thresh: float,
@@ -45,6 +69,6 @@ def wnms_gpu(boxes: Tensor, data2merge_score: Tensor, output: Tensor, keep: Tens
         return 0
     with torch.cuda.device(boxes.device):
         keep_dev = torch.empty(n, dtype=torch.int64, device=boxes.device)
-        k = wnms_sorted(boxes, data2merge_score, output, keep_dev, count, nms_thresh, merge_thresh)
+        k = wnms_sorted(boxes, data2merge_score, output, keep_dev, count, nms_thresh, merge_thresh, _SEMANTICS)
         keep[:k].copy_(keep_dev[:k])  # device -> host, synchronous
     return k

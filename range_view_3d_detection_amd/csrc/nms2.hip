@@ -40,6 +40,8 @@
 //                  position = class base + index among the class's kept boxes, dropped at >= num_post_nms -- no ranking pass;
 //                  the 7 floats and the score are copied from the caller's `cuboids` / `scores` rows (order -> cand), so every
 //                  output row is an input row bit for bit (the yaw never passes through sin / cos / atan2).
+// rv_nms_sweeps_opt carries the weighted-NMS choices (RV_WNMS_*, include/rv3d.h) in Args::flags: stages 4, 5 and 7 read them where
+// nms_core.h makes the choice, and stage 8 ranks by whatever stage 7 stored as the score; rv_nms_sweeps is that entry with 0.
 // The pair loop of stage 4, the word scan of stage 5 and the cluster sum of stage 7 are nms_core.h's, shared with the list path
 // (nms.hip); the kernels here load rows and tiles from the sweep's sorted arrays, address the class-relative masks (`mword`) and
 // record kept boxes as flags.
@@ -79,6 +81,7 @@ struct Args {
     int64_t mask_words;           // word budget per sweep and mask
     int32_t B, cap, cb, n_classes, num_post, num_pre, out_cap;
     int32_t n_masks;        // 2: weighted (suppression + merge masks); 1: hard (suppression mask only)
+    int32_t flags;          // RV_WNMS_* (weighted only; hard: 0)
     float min_conf, nms_t, merge_t;
     float* out_boxes;       // [B][cap][7]
     float* out_scores;      // [B][cap]
@@ -272,7 +275,7 @@ __device__ void k_iou_block(const Args& a, const SweepPtrs& p, int n, int row, i
     const float sa = p.sc[2 * i], ca = p.sc[2 * i + 1];
     unsigned long long bits_n, bits_m;
     // (columns end at the pre-NMS cut)
-    pair_bits<HARD>(tile, (int)(n - j0 < 64 ? n - j0 : 64), bx, sa, ca, cat_i, i, j0, send_i, a.nms_t, a.merge_t, bits_n, bits_m);
+    pair_bits<HARD>(tile, (int)(n - j0 < 64 ? n - j0 : 64), bx, sa, ca, cat_i, i, j0, send_i, a.nms_t, a.merge_t, a.flags, bits_n, bits_m);
     const int64_t mw = mword(p, cat_i, (int)i, col);
     p.nms_mask[mw] = bits_n;
     if constexpr (!HARD) p.merge_mask[mw] = bits_m;
@@ -316,6 +319,7 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
     if (s0 >= s1 || !masks_fit(a, p)) return;
     extern __shared__ unsigned long long remv[];  // words w0 .. w1
     __shared__ unsigned long long kept_word;
+    const bool merge_all = !HARD && (a.flags & kWnmsMergeSuppressed);
     const int w0 = s0 >> 6, w1 = (s1 - 1) >> 6;
     for (int w = threadIdx.x; w <= w1 - w0; w += blockDim.x) remv[w] = 0ull;
     __syncthreads();
@@ -326,10 +330,12 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
             const bool in_seg = i >= s0 && i < s1;
             const unsigned long long diag = in_seg ? p.nms_mask[mword(p, cls, i, wi)] : 0ull;
             unsigned long long rem = remv[wi - w0], kept, alive_mine;
-            scan_diagonal<HARD>(diag, __ballot(in_seg), b, rem, kept, alive_mine);
+            scan_diagonal<HARD>(diag, __ballot(in_seg), b, merge_all, rem, kept, alive_mine);
             if ((kept >> b) & 1ull) {
                 p.kept[i] = 1;
-                if constexpr (!HARD) p.merge_mask[mword(p, cls, i, wi)] &= alive_mine;  // cluster = merge candidates not suppressed before i was visited
+                // cluster = merge candidates not suppressed before i was visited (merge_all: all of them)
+                if constexpr (!HARD)
+                    if (!merge_all) p.merge_mask[mword(p, cls, i, wi)] &= alive_mine;
             }
             if (b == 0) {
                 remv[wi - w0] = rem;
@@ -340,7 +346,7 @@ __global__ __launch_bounds__(256) void k_scan(const Args a) {
         const unsigned long long kept = kept_word;
         // (a word at the segment's edge may hold bits of the neighbouring class: k_iou never sets those -- class check)
         for (int w = wi + 1 + threadIdx.x; w <= w1; w += blockDim.x)
-            remv[w - w0] = scan_fold<HARD>(remv[w - w0], kept, p.nms_mask, p.merge_mask, [&](int q) { return mword(p, cls, wi * 64 + q, w); });
+            remv[w - w0] = scan_fold<HARD>(remv[w - w0], kept, merge_all, p.nms_mask, p.merge_mask, [&](int q) { return mword(p, cls, wi * 64 + q, w); });
         __syncthreads();
     }
 }
@@ -379,7 +385,8 @@ __global__ __launch_bounds__(64) void k_merge(const Args a) {
     float acc, wsum;
     long long members;  // (not reported on this path)
     cluster_sum(p.data, 9, c, i, i >> 6, w1, [&](int w) { return p.merge_mask[mword(p, cls, i, w)]; }, acc, wsum, members);
-    if (c < 9) p.merged[(int64_t)o * 9 + c] = acc / wsum;
+    // (kWnmsScoreKeeper: k_post then ranks the class by the kept boxes' own scores)
+    if (c < 9) p.merged[(int64_t)o * 9 + c] = (a.flags & kWnmsScoreKeeper) && c == 8 ? p.data[(int64_t)i * 9 + 8] : acc / wsum;
     }
 }
 
@@ -498,13 +505,14 @@ template <bool HARD>
 int launch_sweeps(const char* who, const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
                   float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms, int32_t cap,
                   int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts, void* workspace,
-                  void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
+                  void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream, int32_t flags) {
     RV_REQUIRE(scores && cats && cuboids && out_boxes && out_scores && out_cats && out_counts && workspace && mask_workspace,
                "%s: null argument", who);
     RV_REQUIRE(B > 0 && K > 0 && cap >= 64 && cap % 64 == 0 && cap <= 262144, "%s: bad sizes (cap: multiple of 64, <= 262144)", who);
     RV_REQUIRE(n_classes >= 1 && n_classes <= kMaxClasses, "%s: 1..%d classes", who, kMaxClasses);
     RV_REQUIRE(num_post_nms >= 1 && num_pre_nms >= 1, "%s: num_pre_nms / num_post_nms must be positive", who);
     RV_REQUIRE(mask_words >= 1, "%s: mask_words must be positive", who);
+    RV_REQUIRE((flags & ~kWnmsAll) == 0, "%s: unknown flag bits 0x%x (RV_WNMS_*: 0x%x)", who, (unsigned)(flags & ~kWnmsAll), (unsigned)kWnmsAll);
     const int64_t rows_max = (int64_t)n_classes * num_post_nms < cap ? (int64_t)n_classes * num_post_nms : cap;
     RV_REQUIRE(out_cap >= rows_max, "%s: out_cap %d below min(cap, n_classes * num_post_nms) = %lld", who, out_cap, (long long)rows_max);
     Args a;
@@ -513,6 +521,7 @@ int launch_sweeps(const char* who, const float* scores, const int64_t* cats, con
     a.mask_ws = (unsigned long long*)mask_workspace;
     a.mask_words = mask_words;
     a.n_masks = HARD ? 1 : 2;
+    a.flags = HARD ? 0 : flags;
     a.cb = (cap + 63) / 64;
     a.ws_stride = sweep_bytes(cap, a.cb);
     a.K = K; a.B = B; a.cap = cap; a.n_classes = n_classes; a.num_post = num_post_nms; a.num_pre = num_pre_nms; a.out_cap = out_cap;
@@ -555,9 +564,17 @@ extern "C" int rv_nms_sweeps(const float* scores, const int64_t* cats, const flo
                              float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms,
                              int32_t cap, int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts,
                              void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
+    return rv_nms_sweeps_opt(scores, cats, cuboids, B, K, n_classes, min_confidence, nms_thresh, merge_thresh, num_pre_nms, num_post_nms, cap,
+                             out_cap, out_boxes, out_scores, out_cats, out_counts, workspace, mask_workspace, mask_words, resume, stream, 0);
+}
+
+extern "C" int rv_nms_sweeps_opt(const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
+                                 float min_confidence, float nms_thresh, float merge_thresh, int32_t num_pre_nms, int32_t num_post_nms,
+                                 int32_t cap, int32_t out_cap, float* out_boxes, float* out_scores, int32_t* out_cats, int64_t* out_counts,
+                                 void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream, int32_t flags) {
     return launch_sweeps<false>("rv_nms_sweeps", scores, cats, cuboids, B, K, n_classes, min_confidence, nms_thresh, merge_thresh, num_pre_nms,
                                 num_post_nms, cap, out_cap, out_boxes, out_scores, out_cats, out_counts, workspace, mask_workspace, mask_words,
-                                resume, stream);
+                                resume, stream, flags);
 }
 
 extern "C" int rv_nms_sweeps_hard(const float* scores, const int64_t* cats, const float* cuboids, int32_t B, int64_t K, int32_t n_classes,
@@ -566,5 +583,5 @@ extern "C" int rv_nms_sweeps_hard(const float* scores, const int64_t* cats, cons
                                   void* workspace, void* mask_workspace, int64_t mask_words, int32_t resume, rvStream stream) {
     return launch_sweeps<true>("rv_nms_sweeps_hard", scores, cats, cuboids, B, K, n_classes, min_confidence, iou_threshold, 0.f, num_pre_nms,
                                num_post_nms, cap, out_cap, out_boxes, out_scores, out_cats, out_counts, workspace, mask_workspace, mask_words,
-                               resume, stream);
+                               resume, stream, 0);
 }

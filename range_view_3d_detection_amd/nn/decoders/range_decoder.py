@@ -71,13 +71,16 @@ class RangeDecoder:
                 boxes_l.append(b)
         scores, cats, params = torch.cat(scores_l, 1), torch.cat(cats_l, 1), torch.cat(boxes_l, 1)
         if use_nms:
-            from ...math.ops.nms import batched_multiclass_nms
+            from ...math.ops.nms import WnmsSemantics, batched_multiclass_nms
 
+            # optional `wnms_semantics:` block (absent from every shipped conf: the declared weighted-NMS semantics)
+            wnms = post_processing_config["wnms_semantics"] if "wnms_semantics" in post_processing_config else None
             params, scores, cats, batch_index = batched_multiclass_nms(
                 params, scores, cats,
                 num_pre_nms=post_processing_config["num_pre_nms"], num_post_nms=post_processing_config["num_post_nms"],
                 iou_threshold=post_processing_config["nms_threshold"], min_confidence=post_processing_config["min_confidence"],
                 nms_mode=post_processing_config["nms_mode"], n_classes=sum(len(g) for g in task_config.values()),
+                semantics=None if wnms is None else WnmsSemantics.from_config(wnms),
             )
         else:
             B, N, _ = params.shape
