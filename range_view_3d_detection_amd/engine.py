@@ -184,9 +184,7 @@ def tap_kernel_name(geom, shape, scatter: bool) -> str:
     info = L.tap_launch_info(geom, shape, scatter)
     if info is None:
         raise L.RvError(f"rv_tap_launch_info failed: {L.load().rv_last_error().decode()}")
-    if info[0] in (4, 5, 6):
-        name = f"tapconv{info[0]}_kernel<{info[1]}>"
-    elif info[0] in (2, 3):
+    if info[0] in (2, 3, 4, 5, 6):
         name = f"tapconv{info[0]}_kernel<{info[1]}>"
     elif info[0] == 7:
         name = f"pointwise_kernel<{info[1]}>"
@@ -406,7 +404,7 @@ def _require_cuda(t: Tensor, what: str) -> None:
 class Act:
     """NHWC bf16 activation (or activation gradient): ``data`` is (N,H,W,C) with strides (H*W*ld, W*ld, ld, 1)."""
 
-    __slots__ = ("data", "c", "parent", "c0", "_rv_owned")
+    __slots__ = ("data", "c", "parent", "c0")
 
     def __init__(self, data: Tensor, c: Optional[int] = None, parent: Optional["Act"] = None, c0: int = 0) -> None:
         assert data.dtype in (torch.bfloat16, torch.float16) and data.dim() == 4 and data.stride(3) == 1
@@ -414,7 +412,6 @@ class Act:
         self.c = data.shape[3] if c is None else c  # logical channels (<= stored, stored is a multiple of 32)
         self.parent = parent
         self.c0 = c0
-        self._rv_owned = False  # True: a gradient buffer private to the tape (safe to accumulate into)
 
     @staticmethod
     def empty(n: int, h: int, w: int, c: int, device, zero: bool = False) -> "Act":
@@ -505,6 +502,52 @@ class Lazy:
 
 
 Operand = Union[Act, Lazy]
+
+
+def ptr_ld(a: Optional[Act]) -> tuple:
+    """(pointer, pixel pitch) of an optional ``Act`` operand (a ReLU mask, a residual): (NULL, 0) when there is none."""
+    return (a.ptr(), a.ld) if a is not None else (None, 0)
+
+
+def partial_rows(rows: int, cp: int, device) -> Tensor:
+    """fp32 buffer for ``rows`` partial (sum, sum) rows over ``cp`` channels plus the scratch rows the statistics kernels use."""
+    return torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, cp), dtype=torch.float32, device=device)
+
+
+# Gradient pending for a Lazy until the tape reaches its BnOp (``Tape.pending``): ONE record per Lazy, in one of three forms.
+@dataclass(eq=False, slots=True)
+class BnbSums:  # BatchNorm-backward (sum g, sum g*xhat) rows that the one writer of a PendingGrad formed on the way
+    partial: Tensor
+    rows: int
+    over: Act             # the gradient Act they were formed over: valid only while that very object is the entry's ``dout``
+    masked: bool = False  # formed over dout * [block output > 0] (the pair reduce) rather than over the plain dout (backward-data epilogue)
+
+
+@dataclass(eq=False, slots=True)
+class PendingGrad:  # dout * [mask > 0] (mask None: dout); res = (buffer, accumulate): the apply pass also emits it for a residual branch
+    dout: Act
+    mask: Optional[Act] = None
+    res: Optional[Tuple[Act, bool]] = None
+    owned: bool = False  # dout is a buffer private to the tape (safe to accumulate into)
+    sums: Optional[BnbSums] = None
+
+
+@dataclass(eq=False, slots=True)
+class PendingMeta:  # MetaKernel modulation fused into the BatchNorm backward of the positional layer (engine_bwd.modulate_backward)
+    dgeo: Act
+    feat: Act
+    partial: Tensor
+    rows: int
+
+
+@dataclass(eq=False, slots=True)
+class PendingHeadFinal:  # a tower's final conv fused into the BatchNorm backward of the unit before it (engine_bwd._head_final_sums)
+    head: tuple  # leading arguments shared by rv_head_final_bwd_sums / _apply
+    partial: Tensor
+    rows: int
+    dY: Act
+    wp: Tensor   # the final conv's scatter image
+
 
 # The LDS-DMA tap-conv (tapconv4) streams its operands global -> LDS without passing through registers, so it cannot
 # apply a folded BatchNorm(+ReLU) on the way in.  On the layers it is eligible for it is enough faster than the
@@ -793,15 +836,10 @@ class Tape:
         # backward state
         self.grads: Dict[int, Act] = {}          # id(root Act) -> gradient Act (same padded shape)
         self.written: set = set()                # ids of gradient Acts (roots) already holding a value
-        self.lazy_in: Dict[int, Tuple[Act, Optional[Act]]] = {}  # id(Lazy) -> (dOut, OUT mask source)
-        self.lazy_sums: Dict[int, Tuple[Tensor, int]] = {}  # id(Lazy) -> BatchNorm-backward partial sums its ONE writer formed, rows
-        self.meta_in: Dict[int, tuple] = {}      # id(Lazy) -> (dgeo, feat, partial sums, rows): MetaKernel modulation fused into the BatchNorm backward
-        self.head_final: Dict[int, tuple] = {}   # id(Lazy) -> (call head, BatchNorm-backward partial sums, rows, dY of the tower's final conv, its scatter image)
-        self.producers: Dict[int, "Op"] = {}     # id(block-output Act) -> the CombineOp that made it
+        self.pending: Dict[int, Union[PendingGrad, PendingMeta, PendingHeadFinal]] = {}  # id(Lazy) -> gradient waiting for its BnOp
         self.bn_of: Dict[int, "Op"] = {}         # id(Lazy) -> its BnOp
         self.raw_grad: Dict[int, Act] = {}       # id(raw Act) -> gradient w.r.t. the raw conv output
-        self._param_grads: Dict[int, Tensor] = {}  # id(param) -> fp32 gradient (read through `param_grads`)
-        self.params: Dict[int, nn.Parameter] = {}
+        self.param_grads: Dict[int, Tensor] = {}  # id(param) -> fp32 gradient
         self.used_side_stream = False
         self.chained_wgrad = None  # (RV3D_OVERLAP=chain) event behind the last big weight gradient on the side stream
         self.held_wgrads: List = []  # weight-gradient launches held back for a SyncBN all-reduce (engine_bwd._release_held_wgrads)
@@ -841,55 +879,60 @@ class Tape:
         """Buffer a consumer's backward-data kernel writes the gradient w.r.t. ``lazy``'s (activated) value into, and whether
         it must ACCUMULATE: a Lazy may feed several consumers (conv + projection conv of a BasicBlock, say), whose
         contributions add up -- a second writer folds the pending entry into one plain buffer first."""
-        key = id(lazy)
-        prev = self.lazy_in.get(key)
-        self.lazy_sums.pop(key, None)  # (a first writer re-registers its sums after its launch; a second one voids them)
-        if prev is None:
-            dst = lazy.raw.like()
-            dst._rv_owned = True
-            self.lazy_in[key] = (dst, None, None)
-            return dst, False
-        self._flatten_lazy_grad(key)
-        return self.lazy_in[key][0], True
+        e = self._writable(lazy)
+        if e is None:
+            e = self.pending[id(lazy)] = PendingGrad(lazy.raw.like(), owned=True)
+            return e.dout, False
+        self._flatten(e)
+        return e.dout, True
 
-    def add_lazy_grad(self, lazy: "Lazy", dout: Act, mask: Optional[Act], res=None) -> None:
+    def add_lazy_grad(self, lazy: "Lazy", dout: Act, mask: Optional[Act], res=None, owned: bool = False) -> None:
         """Register ``dOut * [mask > 0]`` (mask None: ``dOut``) as (a share of) the gradient w.r.t. ``lazy``'s value; ``res`` =
         (buffer, accumulate) asks the BatchNorm-backward apply pass to also emit that masked gradient for a residual
-        branch -- only possible for a single consumer, otherwise it is written here."""
-        key = id(lazy)
-        self.lazy_sums.pop(key, None)
-        if key not in self.lazy_in:
-            self.lazy_in[key] = (dout, mask, res)
+        branch -- only possible for a single consumer, otherwise it is written here.  ``owned``: ``dout`` is private to the tape."""
+        e = self._writable(lazy)
+        if e is None:
+            self.pending[id(lazy)] = PendingGrad(dout, mask, res, owned)
             return
-        self._flatten_lazy_grad(key)
-        buf = self.lazy_in[key][0]
-        self._masked_into(dout, mask, buf, True)
+        self._flatten(e)
+        self._masked_into(dout, mask, e.dout, True)
         if res is not None:
             self._masked_into(dout, mask, res[0], res[1])
+
+    def _writable(self, lazy: "Lazy") -> Optional[PendingGrad]:
+        """Pending entry of ``lazy`` for one more writer; its sums are void from here on (a first writer registers them AFTER this)."""
+        e = self.pending.get(id(lazy))
+        assert e is None or type(e) is PendingGrad, "a Lazy behind the MetaKernel modulation / a tower's final conv has exactly one consumer"
+        if e is not None:
+            e.sums = None
+        return e
 
     def _masked_into(self, dout: Act, mask: Optional[Act], dst: Act, accumulate: bool) -> None:
-        L.call("rv_ew_mask_grad", dout.pixels, dout.cp, dout.ptr(), dout.ld, mask.ptr() if mask is not None else None,
-               mask.ld if mask is not None else 0, dst.ptr(), dst.ld, 1 if accumulate else 0, L.stream_ptr())
+        L.call("rv_ew_mask_grad", dout.pixels, dout.cp, dout.ptr(), dout.ld, *ptr_ld(mask), dst.ptr(), dst.ld, 1 if accumulate else 0,
+               L.stream_ptr())
 
-    def _flatten_lazy_grad(self, key: int) -> None:
-        dout, mask, res = (self.lazy_in[key] + (None,))[:3]
-        if mask is None and res is None and getattr(dout, "_rv_owned", False):
+    def _flatten(self, e: PendingGrad) -> None:
+        if e.mask is None and e.res is None and e.owned:
             return  # already a private plain buffer
-        buf = dout.like()
-        buf._rv_owned = True
-        self._masked_into(dout, mask, buf, False)
-        if res is not None:
-            self._masked_into(dout, mask, res[0], res[1])
-        self.lazy_in[key] = (buf, None, None)
-
-    @property
-    def param_grads(self) -> Dict[int, Tensor]:
-        return self._param_grads
+        buf = e.dout.like()
+        self._masked_into(e.dout, e.mask, buf, False)
+        if e.res is not None:
+            self._masked_into(e.dout, e.mask, e.res[0], e.res[1])
+        e.dout, e.mask, e.res, e.owned = buf, None, None, True
 
     def add_param_grad(self, p: nn.Parameter, g: Tensor) -> None:
         k = id(p)
-        self.params[k] = p
-        self._param_grads[k] = self._param_grads[k] + g if k in self._param_grads else g  # (a parameter used by two layers: the sum)
+        self.param_grads[k] = self.param_grads[k] + g if k in self.param_grads else g  # (a parameter used by two layers: the sum)
+
+    def add_bn_grads(self, bn: nn.Module, dgamma: Tensor, dbeta: Tensor) -> None:
+        """Parameter gradients of a BatchNorm module from their padded-channel buffers."""
+        c = bn.num_features
+        self.add_param_grad(bn.weight, dgamma[:c])
+        self.add_param_grad(bn.bias, dbeta[:c])
+
+    def add_smallk_wgrad(self, layer: "TapLayer", dw: Tensor) -> None:
+        """Weight gradient of a small-K 1x1 conv from the (padded c_out, c_in) buffer of ``rv_bn_bwd_smallk*``."""
+        self.add_param_grad(layer.weight, layer.unpermute_grad(dw[: layer.c_out].reshape(layer.c_out, layer.c_in, 1, 1).contiguous()))
 
     def backward(self) -> None:
         from . import engine_bwd
@@ -897,7 +940,7 @@ class Tape:
         # Consecutive BatchNorm backward ops (layers whose output gradients are all available: conv_bn_many puts their BnOps
         # next to each other) are independent of one another; under SyncBN their (sum g, sum g*xhat) all-reduces travel as ONE
         # collective: every op of the run forms its local sums first, then one all-reduce, then the finalize + apply passes.
-        pending: List[tuple] = []
+        pending: List["engine_bwd.BnbRecord"] = []
         for op in reversed(self.ops):
             if GROUP_SYNC_BN and isinstance(op, BnOp) and op.sync_world > 1:
                 rec = engine_bwd.bn_backward_begin(op, self)
@@ -947,12 +990,8 @@ class ConvOp(Op):
         src, sc, sh, flags = _operand_parts(x)
         form = layer.fwd_form
         g = layer.geom
-        if form == "gather":
-            wv, wu = src.W, src.W // g.stride_w
-            w_out = wu
-        else:
-            wu, wv = src.W, src.W * g.stride_w
-            w_out = wv
+        wu, wv = (src.W // g.stride_w, src.W) if form == "gather" else (src.W, src.W * g.stride_w)
+        w_out = wu if form == "gather" else wv
         assert src.cp == pad32(layer.c_in), (src.cp, layer.c_in)
         self.x_plain = None
         if _materialize_operand(x, layer, src, wu, wv, out, out_f32, eval_bn):
@@ -993,8 +1032,7 @@ class ConvOp(Op):
             self.rows = L.load().rv_tap_stats_rows(lg, lshape, 1 if form == "scatter" else 0)
             if self.rows < 0:
                 raise L.RvError("rv_tap_stats_rows: " + L.load().rv_last_error().decode())
-            self.partial = torch.empty((self.rows + L.STATS_SCRATCH_ROWS, 2, pad32(layer.c_out)), dtype=torch.float32,
-                                       device=t.device)
+            self.partial = partial_rows(self.rows, pad32(layer.c_out), t.device)
         if eval_bn is not None:
             wp, bias_p = layer.packed_eval("folded" if isinstance(wp, str) else form, eval_bn)
         elif wp is None:
@@ -1229,13 +1267,10 @@ def pos_pair(t: Tape, l0: TapLayer, bn0: nn.BatchNorm2d, l1: TapLayer, bn1: nn.B
     h1 = sk.out
     y2 = Act.empty(x.N, x.H, x.W, l1.c_out, t.device)
     rows = L.load().rv_pos_forward_rows(x.pixels)
-    partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, y2.cp), dtype=torch.float32, device=t.device) if t.training else None
+    partial = partial_rows(rows, y2.cp, t.device) if t.training else None
     call = lambda: L.call("rv_pos_forward", x.ptr(), x.ld, l0.c_in, x.pixels, L.ptr(l0.packed("gather")), pad32(l0.c_in),
                           L.ptr(sk.scale), L.ptr(sk.shift), L.ptr(l1.packed("gather")), y2.cp, h1.ptr(), y2.ptr(), L.ptr(partial), L.stream_ptr())
-    if PROFILE is not None:
-        _launch("pos_fwd_kernel", 2.0 * x.pixels * l1.c_in * l1.c_out, call)
-    else:
-        call()
+    _launch("pos_fwd_kernel", 2.0 * x.pixels * l1.c_in * l1.c_out, call)
     conv = ConvOp(t, l1, h1, stats=t.training, out=y2, precomputed=(partial, rows))
     conv.pos_first = sk  # backward: this conv's input gradient is consumed by `sk`'s BatchNorm backward inside one kernel
     return BnOp(t, conv, bn1, True).lazy
@@ -1272,10 +1307,7 @@ class PosModulateOp(Op):
         call = lambda: L.call("rv_pos_modulate_forward", x.ptr(), x.ld, l0.c_in, L.ptr(l0.packed("gather")), pad32(l0.c_in),
                               L.ptr(s1), L.ptr(t1), L.ptr(l1.packed("gather")), cp, L.ptr(s2), L.ptr(t2), feat.ptr(), feat.ld,
                               feat.N, feat.H, feat.W, self.out.ptr(), L.stream_ptr())
-        if PROFILE is not None:
-            _launch("pos_fwd_kernel<eval>", 2.0 * x.pixels * l1.c_in * l1.c_out, call)
-        else:
-            call()
+        _launch("pos_fwd_kernel<eval>", 2.0 * x.pixels * l1.c_in * l1.c_out, call)
         t.ops.append(self)
 
     def backward(self, t: Tape) -> None:
@@ -1304,9 +1336,8 @@ class CombineOp(Op):
             assert rb.cp == ra.cp and rb.pixels == ra.pixels
         self.out = out if out is not None else ra.like()
         L.call("rv_ew_combine", ra.pixels, ra.cp, ra.ptr(), ra.ld, L.ptr(sa), L.ptr(ta),
-               rb.ptr() if rb is not None else None, rb.ld if rb is not None else 0, L.ptr(sb), L.ptr(tb),
+               *ptr_ld(rb), L.ptr(sb), L.ptr(tb),
                self.out.ptr(), self.out.ld, flags, L.stream_ptr())
-        t.producers[id(self.out)] = self
         t.ops.append(self)
 
     def backward(self, t: Tape) -> None:

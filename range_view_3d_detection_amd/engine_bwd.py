@@ -14,7 +14,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import Optional, Sequence, Tuple
 
 import torch
 from torch import Tensor
@@ -88,7 +89,6 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
     elif op.need_input_grad:
         if isinstance(op.x, Lazy):
             dst, accumulate = t.lazy_grad_target(op.x)
-            dst._rv_owned = True
         else:
             dst, accumulate = t.grad_buffer(op.x)
         shape = L.TapShape(sp.N, sp.H, sp.Wu, sp.Wv, dout.ld, dst.ld, L.OUT_ACCUM if accumulate else 0)
@@ -119,12 +119,12 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
             rows = L.load().rv_tap_bnb_rows(g, shape, 1 if bwd == "scatter" else 0)
             if rows > 0:
                 lz, st = op.x, op.x.bn
-                partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, dst.cp), dtype=torch.float32, device=t.device)
+                partial = E.partial_rows(rows, dst.cp, t.device)
                 epi = L.BnbEpilogue(lz.raw.ptr(), lz.raw.ld, L.BNB_RELU_Z if lz.relu else 0, L.ptr(st.scale), L.ptr(st.shift),
                                     L.ptr(st.mean), L.ptr(st.invstd), L.ptr(partial))
                 call = lambda: L.call("rv_tap_data_grad_bnb", g, shape, 1 if bwd == "scatter" else 0, dout.ptr(),
                                       L.ptr(wp), dst.ptr(), epi, L.stream_ptr())
-                t.lazy_sums[id(lz)] = (partial, rows, dst)
+                t.pending[id(lz)].sums = E.BnbSums(partial, rows, dst)
         if E.OVERLAP_WGRAD and E.EARLY_WGRAD_FILL > 0:
             # a persistent backward-data launch whose LAST round of tiles fills only part of the chip (1328 tiles on 256 CUs: five full
             # rounds and 48 tiles): the weight gradient of the same layer -- it reads dOut and the layer input, both complete -- is
@@ -147,10 +147,7 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
         if not isinstance(op.x, Lazy):
             t.mark_written(op.x)
     # ---- weight gradient ---------------------------------------------------------------------------
-    if fwd == "gather":
-        u, v, v_affine = dout, src, 1
-    else:
-        u, v, v_affine = src, dout, 0
+    u, v, v_affine = (dout, src, 1) if fwd == "gather" else (src, dout, 0)
     wshape = L.TapShape(sp.N, sp.H, sp.Wu, sp.Wv, 0, 0, in_flags | L.WGRAD_TORCH_LAYOUT)
     # strided layers: the weight gradient on the stride-1 FOLDED view of the fine tensor (wgrad3 instead of the generic kernel),
     # then rv_unfold_weight_grad picks the kernel's own entries out of the folded gradient
@@ -216,21 +213,19 @@ HEAD_FINAL_FUSE = True  # (module attribute: tests flip it in-process)
 def _head_final_eligible(op: "E.ConvOp", t: Tape, dout: Act) -> bool:
     """``op`` is a tower's final conv (1x1, stride 1, at most 32 output channels, fp32 output) whose ONLY input is the activated
     output of a conv -> BatchNorm (-> ReLU) unit in training mode that nobody else has contributed a gradient to."""
-    x, lay = op.x, op.layer
-    g = lay.geom
-    return (HEAD_FINAL_FUSE and t.training and op.out_f32 and isinstance(x, Lazy) and x.relu and x.bn.mean is not None and id(x) not in t.lazy_in
-            and id(x) not in t.head_final and lay.fwd_form == "gather" and g.kh == 1 and g.kw == 1 and g.stride_w == 1 and lay.in_perm is None
+    x, lay, g = op.x, op.layer, op.layer.geom
+    return (HEAD_FINAL_FUSE and t.training and op.out_f32 and isinstance(x, Lazy) and x.relu and x.bn.mean is not None and id(x) not in t.pending
+            and lay.fwd_form == "gather" and g.kh == 1 and g.kw == 1 and g.stride_w == 1 and lay.in_perm is None
             and pad32(g.cu) == 32 and x.raw.cp % 256 == 0 and x.raw.cp == pad32(g.cv) and dout.ld >= 32 and dout.pixels == x.raw.pixels)
 
 
 def _head_final_sums(op: "E.ConvOp", t: Tape, dY: Act) -> None:
     """First pass of the fused form: the BatchNorm-backward sums of the unit in front of the final conv (kept on the tape for
     ``bn_backward_begin``) and the final conv's own weight gradient, from ONE pass over the unit's raw output."""
-    lazy, layer = op.x, op.layer
-    st, raw = lazy.bn, lazy.raw
+    lazy, layer, st, raw = op.x, op.layer, op.x.bn, op.x.raw
     wp = layer.packed("scatter")
     rows = L.load().rv_head_final_bwd_rows(raw.pixels)
-    partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, raw.cp), dtype=torch.float32, device=t.device)
+    partial = E.partial_rows(rows, raw.cp, t.device)
     dw_partial = torch.empty((rows, 32 * raw.cp), dtype=torch.float32, device=t.device)
     head = (raw.pixels, raw.cp, raw.ptr(), raw.ld, dY.ptr(), dY.ld, L.ptr(wp), L.ptr(st.scale), L.ptr(st.shift),
             L.ptr(st.mean), L.ptr(st.invstd), 1)
@@ -239,7 +234,7 @@ def _head_final_sums(op: "E.ConvOp", t: Tape, dY: Act) -> None:
     L.call("rv_reduce_rows", L.ptr(dw_partial), rows, 32 * raw.cp, L.ptr(dw), L.stream_ptr())
     g = layer.geom
     t.add_param_grad(layer.weight, dw[: g.cu, : g.cv].reshape(g.cu, g.cv, 1, 1))
-    t.head_final[id(lazy)] = (head, partial, rows, dY, wp)
+    t.pending[id(lazy)] = E.PendingHeadFinal(head, partial, rows, dY, wp)
 
 
 def _release_held_wgrads(t: Tape) -> None:
@@ -272,10 +267,8 @@ POS_BWD_FUSE = True  # (module attribute: tests and A/B tools flip it in-process
 def _pos_pair_backward(op: "E.ConvOp", t: Tape, dy2: Act) -> None:
     """Parameter gradients of the FIRST positional layer (conv 3 -> C, BatchNorm) from the second layer's output gradient."""
     sk = op.pos_first
-    lay0, bn0, rel = sk.layer, sk.bn, sk.x
-    l1 = op.layer
+    lay0, bn0, rel, l1, dev = sk.layer, sk.bn, sk.x, op.layer, t.device
     cp, cin, pixels = sk.out.cp, lay0.c_in, sk.out.pixels
-    dev = t.device
     ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(pixels, cp, cin), dtype=torch.uint8, device=dev)
     sums = torch.empty((2 + 4) * cp, dtype=torch.float64, device=dev)
     moms = torch.empty(4 + 16, dtype=torch.float64, device=dev)
@@ -283,10 +276,7 @@ def _pos_pair_backward(op: "E.ConvOp", t: Tape, dy2: Act) -> None:
     call = lambda: L.call("rv_pos_backward_sums", pixels, cp, dy2.ptr(), L.ptr(l1.packed("scatter")), rel.ptr(), rel.ld, cin,
                           L.ptr(wp0), E.pad32(cin), L.ptr(sk.scale), L.ptr(sk.shift), L.ptr(sk.mean), L.ptr(sk.invstd), L.ptr(sums),
                           L.ptr(moms), L.ptr(ws), L.stream_ptr())
-    if E.PROFILE is not None:
-        E._launch("pos_bwd_kernel", 2.0 * pixels * cp * cp, call)
-    else:
-        call()
+    E._launch("pos_bwd_kernel", 2.0 * pixels * cp * cp, call)
     dgamma = torch.empty(cp, dtype=torch.float32, device=dev)
     dbeta = torch.empty(cp, dtype=torch.float32, device=dev)
     dw = torch.empty((cp, cin), dtype=torch.float32, device=dev)
@@ -295,10 +285,8 @@ def _pos_pair_backward(op: "E.ConvOp", t: Tape, dy2: Act) -> None:
         g01 = _global_s01(sums, cp, pixels)
     L.call("rv_bn_bwd_smallk_from_sums", cp, cin, L.ptr(sums), L.ptr(moms), L.ptr(g01), L.ptr(wp0), E.pad32(cin),
            L.ptr(sk.gamma_p), L.ptr(sk.mean), L.ptr(sk.invstd), sk.count, L.ptr(dgamma), L.ptr(dbeta), L.ptr(dw), L.stream_ptr())
-    c = bn0.num_features
-    t.add_param_grad(bn0.weight, dgamma[:c])
-    t.add_param_grad(bn0.bias, dbeta[:c])
-    t.add_param_grad(lay0.weight, lay0.unpermute_grad(dw[: lay0.c_out].reshape(lay0.c_out, cin, 1, 1).contiguous()))
+    t.add_bn_grads(bn0, dgamma, dbeta)
+    t.add_smallk_wgrad(lay0, dw)
     sk.grads_done = True
 
 
@@ -318,15 +306,13 @@ def _smallk_grads(t: Tape, pixels: int, cp: int, dout: Act, mask: Optional[Act],
                   lay, gamma_p, stat_mean, stat_invstd, count: int, sync: bool):
     """(dgamma, dbeta, dW) of a small-K conv + BatchNorm from one pass (``rv_bn_bwd_smallk``); under SyncBN the two-phase
     form with the all-reduce of (sum g, sum g*xhat) in between."""
-    cin = lay.c_in
-    dev = t.device
+    cin, dev = lay.c_in, t.device
     ws = torch.empty(L.load().rv_bn_bwd_smallk_workspace_bytes(pixels, cp, cin), dtype=torch.uint8, device=dev)
     dgamma = torch.empty(cp, dtype=torch.float32, device=dev)
     dbeta = torch.empty(cp, dtype=torch.float32, device=dev)
     dw = torch.empty((cp, cin), dtype=torch.float32, device=dev)
     wp = lay.packed("gather")
-    head = (pixels, cp, dout.ptr(), dout.ld, mask.ptr() if mask is not None else None,
-            mask.ld if mask is not None else 0, y.ptr() if y is not None else None, y.ld if y is not None else 0, L.ptr(scale),
+    head = (pixels, cp, dout.ptr(), dout.ld, *E.ptr_ld(mask), *E.ptr_ld(y), L.ptr(scale),
             L.ptr(shift), L.ptr(mean), L.ptr(invstd), flags, v.ptr(), v.ld, cin, L.ptr(wp), E.pad32(cin))
     if sync:
         cin_pad = 4 if cin <= 4 else 8
@@ -351,32 +337,39 @@ def bn_backward(op: "E.BnOp", t: Tape) -> None:
         bn_backward_finish([rec], t)
 
 
-def bn_backward_begin(op: "E.BnOp", t: Tape):
+@dataclass(eq=False, slots=True)
+class BnbRecord:
+    """What ``bn_backward_begin`` leaves for ``bn_backward_finish``: this rank's sums and the apply pass still to be issued."""
+
+    op: "E.BnOp"
+    partial: Tensor
+    rows: int
+    tower_final: bool  # the apply pass is rv_head_final_bwd_apply(*args, ...) rather than rv_bn_bwd_apply(*args, ..., flags, ..., res)
+    args: tuple       # leading arguments of that call
+    keep: tuple       # what ``args`` points into (dout, mask / dY, weight image): referenced until the apply pass has been issued
+    flags: int = 0
+    res: Optional[Tuple[Act, bool]] = None
+
+
+def bn_backward_begin(op: "E.BnOp", t: Tape) -> Optional[BnbRecord]:
     """First half of a BatchNorm backward: this rank's (sum g, sum g*xhat) rows (from the backward-data epilogue that wrote the
     gradient, or a reduce pass).  Returns a record for ``bn_backward_finish``, or None when the op was completed here (no
     gradient arrived; the MetaKernel / small-K fused forms, which carry their own collectives)."""
     lazy = op.lazy
-    meta = t.meta_in.pop(id(lazy), None)
-    if meta is not None:
-        assert id(lazy) not in t.lazy_in, "the positional Lazy behind the MetaKernel modulation has exactly one consumer"
-        _bn_backward_meta(op, t, meta)
+    e = t.pending.pop(id(lazy), None)
+    if e is None:
         return None
-    hf = t.head_final.pop(id(lazy), None)
-    if hf is not None:
-        assert id(lazy) not in t.lazy_in, "the last unit of a head tower feeds the final conv only"
-        head, partial, rows, dY, wp = hf  # (the sums were formed with the final conv's weight gradient: _head_final_sums)
-        return (op, None, partial, rows, lazy.raw.pixels, 0, None, ("head_final", head, dY, wp))
-    entry = t.lazy_in.pop(id(lazy), None)
-    if entry is None:
+    if type(e) is E.PendingMeta:
+        _bn_backward_meta(op, t, e)
         return None
-    dout, mask, res = entry if len(entry) == 3 else (entry[0], entry[1], None)
+    if type(e) is E.PendingHeadFinal:  # (the sums were formed with the final conv's weight gradient: _head_final_sums)
+        return BnbRecord(op, e.partial, e.rows, True, e.head, (e.dY, e.wp))
+    dout, mask, res = e.dout, e.mask, e.res
     st, raw = lazy.bn, lazy.raw
     if st.mean is None:
         raise L.RvError("BatchNorm backward needs batch statistics (module was run in eval mode)")
-    cp, pixels = raw.cp, raw.pixels
-    flags = L.BNB_RELU_Z if lazy.relu else 0
-    conv = op.conv
-    lay, geo = conv.layer, conv.layer.geom
+    cp, pixels, flags = raw.cp, raw.pixels, L.BNB_RELU_Z if lazy.relu else 0
+    conv, lay, geo = op.conv, op.conv.layer, op.conv.layer.geom
     if (SMALLK_FUSION and res is None and not conv.need_input_grad and not conv.out_f32 and not isinstance(conv.x, Lazy)
             and geo.kh == 1 and geo.kw == 1 and geo.stride_w == 1 and lay.fwd_form == "gather" and lay.c_in <= 8 and lay.in_perm is None
             and lay.bias is None):
@@ -384,54 +377,45 @@ def bn_backward_begin(op: "E.BnOp", t: Tape):
         # weight gradient from one pass over (dOut, y, input) -- neither dy nor a separate wgrad pass (rv_bn_bwd_smallk)
         dgamma, dbeta, dw = _smallk_grads(t, pixels, cp, dout, mask, raw, st.scale, st.shift, st.mean, st.invstd, flags, conv.x, lay,
                                           op.gamma_p, st.mean, st.invstd, st.count, op.sync_world > 1)
-        c, cin = st.module.num_features, lay.c_in
-        t.add_param_grad(st.module.weight, dgamma[:c])
-        t.add_param_grad(st.module.bias, dbeta[:c])
-        t.add_param_grad(lay.weight, lay.unpermute_grad(dw[: lay.c_out].reshape(lay.c_out, cin, 1, 1).contiguous()))
+        t.add_bn_grads(st.module, dgamma, dbeta)
+        t.add_smallk_wgrad(lay, dw)
         return None
-    common = (pixels, cp, dout.ptr(), dout.ld, mask.ptr() if mask is not None else None,
-              mask.ld if mask is not None else 0, raw.ptr(), raw.ld, L.ptr(st.scale), L.ptr(st.shift),
+    common = (pixels, cp, dout.ptr(), dout.ld, *E.ptr_ld(mask), raw.ptr(), raw.ld, L.ptr(st.scale), L.ptr(st.shift),
               L.ptr(st.mean), L.ptr(st.invstd))
-    sums = t.lazy_sums.pop(id(lazy), None)
-    if sums is not None and sums[2] is dout and ((len(sums) == 3 and mask is None and res is None) or (len(sums) == 4 and mask is not None)):
-        partial, rows = sums[0], sums[1]  # formed by the backward-data launch that wrote dout (rv_tap_data_grad_bnb)
+    sums = e.sums
+    if sums is not None and sums.over is dout and (mask is not None if sums.masked else (mask is None and res is None)):
+        partial, rows = sums.partial, sums.rows  # formed by the launch that wrote dout (rv_tap_data_grad_bnb) / the pair reduce over it
     else:
         rows = L.load().rv_bn_bwd_rows(pixels)
-        partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, cp), dtype=torch.float32, device=t.device)
+        partial = E.partial_rows(rows, cp, t.device)
         L.call("rv_bn_bwd_reduce", *common, flags, L.ptr(partial), L.stream_ptr())
-    return (op, common, partial, rows, pixels, flags, res, (dout, mask))  # (dout / mask referenced until the apply pass has been issued)
+    return BnbRecord(op, partial, rows, False, common, (dout, mask), flags, res)
 
 
-def bn_backward_finish(recs, t: Tape) -> None:
+def bn_backward_finish(recs: Sequence[BnbRecord], t: Tape) -> None:
     """Second half for a run of independent BatchNorm layers: ONE all-reduce of all their sums under SyncBN, then per layer
     the coefficients and the apply pass (gradient w.r.t. the raw conv output)."""
-    glob = [None] * len(recs)
-    local = [None] * len(recs)
-    sync = [i for i, r in enumerate(recs) if r[0].sync_world > 1]
+    glob, local = [None] * len(recs), [None] * len(recs)
+    sync = [i for i, r in enumerate(recs) if r.op.sync_world > 1]
     if sync:
         for i in sync:  # this rank's own (sum g, sum g*xhat) = (dbeta, dgamma): written by the same launch that fills the all-reduce buffer
-            local[i] = torch.empty((2, recs[i][0].lazy.raw.cp), dtype=torch.float32, device=t.device)
-        views = E.allreduce_partial_rows_many([(recs[i][2], recs[i][3], recs[i][4], local[i]) for i in sync])
+            local[i] = torch.empty((2, recs[i].op.lazy.raw.cp), dtype=torch.float32, device=t.device)
+        views = E.allreduce_partial_rows_many([(recs[i].partial, recs[i].rows, recs[i].op.lazy.raw.pixels, local[i]) for i in sync])
         for i, v in zip(sync, views):
             glob[i] = v
         _release_held_wgrads(t)  # (the collective is enqueued and the main stream waits for it: the held weight gradients may take the CUs now)
-    for (op, common, partial, rows, pixels, flags, res, _keep), g, loc in zip(recs, glob, local):
-        lazy = op.lazy
-        st, raw = lazy.bn, lazy.raw
-        dgamma, dbeta, coef = _bn_finalize(op, t, partial, rows, pixels, glob=g, local=loc)
+    for r, g, loc in zip(recs, glob, local):
+        raw = r.op.lazy.raw
+        dgamma, dbeta, coef = _bn_finalize(r.op, t, r.partial, r.rows, raw.pixels, glob=g, local=loc)
         dy = raw.like()
-        if common is None:  # the head-final form: dA recomputed from the final conv's output gradient (bn_backward_begin)
-            L.call("rv_head_final_bwd_apply", *_keep[1], L.ptr(coef), dy.ptr(), dy.ld, L.stream_ptr())
-        elif res is not None:
-            rg, racc = res
-            L.call("rv_bn_bwd_apply", *common, L.ptr(coef), flags | (L.BNB_RES_ACCUM if racc else 0), dy.ptr(), dy.ld,
-                   rg.ptr(), rg.ld, L.stream_ptr())
+        if r.tower_final:  # dA recomputed from the final conv's output gradient
+            L.call("rv_head_final_bwd_apply", *r.args, L.ptr(coef), dy.ptr(), dy.ld, L.stream_ptr())
         else:
-            L.call("rv_bn_bwd_apply", *common, L.ptr(coef), flags, dy.ptr(), dy.ld, None, 0, L.stream_ptr())
+            rg, racc = r.res if r.res is not None else (None, False)
+            L.call("rv_bn_bwd_apply", *r.args, L.ptr(coef), r.flags | (L.BNB_RES_ACCUM if racc else 0), dy.ptr(), dy.ld,
+                   *E.ptr_ld(rg), L.stream_ptr())
         t.raw_grad[id(raw)] = dy
-        c = st.module.num_features
-        t.add_param_grad(st.module.weight, dgamma[:c])
-        t.add_param_grad(st.module.bias, dbeta[:c])
+        t.add_bn_grads(r.op.lazy.bn.module, dgamma, dbeta)
 
 
 def _bn_finalize(op: "E.BnOp", t: Tape, partial: Tensor, rows: int, pixels: int, glob: Optional[Tensor] = None, local: Optional[Tensor] = None):
@@ -457,19 +441,15 @@ def _bn_finalize(op: "E.BnOp", t: Tape, partial: Tensor, rows: int, pixels: int,
     return dgamma, dbeta, coef
 
 
-def _bn_backward_meta(op: "E.BnOp", t: Tape, meta) -> None:
+def _bn_backward_meta(op: "E.BnOp", t: Tape, meta: "E.PendingMeta") -> None:
     """BatchNorm backward of the positional layer behind the MetaKernel modulation (sums formed by modulate_backward)."""
-    dgeo, feat, partial, rows = meta
-    lazy = op.lazy
-    st, raw = lazy.bn, lazy.raw
-    dgamma, dbeta, coef = _bn_finalize(op, t, partial, rows, raw.pixels)
+    dgeo, feat, st, raw = meta.dgeo, meta.feat, op.lazy.bn, op.lazy.raw
+    dgamma, dbeta, coef = _bn_finalize(op, t, meta.partial, meta.rows, raw.pixels)
     dy = raw.like()
     L.call("rv_meta_modulate_bwd_apply", dgeo.ptr(), raw.ptr(), L.ptr(st.scale), L.ptr(st.shift), L.ptr(st.mean), L.ptr(st.invstd),
            L.ptr(coef), feat.ptr(), feat.ld, feat.N, feat.H, feat.W, feat.cp, dy.ptr(), L.stream_ptr())
     t.raw_grad[id(raw)] = dy
-    c = st.module.num_features
-    t.add_param_grad(st.module.weight, dgamma[:c])
-    t.add_param_grad(st.module.bias, dbeta[:c])
+    t.add_bn_grads(st.module, dgamma, dbeta)
 
 
 def combine_backward(op: "E.CombineOp", t: Tape) -> None:
@@ -483,14 +463,13 @@ def combine_backward(op: "E.CombineOp", t: Tape) -> None:
     # already forms, so that pass also writes it (rv_bn_bwd_apply's dres output) instead of a separate masking pass.
     fuse_res = len(lazies) == 1 and len(plains) == 1 and not lazies[0].relu and t.training
     if (BNB_PAIR and len(lazies) == 2 and not plains and mask is not None and t.training and all(not x.relu and x.bn.mean is not None for x in lazies)
-            and all(id(x) not in t.lazy_in for x in lazies) and lazies[0].raw.cp == lazies[1].raw.cp == gout.cp
+            and all(id(x) not in t.pending for x in lazies) and lazies[0].raw.cp == lazies[1].raw.cp == gout.cp
             and lazies[0].raw.pixels == lazies[1].raw.pixels == gout.pixels):
         # out = relu(bn_a(ya) + bn_b(yb)) (a block with a projection): the sums of BOTH BatchNorm backwards from one pass
         # over (dOut, out, ya, yb); each bn_backward_begin then finds its rows and skips its own reduce pass
         la, lb = lazies
         rows = L.load().rv_bn_bwd_rows(gout.pixels)
-        pa = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, gout.cp), dtype=torch.float32, device=t.device)
-        pb = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, gout.cp), dtype=torch.float32, device=t.device)
+        pa, pb = E.partial_rows(rows, gout.cp, t.device), E.partial_rows(rows, gout.cp, t.device)
         L.call("rv_bn_bwd_reduce_pair", gout.pixels, gout.cp, gout.ptr(), gout.ld, mask.ptr(), mask.ld,
                la.raw.ptr(), la.raw.ld, L.ptr(la.bn.mean), L.ptr(la.bn.invstd), lb.raw.ptr(), lb.raw.ld, L.ptr(lb.bn.mean),
                L.ptr(lb.bn.invstd), L.ptr(pa), L.ptr(pb), L.stream_ptr())
@@ -506,9 +485,7 @@ def combine_backward(op: "E.CombineOp", t: Tape) -> None:
             coefs = []
             for o, part, gl, lo in zip(ops, (pa, pb), globs, locs):
                 dgamma, dbeta, coef = _bn_finalize(o, t, part, rows, gout.pixels, glob=gl, local=lo)
-                c = o.lazy.bn.module.num_features
-                t.add_param_grad(o.lazy.bn.module.weight, dgamma[:c])
-                t.add_param_grad(o.lazy.bn.module.bias, dbeta[:c])
+                t.add_bn_grads(o.lazy.bn.module, dgamma, dbeta)
                 coefs.append(coef)
             dya, dyb = la.raw.like(), lb.raw.like()
             L.call("rv_bn_bwd_apply_pair", gout.pixels, gout.cp, gout.ptr(), gout.ld, mask.ptr(), mask.ld,
@@ -519,22 +496,18 @@ def combine_backward(op: "E.CombineOp", t: Tape) -> None:
             return
         for x, part in ((la, pa), (lb, pb)):
             t.add_lazy_grad(x, gout, mask, None)
-            t.lazy_sums[id(x)] = (part, rows, gout, True)
+            t.pending[id(x)].sums = E.BnbSums(part, rows, gout, masked=True)
         return
     for x in lazies:
-        res = None
+        res = t.grad_buffer(plains[0]) if fuse_res else None  # (buffer, accumulate)
         if fuse_res:
-            g, have_x = t.grad_buffer(plains[0])
-            res = (g, have_x)
             t.mark_written(plains[0])
         t.add_lazy_grad(x, gout, mask, res)
     if fuse_res:
         return
     for x in plains:
         g, have_x = t.grad_buffer(x)
-        L.call("rv_ew_mask_grad", gout.pixels, gout.cp, gout.ptr(), gout.ld,
-               mask.ptr() if mask is not None else None, mask.ld if mask is not None else 0, g.ptr(), g.ld,
-               1 if have_x else 0, L.stream_ptr())
+        t._masked_into(gout, mask, g, have_x)
         t.mark_written(x)
 
 
@@ -543,30 +516,28 @@ META_BWD_FUSE = True
 
 
 def modulate_backward(op: "E.MetaModulateOp", t: Tape) -> None:
-    pos, feat = op.pos, op.feat
-    st = pos.bn
+    pos, feat, st = op.pos, op.feat, op.pos.bn
     g, have = t.grad_buffer(op.out)
     if not have:
         return
     gf, have_f = t.grad_buffer(feat)
     assert not have_f, "MetaKernel projection output has a single consumer"
-    if META_BWD_FUSE and pos.relu and st.mean is not None and id(pos) not in t.lazy_in:
+    if META_BWD_FUSE and pos.relu and st.mean is not None and id(pos) not in t.pending:
         # fused with the BatchNorm(+ReLU) backward of the positional layer: this pass forms dfeat and the (sum z, sum z*xhat)
         # rows; bn_backward finalizes them and a second pass writes dy -- the activated-gradient tensor is never written
         rows = L.load().rv_meta_bwd_rows(feat.N, feat.H, feat.W)
-        partial = torch.empty((rows + L.STATS_SCRATCH_ROWS, 2, feat.cp), dtype=torch.float32, device=t.device)
+        partial = E.partial_rows(rows, feat.cp, t.device)
         L.call("rv_meta_modulate_bwd_sums", g.ptr(), pos.raw.ptr(), L.ptr(st.scale), L.ptr(st.shift), L.ptr(st.mean), L.ptr(st.invstd),
                feat.ptr(), feat.ld, feat.N, feat.H, feat.W, feat.cp, gf.ptr(), gf.ld,
                L.ptr(partial), L.stream_ptr())
         t.mark_written(feat)
-        t.meta_in[id(pos)] = (g, feat, partial, rows)
+        t.pending[id(pos)] = E.PendingMeta(g, feat, partial, rows)
         return
     dpos = pos.raw.like()
     L.call("rv_meta_modulate_bwd", g.ptr(), pos.raw.ptr(), L.ptr(pos.bn.scale), L.ptr(pos.bn.shift), feat.ptr(), feat.ld,
            feat.N, feat.H, feat.W, feat.cp, dpos.ptr(), gf.ptr(), gf.ld, L.stream_ptr())
     t.mark_written(feat)
-    dpos._rv_owned = True
-    t.add_lazy_grad(pos, dpos, None)
+    t.add_lazy_grad(pos, dpos, None, owned=True)
 
 
 def smallk_backward(op: "E.SmallKOp", t: Tape) -> None:
@@ -580,10 +551,7 @@ def smallk_backward(op: "E.SmallKOp", t: Tape) -> None:
     if not t.training:
         raise L.RvError("BatchNorm backward needs batch statistics (module was run in eval mode)")
     lay, bn, h, v = op.layer, op.bn, op.out, op.x
-    cp, cin, pixels = h.cp, lay.c_in, h.pixels
-    dgamma, dbeta, dw = _smallk_grads(t, pixels, cp, dout, None, None, op.scale, op.shift, op.mean, op.invstd, L.BNB_RELU_Z | L.BNB_Y_FROM_INPUT,
+    dgamma, dbeta, dw = _smallk_grads(t, h.pixels, h.cp, dout, None, None, op.scale, op.shift, op.mean, op.invstd, L.BNB_RELU_Z | L.BNB_Y_FROM_INPUT,
                                       v, lay, op.gamma_p, op.mean, op.invstd, op.count, op.sync_world > 1)
-    c = bn.num_features
-    t.add_param_grad(bn.weight, dgamma[:c])
-    t.add_param_grad(bn.bias, dbeta[:c])
-    t.add_param_grad(lay.weight, lay.unpermute_grad(dw[: lay.c_out].reshape(lay.c_out, cin, 1, 1).contiguous()))
+    t.add_bn_grads(bn, dgamma, dbeta)
+    t.add_smallk_wgrad(lay, dw)
