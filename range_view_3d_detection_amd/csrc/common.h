@@ -50,6 +50,8 @@ void rv_set_error(const char* fmt, ...);
 
 static inline int rv_ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline int rv_pad32(int c) { return (c + 31) & ~31; }
+// byte count rounded up to the 256-byte alignment every part of a workspace has
+__host__ __device__ static inline int64_t rv_align256(int64_t v) { return (v + 255) & ~255ll; }
 // compute units of the CURRENT device (a read-only cache of a device property, one slot per device ordinal: a process that drives
 // several devices gets each one's own count; relaxed atomics: two threads racing on the first call store the same value).  256 = an
 // MI355X when no device is visible: the host-side planning entry points also run on GPU-less build boxes.  Note that hipGetDevice

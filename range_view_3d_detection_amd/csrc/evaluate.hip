@@ -26,21 +26,20 @@
 
 #pragma clang fp contract(off)
 
+#include "segments.h"
+
 namespace {
 
 constexpr int THREADS = 256;
+static_assert(THREADS == 64 * SEG_WAVES, "segments.h scans a workgroup of 256 threads");
 constexpr int GT_CHUNK = 1024;  // ground truths staged per pass: 12 KB of centres + 4 KB of claims
 
 struct EvalMatchArgs {
+    Segments s;
     const float* dts;         // (n_dt, 10)
-    const int64_t* dt_order;  // (n_dt): position in (segment, score) order -> row
-    const int64_t* dt_off;    // (n_seg + 1)
     const float* gts;         // (n_gt, 10)
     const uint8_t* gt_valid;  // (n_gt) or null
     const uint8_t* dt_roi;    // (n_dt) or null: rv_eval_match_roi
-    const int64_t* gt_order;  // (n_gt)
-    const int64_t* gt_off;    // (n_seg + 1)
-    int64_t n_dt, n_gt;
     int n_seg, n_thr, cap;
     double range2, tp_thr2;
     double thr2[RV_EVAL_MAX_THRESHOLDS];
@@ -51,20 +50,12 @@ struct EvalMatchArgs {
     uint8_t* gt_evaluated;
 };
 
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __device__ __forceinline__ double norm2(const float* row) {
     const double x = row[0], y = row[1], z = row[2];
     return (x * x + y * y) + z * z;
 }
 
 __device__ __forceinline__ double yaw_of(const float* row) { return 2.0 * atan2((double)row[9], (double)row[6]); }
-
-// row of `order[i]`, or -1 when it does not name a row (nothing is read or written through such an entry)
-__device__ __forceinline__ int64_t row_at(const int64_t* order, int64_t i, int64_t n) {
-    const int64_t r = order[i];
-    return r >= 0 && r < n ? r : -1;
-}
 
 __device__ __forceinline__ void write_unmatched(const EvalMatchArgs& a, int64_t row, bool evaluated) {
     a.dt_evaluated[row] = evaluated ? 1 : 0;
@@ -76,11 +67,11 @@ __device__ __forceinline__ void write_unmatched(const EvalMatchArgs& a, int64_t 
 // rows of [lo, hi) in sorted order that belong to no segment: not evaluated
 __device__ void write_outside(const EvalMatchArgs& a, int64_t dlo, int64_t dhi, int64_t glo, int64_t ghi) {
     for (int64_t i = dlo + threadIdx.x; i < dhi; i += THREADS) {
-        const int64_t row = row_at(a.dt_order, i, a.n_dt);
+        const int64_t row = row_at(a.s.dt_order, i, a.s.n_dt);
         if (row >= 0) write_unmatched(a, row, false);
     }
     for (int64_t i = glo + threadIdx.x; i < ghi; i += THREADS) {
-        const int64_t row = row_at(a.gt_order, i, a.n_gt);
+        const int64_t row = row_at(a.s.gt_order, i, a.s.n_gt);
         if (row >= 0) a.gt_evaluated[row] = 0;
     }
 }
@@ -91,53 +82,41 @@ __global__ __launch_bounds__(THREADS) void eval_match_kernel(const EvalMatchArgs
     __shared__ int ev_best[RV_EVAL_MAX_DTS];     // its index in the segment, or -1
     __shared__ float gt_xyz[GT_CHUNK * 3];
     __shared__ int claim[GT_CHUNK];
-    __shared__ int wave_count[THREADS / 64];
-    __shared__ int wave_kept[THREADS / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ int wave_count[SEG_WAVES];
+    const int tid = threadIdx.x;
     const int seg = blockIdx.x;
-    if (seg == a.n_seg) {
-        write_outside(a, 0, clamp64(a.dt_off[0], 0, a.n_dt), 0, clamp64(a.gt_off[0], 0, a.n_gt));
-        write_outside(a, clamp64(a.dt_off[a.n_seg], 0, a.n_dt), a.n_dt, clamp64(a.gt_off[a.n_seg], 0, a.n_gt), a.n_gt);
+    if (seg == a.n_seg) {  // the rows before the first segment and behind the last one
+        const Bounds first = bounds_of(a.s, 0), last = bounds_of(a.s, a.n_seg - 1);
+        write_outside(a, 0, first.d0, 0, first.g0);
+        write_outside(a, last.d0 + last.nd, a.s.n_dt, last.g0 + last.ng, a.s.n_gt);
         return;
     }
-    const int64_t d0 = clamp64(a.dt_off[seg], 0, a.n_dt), d1 = clamp64(a.dt_off[seg + 1], d0, a.n_dt);
-    const int64_t g0 = clamp64(a.gt_off[seg], 0, a.n_gt), g1 = clamp64(a.gt_off[seg + 1], g0, a.n_gt);
+    const Bounds b = bounds_of(a.s, seg);
+    const int64_t d0 = b.d0, d1 = b.d0 + b.nd, g0 = b.g0, g1 = b.g0 + b.ng;
 
     // A: the first `cap` rows in range, in score order
     int n_eval = 0, n_kept = 0;  // rows in range so far; with dt_roi: the evaluated ones among them
     for (int64_t base = d0; base < d1; base += THREADS) {
         const int64_t i = base + tid;
-        const int64_t row = i < d1 ? row_at(a.dt_order, i, a.n_dt) : -1;
+        const int64_t row = i < d1 ? row_at(a.s.dt_order, i, a.s.n_dt) : -1;
         const bool in_range = row >= 0 && norm2(a.dts + row * 10) <= a.range2;
-        const unsigned long long votes = __ballot(in_range);
-        if (lane == 0) wave_count[wave] = __popcll(votes);
-        __syncthreads();
-        int rank = n_eval + __popcll(votes & ((1ull << lane) - 1ull));
-        int total = 0;
-        for (int w = 0; w < THREADS / 64; ++w) {
-            if (w < wave) rank += wave_count[w];
-            total += wave_count[w];
-        }
+        int total;
+        const int rank = tile_rank(in_range, n_eval, wave_count, &total);
         bool evaluated = in_range && rank < a.cap;
         int slot = rank;
         if (a.dt_roi) {  // (the same for the whole grid) cap first, then the ROI flag: the evaluated rows are packed by a second scan
             evaluated = evaluated && a.dt_roi[row] != 0;
-            const unsigned long long kept = __ballot(evaluated);
-            if (lane == 0) wave_kept[wave] = __popcll(kept);
-            __syncthreads();
-            slot = n_kept + __popcll(kept & ((1ull << lane) - 1ull));
-            for (int w = 0; w < THREADS / 64; ++w) {
-                if (w < wave) slot += wave_kept[w];
-                n_kept += wave_kept[w];
-            }
+            int kept;
+            slot = tile_rank(evaluated, n_kept, wave_count, &kept);
+            n_kept += kept;
         }
         if (evaluated) ev_row[slot] = row;
         else if (row >= 0) write_unmatched(a, row, false);
         n_eval += total;
-        __syncthreads();
     }
     if (n_eval > a.cap) n_eval = a.cap;
     if (a.dt_roi) n_eval = n_kept;
+    __syncthreads();  // (B reads ranks that other threads wrote)
 
     // B: nearest evaluated ground truth of every evaluated detection (ties: the lowest index, `<` below)
     const int n_pass = n_eval > 0 ? (n_eval + THREADS - 1) / THREADS : 1;  // (one pass with no detections still flags the ground truth)
@@ -153,7 +132,7 @@ __global__ __launch_bounds__(THREADS) void eval_match_kernel(const EvalMatchArgs
             const int n_c = (int)(g1 - c0 < GT_CHUNK ? g1 - c0 : GT_CHUNK);
             __syncthreads();
             for (int j = tid; j < n_c; j += THREADS) {
-                const int64_t row = row_at(a.gt_order, c0 + j, a.n_gt);
+                const int64_t row = row_at(a.s.gt_order, c0 + j, a.s.n_gt);
                 bool evaluated = false;
                 if (row >= 0) {
                     const float* g = a.gts + row * 10;
@@ -197,7 +176,7 @@ __global__ __launch_bounds__(THREADS) void eval_match_kernel(const EvalMatchArgs
                 write_unmatched(a, row, true);
                 continue;
             }
-            const int64_t gt_row = a.gt_order[c0 + g];  // (in range: this entry was staged as evaluated)
+            const int64_t gt_row = a.s.gt_order[c0 + g];  // (in range: this entry was staged as evaluated)
             const double d2 = ev_d2[rank];
             a.dt_evaluated[row] = 1;
             a.matched[row] = (int32_t)gt_row;
@@ -266,17 +245,6 @@ __device__ __forceinline__ T block_scan(T v, Op op, T* scratch, T* total) {
     }
     *total = all;
     return v;
-}
-
-// sum over the 256 threads in a fixed order (wave butterfly, then the waves in order): the same bits on every run
-__device__ __forceinline__ double block_sum(double v, double* scratch) {
-    v = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = scratch[0];
-    for (int w = 1; w < THREADS / 64; ++w) s += scratch[w];
-    return s;
 }
 
 __global__ __launch_bounds__(THREADS) void eval_curve_kernel(const EvalSumArgs a) {
@@ -376,8 +344,6 @@ __global__ __launch_bounds__(THREADS) void eval_table_kernel(const EvalSumArgs a
     }
 }
 
-int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
-
 }  // namespace
 
 namespace {
@@ -397,8 +363,8 @@ int eval_match(const float* dts, const int64_t* dt_order, const int64_t* dt_offs
     RV_REQUIRE(n_gt == 0 || (gts && gt_order && gt_evaluated), "rv_eval_match: null ground-truth buffer");
     EvalMatchArgs a;
     memset(&a, 0, sizeof(a));
-    a.dts = dts, a.dt_order = dt_order, a.dt_off = dt_offsets, a.n_dt = n_dt;
-    a.gts = gts, a.gt_valid = gt_valid, a.dt_roi = n_dt > 0 ? dt_roi : nullptr, a.gt_order = gt_order, a.gt_off = gt_offsets, a.n_gt = n_gt;
+    a.s = Segments{dt_order, dt_offsets, gt_order, gt_offsets, n_dt, n_gt};
+    a.dts = dts, a.gts = gts, a.gt_valid = gt_valid, a.dt_roi = n_dt > 0 ? dt_roi : nullptr;
     a.n_seg = n_segments, a.n_thr = n_thresholds, a.cap = max_num_dts;
     a.range2 = max_range_m * max_range_m;
     a.tp_thr2 = tp_threshold_m * tp_threshold_m;
@@ -435,8 +401,8 @@ extern "C" int rv_eval_match_roi(const float* dts, const int64_t* dt_order, cons
 
 extern "C" int64_t rv_eval_summarize_workspace_bytes(int64_t n_rows, int32_t n_categories, int32_t n_thresholds) {
     if (n_rows < 0 || n_categories < 1 || n_thresholds < 1) return 0;
-    return align256(n_rows * n_thresholds * (int64_t)sizeof(double)) + align256(n_rows * n_thresholds * (int64_t)sizeof(int32_t)) +
-           align256((int64_t)n_categories * 4 * (int64_t)sizeof(double));
+    return rv_align256(n_rows * n_thresholds * (int64_t)sizeof(double)) + rv_align256(n_rows * n_thresholds * (int64_t)sizeof(int32_t)) +
+           rv_align256((int64_t)n_categories * 4 * (int64_t)sizeof(double));
 }
 
 extern "C" int rv_eval_summarize(const uint8_t* flags, const float* err, const int64_t* cat_offsets, const int64_t* n_gt, int64_t n_rows,
@@ -459,9 +425,9 @@ extern "C" int rv_eval_summarize(const uint8_t* flags, const float* err, const i
     a.tp_thr = tp_threshold_m, a.default_ase = default_ase, a.default_aoe = default_aoe;
     char* ws = (char*)workspace;
     a.pmax = (double*)ws;
-    ws += align256(n_rows * n_thresholds * (int64_t)sizeof(double));
+    ws += rv_align256(n_rows * n_thresholds * (int64_t)sizeof(double));
     a.cum = (int32_t*)ws;
-    ws += align256(n_rows * n_thresholds * (int64_t)sizeof(int32_t));
+    ws += rv_align256(n_rows * n_thresholds * (int64_t)sizeof(int32_t));
     a.err_sums = (double*)ws;
     a.table = table, a.ap_t = ap_per_threshold;
     hipStream_t st = (hipStream_t)stream;

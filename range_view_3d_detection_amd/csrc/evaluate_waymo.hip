@@ -28,6 +28,7 @@
 #pragma clang fp contract(off)
 
 #include "nms_geom.h"
+#include "segments.h"
 
 namespace {
 
@@ -41,36 +42,7 @@ constexpr int START = -2, NONE = -1;  // back-pointer of a column reached from t
 enum { ERR_DTS = 0, ERR_GTS = 1, ERR_WORKSPACE = 2, ERR_BOUND = 3 };
 
 static_assert(RV_WAYMO_MAX_GTS % THREADS == 0 && RV_WAYMO_MAX_DTS % THREADS == 0, "limits are multiples of the workgroup size");
-
-__host__ __device__ inline int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
-__device__ __forceinline__ int64_t clamp64(int64_t v, int64_t lo, int64_t hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// row of `order[i]`, or -1 when it does not name a row (nothing is read or written through such an entry)
-__device__ __forceinline__ int64_t row_at(const int64_t* order, int64_t i, int64_t n) {
-    const int64_t r = order[i];
-    return r >= 0 && r < n ? r : -1;
-}
-
-struct Segments {
-    const int64_t* dt_order;
-    const int64_t* dt_off;
-    const int64_t* gt_order;
-    const int64_t* gt_off;
-    int64_t n_dt, n_gt;
-};
-
-struct Bounds {
-    int64_t d0, g0;
-    int64_t nd, ng;
-};
-
-__device__ __forceinline__ Bounds bounds_of(const Segments& s, int64_t seg) {
-    Bounds b;
-    b.d0 = clamp64(s.dt_off[seg], 0, s.n_dt);
-    b.nd = clamp64(s.dt_off[seg + 1], b.d0, s.n_dt) - b.d0;
-    b.g0 = clamp64(s.gt_off[seg], 0, s.n_gt);
-    b.ng = clamp64(s.gt_off[seg + 1], b.g0, s.n_gt) - b.g0;
-    return b;
-}
+static_assert(WAVES == SEG_WAVES, "segments.h scans a workgroup of 256 threads");
 
 // pairs of a segment in the table: none for a segment beyond a limit (rv_waymo_match reports it)
 __device__ __forceinline__ int64_t pairs_of(const Bounds& b) {
@@ -191,23 +163,6 @@ __device__ __forceinline__ long long heading_quanta(float yaw_d, float yaw_g) {
     const double acc = 1.0 - d / M_PI;
     if (!(acc >= 0.0)) return 0;  // (NaN yaw)
     return (long long)rint(acc * 1099511627776.0);
-}
-
-// position of every set flag among the set flags of the workgroup's tile, in thread order; `base` carries over tiles
-__device__ __forceinline__ int tile_rank(bool flag, int base, int* wave_count, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long votes = __ballot(flag);
-    __syncthreads();  // (wave_count may still be read from the tile before)
-    if (lane == 0) wave_count[wave] = __popcll(votes);
-    __syncthreads();
-    int rank = base + __popcll(votes & ((1ull << lane) - 1ull));
-    int all = 0;
-    for (int w = 0; w < WAVES; ++w) {
-        if (w < wave) rank += wave_count[w];
-        all += wave_count[w];
-    }
-    *total = all;
-    return rank;
 }
 
 __global__ __launch_bounds__(THREADS) void waymo_match_kernel(const WaymoMatchArgs a) {
@@ -474,7 +429,7 @@ int64_t pair_capacity(int64_t n_dt, int64_t n_gt) { return n_dt * (n_gt < RV_WAY
 
 extern "C" int64_t rv_waymo_match_workspace_bytes(int64_t n_dt, int64_t n_gt, int32_t n_segments) {
     if (n_dt < 0 || n_gt < 0 || n_segments < 1) return 0;
-    return align256(((int64_t)n_segments + 1) * 8) + align256(pair_capacity(n_dt, n_gt) * 8) + 256;
+    return rv_align256(((int64_t)n_segments + 1) * 8) + rv_align256(pair_capacity(n_dt, n_gt) * 8) + 256;
 }
 
 extern "C" int rv_waymo_iou(const float* dts, const int64_t* dt_order, const int64_t* dt_offsets, int64_t n_dt, const float* gts,
@@ -489,7 +444,7 @@ extern "C" int rv_waymo_iou(const float* dts, const int64_t* dt_order, const int
     RV_REQUIRE(n_gt == 0 || (gts && gt_order), "rv_waymo_iou: null ground-truth buffer");
     Segments s = {dt_order, dt_offsets, gt_order, gt_offsets, n_dt, n_gt};
     int64_t* pair_off = (int64_t*)workspace;
-    float2* iou = (float2*)((char*)workspace + align256(((int64_t)n_segments + 1) * 8));
+    float2* iou = (float2*)((char*)workspace + rv_align256(((int64_t)n_segments + 1) * 8));
     const int64_t capacity = pair_capacity(n_dt, n_gt);
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(waymo_offsets_kernel, dim3(1), dim3(THREADS), 0, st, s, n_segments, pair_off);
@@ -523,7 +478,7 @@ extern "C" int rv_waymo_match(const float* dts, const float* scores, const int64
     a.s = Segments{dt_order, dt_offsets, gt_order, gt_offsets, n_dt, n_gt};
     a.dts = dts, a.scores = scores, a.gts = gts, a.gt_level = gt_level, a.sweep_valid = sweep_valid;
     a.pair_off = (const int64_t*)workspace;
-    a.iou = (const float*)((const char*)workspace + align256(((int64_t)n_segments + 1) * 8));
+    a.iou = (const float*)((const char*)workspace + rv_align256(((int64_t)n_segments + 1) * 8));
     a.capacity = pair_capacity(n_dt, n_gt);
     a.tables = (unsigned long long*)tables, a.errors = errors;
     hipLaunchKernelGGL(waymo_match_kernel, dim3((unsigned)n_segments * 8), dim3(THREADS), 0, (hipStream_t)stream, a);

@@ -129,18 +129,16 @@ __global__ void pairwise_iou_kernel(const float* a, int64_t n, const float* b, i
     }
 }
 
-int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
-
 // workspace of one list, byte offsets: nms_mask [n][cb] at 0, merge_mask [n][cb] (weighted only), sc [n][2], num_out
 struct ListLayout {
     int64_t merge_mask, sc, num_out, bytes;
 };
 ListLayout carve_list(int64_t n, bool hard) {
-    const int64_t mask = align256(n * ((n + 63) / 64) * 8);
+    const int64_t mask = rv_align256(n * ((n + 63) / 64) * 8);
     ListLayout l;
     l.merge_mask = mask;
     l.sc = hard ? mask : 2 * mask;
-    l.num_out = l.sc + align256(n * 2 * 4);
+    l.num_out = l.sc + rv_align256(n * 2 * 4);
     l.bytes = l.num_out + 256;
     return l;
 }

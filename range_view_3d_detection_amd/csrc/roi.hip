@@ -204,8 +204,6 @@ __global__ __launch_bounds__(THREADS) void roi_col_kernel(const RasterArgs a) {
     }
 }
 
-int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
-
 int fill_args(RoiArgs& a, const char* who, int32_t n_sweeps, const int32_t* layer_index, const double* city_SE3_ego, const uint8_t* raster,
               int64_t raster_bytes, const rvRoiLayer* layers, int32_t n_layers, int64_t* stray) {
     RV_REQUIRE(n_sweeps >= 1, "%s: %d sweeps", who, n_sweeps);
@@ -269,7 +267,7 @@ extern "C" int rv_roi_boxes(const float* boxes, const int64_t* batch_index, int6
 
 extern "C" int64_t rv_roi_rasterize_workspace_bytes(int32_t n_polygons, int32_t height, int32_t width) {
     if (n_polygons < 0 || height < 1 || width < 1) return 0;
-    return align256((int64_t)(n_polygons > 0 ? n_polygons : 1) * 4 * (int64_t)sizeof(double)) + align256((int64_t)height * width * (int64_t)sizeof(int32_t));
+    return rv_align256((int64_t)(n_polygons > 0 ? n_polygons : 1) * 4 * (int64_t)sizeof(double)) + rv_align256((int64_t)height * width * (int64_t)sizeof(int32_t));
 }
 
 extern "C" int rv_roi_rasterize(const double* vertices, const int64_t* polygon_offsets, int64_t n_vertices, int32_t n_polygons, double s, double tx,
@@ -290,7 +288,7 @@ extern "C" int rv_roi_rasterize(const double* vertices, const int64_t* polygon_o
     a.s = s, a.tx = tx, a.ty = ty, a.r2 = r * r;
     char* ws = (char*)workspace;
     a.bbox = (double*)ws;
-    ws += align256((int64_t)(n_polygons > 0 ? n_polygons : 1) * 4 * (int64_t)sizeof(double));
+    ws += rv_align256((int64_t)(n_polygons > 0 ? n_polygons : 1) * 4 * (int64_t)sizeof(double));
     a.dist = (int32_t*)ws;
     a.drivable = drivable, a.roi = roi;
     hipStream_t st = (hipStream_t)stream;

@@ -216,14 +216,12 @@ __global__ __launch_bounds__(256) void sa_apply_kernel(const SaTable t) {
     }
 }
 
-int64_t align256(int64_t v) { return (v + 255) & ~255ll; }
-
 }  // namespace
 
 extern "C" int64_t rv_soft_assign_workspace_bytes(int32_t n_entries, int32_t m, int32_t B) {
     if (n_entries < 1 || m < 0 || B < 1) return 0;
     const int64_t slots = (int64_t)n_entries * ((int64_t)m + B);
-    return align256(slots * (3 + 256) * (int64_t)sizeof(uint32_t));
+    return rv_align256(slots * (3 + 256) * (int64_t)sizeof(uint32_t));
 }
 
 extern "C" int rv_soft_assign(const rvLossEntry* host_entries, int32_t n_entries, const rvLossParams* host_params, int32_t affinity_fn,

@@ -11,7 +11,7 @@ too: with ``DetectionCfg.eval_only_roi_instances`` the evaluator
 sweep, the log's layer and ``city_SE3_ego``; boxes are flagged by ``rv_roi_boxes`` and filtered in ``rv_eval_match_roi``.  Without
 the flag (the default) every row handed in counts, subject to the two filters above.
 
-Matching (``rv_eval_match``) and the summary (``rv_eval_summarize``) are HIP kernels; torch orders the rows (one ``sort`` on a
+Matching (``rv_eval_match``) and the summary (``rv_eval_summarize``) are HIP kernels; torch orders the rows (:mod:`.rows`: one ``sort`` on a
 combined integer key, segment offsets by ``searchsorted``: fixed output sizes, no host synchronisation).  No CPU fallback.
 """
 
@@ -27,7 +27,8 @@ from torch import Tensor
 
 from .. import _lib as L
 from ..engine import _require_cuda
-from ..math.ops.coding import DETECTION_COLUMNS, _column
+from ..math.ops.coding import _column
+from .rows import ClassMap, frame_rows, order_rows, segment_offsets, sort_key, stray_rows_message, sweep_index, task_bases
 
 METRIC_COLUMNS = ("AP", "ATE", "ASE", "AOE", "CDS")
 AVERAGE_ROW = "AVERAGE_METRICS"
@@ -91,20 +92,6 @@ def _check_roi(cfg: DetectionCfg, what: str, *inputs) -> None:
                         "eval_only_roi_instances=True)) or drop the argument")
 
 
-def _sort_key(segment: Tensor, scores: Tensor) -> Tensor:
-    """int64 key that orders rows by (segment ascending, score descending) under ONE stable ascending sort: the segment in the
-    high word, the complement of the score's order-preserving bit pattern in the low word (-0.0 counts as +0.0)."""
-    bits = (scores.float() + 0.0).contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
-    ascending = torch.where(bits >= 0x80000000, 0xFFFFFFFF - bits, bits + 0x80000000)
-    return (segment << 32) | (0xFFFFFFFF - ascending)
-
-
-def _segments(sorted_keys: Tensor, n: int, shift: int) -> Tensor:
-    """(n + 1) offsets of the segments 0 .. n - 1 in a sorted key array (a fixed-size output: nothing is read back)."""
-    bounds = torch.arange(n + 1, dtype=torch.int64, device=sorted_keys.device) << shift
-    return torch.searchsorted(sorted_keys, bounds)
-
-
 def match(dts: Tensor, scores: Tensor, dt_segment: Tensor, gts: Tensor, gt_valid: Optional[Tensor], gt_segment: Tensor, n_segments: int,
           cfg: DetectionCfg, dt_roi: Optional[Tensor] = None) -> Dict[str, Tensor]:
     """``rv_eval_match`` over rows already labelled with their (sweep, category) segment (``n_segments`` = no segment); with ``dt_roi``
@@ -117,10 +104,7 @@ def match(dts: Tensor, scores: Tensor, dt_segment: Tensor, gts: Tensor, gt_valid
     _require_cuda(dts, "detections")
     _require_cuda(gts, "ground truth")
     dev, n, m, n_thr = dts.device, dts.shape[0], gts.shape[0], len(cfg.affinity_thresholds_m)
-    sorted_keys, dt_order = torch.sort(_sort_key(dt_segment, scores), stable=True)
-    dt_off = _segments(sorted_keys, n_segments, 32)
-    gt_sorted, gt_order = torch.sort(gt_segment, stable=True)
-    gt_off = _segments(gt_sorted, n_segments, 0)
+    dt_order, dt_off, gt_order, gt_off = order_rows(dt_segment, scores, gt_segment, n_segments)
     out = {"evaluated": torch.empty(n, dtype=torch.uint8, device=dev), "tp": torch.empty((n, n_thr), dtype=torch.uint8, device=dev),
            "err": torch.empty((n, 3), dtype=torch.float32, device=dev), "matched_gt": torch.empty(n, dtype=torch.int32, device=dev),
            "gt_evaluated": torch.empty(m, dtype=torch.uint8, device=dev)}
@@ -147,8 +131,8 @@ def summarize(scores: Tensor, categories: Tensor, evaluated: Tensor, tp: Tensor,
     _require_cuda(scores, "scores")
     dev, n_cat, n_thr = scores.device, len(cfg.categories), len(cfg.affinity_thresholds_m)
     segment = torch.where(evaluated != 0, categories.to(torch.int64), n_cat)  # rows that were not evaluated: behind every category
-    sorted_keys, order = torch.sort(_sort_key(segment, scores), stable=True)
-    cat_off = _segments(sorted_keys, n_cat, 32)
+    sorted_keys, order = torch.sort(sort_key(segment, scores), stable=True)
+    cat_off = segment_offsets(sorted_keys, n_cat, 32)
     offsets = cat_off.cpu()
     n_rows = int(offsets[n_cat])
     order = order[:n_rows]
@@ -177,43 +161,18 @@ def _metrics_table(cfg: DetectionCfg, table: Tensor, n_dts: Tensor, n_gts: Tenso
     return pa.table(cols)
 
 
-def _task_bases(idx_to_category, tasks: Optional[Mapping[int, Sequence[str]]]) -> Tuple[Tuple[str, ...], Dict[int, int]]:
-    """Category names in class-index order and, per task id, the class index of its offset 0: ``DetectionHead`` numbers the
-    classes task after task (``RangeDecoder.decode``'s ``category_offset``)."""
-    if isinstance(idx_to_category, (list, tuple)):
-        names = tuple(str(c) for c in idx_to_category)
-        task_ids = offsets = None
-    else:
-        names = tuple(str(c) for c in _column(idx_to_category, "category"))
-        try:
-            task_ids, offsets = _column(idx_to_category, "task_id"), _column(idx_to_category, "offset")
-        except (KeyError, AttributeError):
-            task_ids = offsets = None
-    bases: Dict[int, int] = {}
-    if tasks is not None:
-        base = 0
-        for task_id, group in tasks.items():
-            bases[int(task_id)] = base
-            base += len(group)
-        if base != len(names):
-            raise L.RvError(f"the task table holds {base} categories, idx_to_category {len(names)}")
-    elif task_ids is not None:
-        for i, (t, o) in enumerate(zip(task_ids, offsets)):
-            if int(o) == 0:
-                bases[int(t)] = i
-    else:
-        bases[0] = 0  # one task
-    return names, bases
-
-
 class DetectionEvaluator:
     """Accumulates matched detections on the device, step by step, and reduces them to the metric table at the end.
 
     ``cfg.categories`` are evaluated (the table's rows, in that order); ``idx_to_category`` lists the category names in
     class-index order (a list, or the task frame with ``category`` [+ ``task_id``, ``offset``] columns), ``tasks`` the head's task
     table when there are several tasks and no frame.  ``max_sweeps`` bounds ``batch_index`` in an ``update`` (the launch grid has to be
-    known on the host); a row beyond it is counted on the device and ``compute`` raises.  ``atlas``: the ROI rasters of the logs
-    (``converters.av2.roi.RoiAtlas``), required exactly when ``cfg.eval_only_roi_instances`` is set.
+    known on the host).  ``atlas``: the ROI rasters of the logs (``converters.av2.roi.RoiAtlas``), required exactly when
+    ``cfg.eval_only_roi_instances`` is set.
+
+    Stray rows: a detection or annotation whose ``batch_index`` is outside ``[0, n_sweeps)`` is counted on the device and ``compute``
+    raises.  A row of a class that is not in ``cfg.categories``, of an unknown class index or of an unknown task is dropped quietly:
+    it has no segment and is never evaluated (the Waymo evaluator raises for those too).
     """
 
     def __init__(self, cfg: DetectionCfg, idx_to_category, tasks: Optional[Mapping[int, Sequence[str]]] = None, max_sweeps: int = 64,
@@ -222,9 +181,9 @@ class DetectionEvaluator:
         _check_roi(cfg, "atlas", atlas)
         self.cfg = cfg
         self.atlas = atlas
-        names, self._bases = _task_bases(idx_to_category, tasks)
+        names, bases = task_bases(idx_to_category, tasks)
         # class index -> row of cfg.categories, or -1: a class that is not evaluated
-        self._class_to_cat = [cfg.categories.index(n) if n in cfg.categories else -1 for n in names]
+        self._classes = ClassMap([cfg.categories.index(n) if n in cfg.categories else -1 for n in names], bases)
         self.max_sweeps = int(max_sweeps)
         self.reset()
 
@@ -233,15 +192,6 @@ class DetectionEvaluator:
         self._buf: Dict[str, Tensor] = {}
         self._n_gt: Optional[Tensor] = None
         self._stray: Optional[Tensor] = None
-        self._lut: Optional[Tuple[Tensor, Tensor]] = None
-
-    def _tables(self, dev) -> Tuple[Tensor, Tensor]:
-        if self._lut is None or self._lut[0].device != dev:
-            base = [-1] * (max(self._bases) + 1)
-            for t, b in self._bases.items():
-                base[t] = b
-            self._lut = (torch.tensor(self._class_to_cat, dtype=torch.int64, device=dev), torch.tensor(base, dtype=torch.int64, device=dev))
-        return self._lut
 
     def _append(self, rows: Dict[str, Tensor]) -> None:
         n = next(iter(rows.values())).shape[0]
@@ -275,24 +225,8 @@ class DetectionEvaluator:
                 raise L.RvError(f"roi describes {n_roi} sweeps, n_sweeps = {n_sweeps}")
             n_sweeps = n_roi
         n_sweeps = self.max_sweeps if n_sweeps is None else int(n_sweeps)
-        class_to_cat, task_base = self._tables(dev)
-
-        def segment_of(sweep: Tensor, cls: Tensor, known: Tensor):
-            known = known & (cls >= 0) & (cls < class_to_cat.shape[0])
-            cat = torch.where(known, class_to_cat[cls.clamp(0, class_to_cat.shape[0] - 1)], -1)
-            inside = (sweep >= 0) & (sweep < n_sweeps)
-            return torch.where(inside & (cat >= 0), sweep * n_cat + cat, n_sweeps * n_cat), cat, (~inside).sum()
-
-        dts = params.detach().float().reshape(-1, 10).contiguous()
-        sc = scores.detach().float().reshape(-1).contiguous()
-        cls = categories.detach().reshape(-1).to(torch.int64)
-        dt_segment, dt_cat, stray_dts = segment_of(batch_index.detach().reshape(-1).to(torch.int64), cls, torch.ones_like(cls, dtype=torch.bool))
-        ann = annotations.detach().to(dev).reshape(-1, 13)  # (the loader's rows are host tensors: a copy, no read-back)
-        gts = ann[:, :10].float().contiguous()
-        task = ann[:, 10].to(torch.int64)
-        known = (task >= 0) & (task < task_base.shape[0])
-        base = task_base[task.clamp(0, task_base.shape[0] - 1)]
-        gt_segment, gt_cat, stray_gts = segment_of(ann[:, 12].to(torch.int64), base + ann[:, 11].to(torch.int64), known & (base >= 0))
+        dt, sc, gt = self._classes.step_rows(params, scores, categories, batch_index, annotations, n_sweeps, n_cat)
+        stray = (~dt.inside).sum() + (~gt.inside).sum()  # the AV2 rule: only the sweep decides (the class docstring)
         gt_valid = None if num_interior_pts is None else (num_interior_pts.to(dev).reshape(-1) > 0).to(torch.uint8).contiguous()
         if self._n_gt is None:
             self._n_gt = torch.zeros(n_cat + 1, dtype=torch.int64, device=dev)
@@ -304,16 +238,16 @@ class DetectionEvaluator:
             if self.atlas.device != dev:
                 self.atlas = self.atlas.to(dev)
             layer_index, city_SE3_ego = roi
-            # (rows outside the step's sweeps are counted by segment_of already: these launches count into a spare)
+            # (rows outside the step's sweeps are counted above already: these launches count into a spare)
             spare = torch.zeros((), dtype=torch.int64, device=dev)
-            dt_roi = roi_boxes(dts, batch_index.detach().reshape(-1).to(torch.int64), layer_index, city_SE3_ego, self.atlas, stray=spare)
-            gt_roi = roi_boxes(gts, ann[:, 12].to(torch.int64), layer_index, city_SE3_ego, self.atlas, stray=spare)
+            dt_roi = roi_boxes(dt.rows, dt.sweep, layer_index, city_SE3_ego, self.atlas, stray=spare)
+            gt_roi = roi_boxes(gt.rows, gt.sweep, layer_index, city_SE3_ego, self.atlas, stray=spare)
             gt_valid = gt_roi if gt_valid is None else gt_valid & gt_roi
-        out = match(dts, sc, dt_segment, gts, gt_valid, gt_segment, n_sweeps * n_cat, self.cfg, dt_roi=dt_roi)
-        self._append({"score": sc, "category": dt_cat, "evaluated": out["evaluated"], "tp": out["tp"], "err": out["err"]})
+        out = match(dt.rows, sc, dt.segment, gt.rows, gt_valid, gt.segment, n_sweeps * n_cat, self.cfg, dt_roi=dt_roi)
+        self._append({"score": sc, "category": dt.group, "evaluated": out["evaluated"], "tp": out["tp"], "err": out["err"]})
         # (ground truth of a class that is not evaluated is never flagged: its slot is the spare one at the end)
-        self._n_gt.index_add_(0, torch.where(gt_cat >= 0, gt_cat, n_cat), out["gt_evaluated"].to(torch.int64))
-        self._stray += stray_dts + stray_gts
+        self._n_gt.index_add_(0, torch.where(gt.group >= 0, gt.group, n_cat), out["gt_evaluated"].to(torch.int64))
+        self._stray += stray
 
     def _gathered(self) -> Tuple[Dict[str, Tensor], Tensor, Tensor]:
         """The accumulators, concatenated over the ranks when ``torch.distributed`` is initialised (rank order; sizes first,
@@ -346,8 +280,7 @@ class DetectionEvaluator:
             raise L.RvError("DetectionEvaluator.compute() before any update()")
         rows, n_gt, stray = self._gathered()
         if int(stray) != 0:
-            raise L.RvError(f"{int(stray)} rows had a batch_index outside [0, n_sweeps): pass the step's batch size to update() "
-                            f"(or a larger max_sweeps, now {self.max_sweeps})")
+            raise L.RvError(stray_rows_message(int(stray), self.max_sweeps))
         n_gt = n_gt.contiguous()
         table, _, n_dts = summarize(rows["score"], rows["category"], rows["evaluated"], rows["tp"], rows["err"], n_gt, self.cfg)
         return _metrics_table(self.cfg, table, n_dts, n_gt.cpu())
@@ -377,11 +310,9 @@ def evaluate(dts, gts, cfg: DetectionCfg, device: Any = "cuda", atlas=None, pose
     cat_index = {c: i for i, c in enumerate(cfg.categories)}
 
     def rows_of(frame):
-        box = np.stack([np.asarray(_column(frame, c), dtype=np.float32) for c in DETECTION_COLUMNS], 1) if frame.num_rows else np.zeros((0, 10), np.float32)
-        sweep = [sweeps.setdefault((str(l), int(t)), len(sweeps)) for l, t in zip(_column(frame, "log_id"), _column(frame, "timestamp_ns"))]
         cat = [cat_index.get(str(c), -1) for c in _column(frame, "category")]
-        sweep_t, cat_t = torch.tensor(sweep, dtype=torch.int64, device=dev), torch.tensor(cat, dtype=torch.int64, device=dev)
-        return torch.from_numpy(box).to(dev), sweep_t, cat_t
+        return (torch.from_numpy(frame_rows(frame)).to(dev), torch.from_numpy(sweep_index(frame, sweeps)).to(dev),
+                torch.tensor(cat, dtype=torch.int64, device=dev))
 
     dt_box, dt_sweep, dt_cat = rows_of(dts)
     gt_box, gt_sweep, gt_cat = rows_of(gts)

@@ -7,7 +7,7 @@ DESIGN.md 8.3) and not pinned against that library's binaries.  Pinned to the re
 (``evaluate.py:325-333``), the object types (``:68``), frames = the sweeps with ground truth (``:382-389``), yaw from the quaternion
 (``:269-286``, rounded to fp32 with the box ``:407-408``), the configuration (``:289-319``) and the result layout (``:70-243``).
 
-The three steps (``rv_waymo_iou``, ``rv_waymo_match``, ``rv_waymo_summarize``) are HIP kernels; torch orders the rows (one stable
+The three steps (``rv_waymo_iou``, ``rv_waymo_match``, ``rv_waymo_summarize``) are HIP kernels; torch orders the rows (:mod:`.rows`: one stable
 ``sort`` per side, segment offsets by ``searchsorted``).  ``update`` reads nothing back and keeps only the integer count tables
 (2 x 16 x 2 x 101 x 4 int64) between steps.  No CPU fallback.
 """
@@ -24,8 +24,8 @@ from torch import Tensor
 
 from .. import _lib as L
 from ..engine import _require_cuda
-from ..math.ops.coding import DETECTION_COLUMNS, _column
-from .detection import _segments, _sort_key, _task_bases
+from ..math.ops.coding import _column
+from .rows import ClassMap, frame_rows, order_rows, stray_rows_message, sweep_index, task_bases
 
 OBJECT_TYPES = {"VEHICLE": 1, "PEDESTRIAN": 2, "SIGN": 3, "CYCLIST": 4}  # evaluate.py:68
 RANGE_SHARDS = ((0.0, math.inf), (0.0, 30.0), (30.0, 50.0), (50.0, math.inf))  # shard 0 = all ranges
@@ -106,10 +106,7 @@ def accumulate(dts: Tensor, scores: Tensor, dt_segment: Tensor, gts: Tensor, gt_
     dev, n, m, n_seg = dts.device, dts.shape[0], gts.shape[0], 4 * n_sweeps
     if len(cfg.iou_thresholds) != 5:
         raise L.RvError(f"{len(cfg.iou_thresholds)} IoU thresholds (5: index 0 unused, then VEHICLE, PEDESTRIAN, SIGN, CYCLIST)")
-    sorted_keys, dt_order = torch.sort(_sort_key(dt_segment, scores), stable=True)
-    dt_off = _segments(sorted_keys, n_seg, 32)
-    gt_sorted, gt_order = torch.sort(gt_segment, stable=True)
-    gt_off = _segments(gt_sorted, n_seg, 0)
+    dt_order, dt_off, gt_order, gt_off = order_rows(dt_segment, scores, gt_segment, n_seg)
     if sweep_valid is None:
         inside = (gt_segment >= 0) & (gt_segment < n_seg) & (gt_level != 0)
         sweep_valid = torch.zeros(n_sweeps + 1, dtype=torch.int64, device=dev).index_add_(
@@ -147,8 +144,7 @@ def _result_table(values: Tensor):
 
 def _raise_on_errors(errors: Sequence[int], stray: int, max_sweeps: int) -> None:
     if stray:
-        raise L.RvError(f"{stray} rows had a batch_index outside [0, n_sweeps): pass the step's batch size to update() "
-                        f"(or a larger max_sweeps, now {max_sweeps})")
+        raise L.RvError(stray_rows_message(stray, max_sweeps))
     for count, what in zip(errors, _ERRORS):
         if count:
             raise L.RvError(f"{count} {what}: nothing is truncated, the metric is not computed")
@@ -159,37 +155,32 @@ class WaymoDetectionEvaluator:
 
     ``idx_to_category`` lists the category names in class-index order (a list, or the task frame with ``category`` [+ ``task_id``,
     ``offset``] columns), ``tasks`` the head's task table when there are several tasks and no frame; every name must be one of
-    ``OBJECT_TYPES`` (the reference's ``replace_strict``).  ``max_sweeps`` bounds ``batch_index`` in an ``update``; a row beyond it is
-    counted on the device and ``compute`` raises, as it does for a (sweep, type) with more rows than ``RV_WAYMO_MAX_DTS`` /
-    ``RV_WAYMO_MAX_GTS``.
+    ``OBJECT_TYPES`` (the reference's ``replace_strict``).  ``max_sweeps`` bounds ``batch_index`` in an ``update``.
+
+    Stray rows: a detection or annotation whose ``batch_index`` is outside ``[0, n_sweeps)``, or whose class index or task is not in
+    the table, is counted on the device and ``compute`` raises (every class here is an object type, so nothing is dropped quietly; the
+    AV2 evaluator drops rows of classes it does not evaluate).  ``compute`` also raises for a (sweep, type) with more rows than
+    ``RV_WAYMO_MAX_DTS`` / ``RV_WAYMO_MAX_GTS``.
     """
 
     def __init__(self, cfg: Optional[WaymoDetectionCfg] = None, idx_to_category=tuple(OBJECT_TYPES), tasks: Optional[Mapping[int, Sequence[str]]] = None,
                  max_sweeps: int = 64) -> None:
         self.cfg = cfg or WaymoDetectionCfg()
-        names, self._bases = _task_bases(idx_to_category, tasks)
+        names, bases = task_bases(idx_to_category, tasks)
         unknown = [n for n in names if n not in OBJECT_TYPES]
         if unknown:
             raise L.RvError(f"categories {unknown} are not Waymo object types {tuple(OBJECT_TYPES)}")
-        self._class_to_type = [OBJECT_TYPES[n] for n in names]
+        # (configuration, not state: kept over reset(), whose next update stays free of copies)
+        self._classes = ClassMap([OBJECT_TYPES[n] - 1 for n in names], bases)
         if not 1 <= int(max_sweeps) <= L.WAYMO_MAX_SWEEPS:
             raise L.RvError(f"max_sweeps = {max_sweeps} (1 .. {L.WAYMO_MAX_SWEEPS})")
         self.max_sweeps = int(max_sweeps)
-        self._lut: Optional[Tuple[Tensor, Tensor]] = None  # (configuration, not state: kept over reset(), whose next update stays free of copies)
         self.reset()
 
     def reset(self) -> None:
         self._tables: Optional[Tensor] = None
         self._errors: Optional[Tensor] = None
         self._stray: Optional[Tensor] = None
-
-    def _luts(self, dev) -> Tuple[Tensor, Tensor]:
-        if self._lut is None or self._lut[0].device != dev:
-            base = [-1] * (max(self._bases) + 1)
-            for t, b in self._bases.items():
-                base[t] = b
-            self._lut = (torch.tensor(self._class_to_type, dtype=torch.int64, device=dev), torch.tensor(base, dtype=torch.int64, device=dev))
-        return self._lut
 
     def _state(self, dev) -> None:
         if self._tables is None:
@@ -210,29 +201,13 @@ class WaymoDetectionEvaluator:
         n_sweeps = self.max_sweeps if n_sweeps is None else int(n_sweeps)
         if not 1 <= n_sweeps <= L.WAYMO_MAX_SWEEPS:
             raise L.RvError(f"n_sweeps = {n_sweeps} (1 .. {L.WAYMO_MAX_SWEEPS})")
-        class_to_type, task_base = self._luts(dev)
-        n_cls = class_to_type.shape[0]
-
-        def segment_of(sweep: Tensor, cls: Tensor, known: Tensor):
-            known = known & (cls >= 0) & (cls < n_cls)
-            inside = (sweep >= 0) & (sweep < n_sweeps)
-            seg = sweep * 4 + class_to_type[cls.clamp(0, n_cls - 1)] - 1
-            return torch.where(inside & known, seg, 4 * n_sweeps), (~(inside & known)).sum()
-
-        dts = boxes_from_rows(params.detach().reshape(-1, 10))
-        sc = scores.detach().float().reshape(-1).contiguous()
-        cls = categories.detach().reshape(-1).to(torch.int64)
-        dt_segment, stray_dts = segment_of(batch_index.detach().reshape(-1).to(torch.int64), cls, torch.ones_like(cls, dtype=torch.bool))
-        ann = annotations.detach().to(dev).reshape(-1, 13)  # (the loader's rows are host tensors: a copy, no read-back)
-        gts = boxes_from_rows(ann[:, :10])
-        task = ann[:, 10].to(torch.int64)
-        known = (task >= 0) & (task < task_base.shape[0])
-        base = task_base[task.clamp(0, task_base.shape[0] - 1)]
-        gt_segment, stray_gts = segment_of(ann[:, 12].to(torch.int64), base + ann[:, 11].to(torch.int64), known & (base >= 0))
+        dt, sc, gt = self._classes.step_rows(params, scores, categories, batch_index, annotations, n_sweeps, 4)
+        stray = (~(dt.inside & dt.known)).sum() + (~(gt.inside & gt.known)).sum()  # the Waymo rule: sweep and class (the class docstring)
         level = difficulty_levels(num_interior_pts.detach().to(dev), None if difficulty_level is None else difficulty_level.detach().to(dev))
         self._state(dev)
-        accumulate(dts, sc, dt_segment, gts, level, gt_segment, n_sweeps, self.cfg, self._tables, self._errors)
-        self._stray += stray_dts + stray_gts
+        accumulate(boxes_from_rows(dt.rows), sc, dt.segment, boxes_from_rows(gt.rows), level, gt.segment, n_sweeps, self.cfg, self._tables,
+                   self._errors)
+        self._stray += stray
 
     def tables(self) -> Tensor:
         """The (2, 16, 2, 101, 4) int64 counts seen since ``reset``, summed over the ranks under ``torch.distributed``; raises for rows
@@ -286,21 +261,13 @@ def evaluate_waymo(dts, gts, device: Any = "cuda", cfg: Optional[WaymoDetectionC
             raise L.RvError(f"categories {unknown} are not Waymo object types {tuple(OBJECT_TYPES)}")
         return np.asarray([OBJECT_TYPES[c] for c in names], dtype=np.int64)
 
-    def rows_of(frame) -> np.ndarray:
-        if not frame.num_rows:
-            return np.zeros((0, 10), np.float32)
-        return np.stack([np.asarray(_column(frame, c), dtype=np.float32) for c in DETECTION_COLUMNS], 1)
-
     gt_type, dt_type = types_of(gts), types_of(dts)
     npts = np.asarray(_column(gts, "num_interior_pts"), dtype=np.int64)
     given = np.asarray(_column(gts, "difficulty_level"), dtype=np.int64) if "difficulty_level" in gts.column_names else np.zeros_like(npts)
     frames: Dict[Tuple[str, int], int] = {}
-    gt_sweep = np.full(len(npts), -1, np.int64)
-    for i, key in enumerate(zip(_column(gts, "log_id"), _column(gts, "timestamp_ns"))):
-        if npts[i] > 0:
-            gt_sweep[i] = frames.setdefault((str(key[0]), int(key[1])), len(frames))
-    dt_sweep = np.asarray([frames.get((str(l), int(t)), -1) for l, t in zip(_column(dts, "log_id"), _column(dts, "timestamp_ns"))], dtype=np.int64)
-    dt_rows, gt_rows = rows_of(dts), rows_of(gts)
+    gt_sweep = sweep_index(gts, frames, keep=npts > 0)
+    dt_sweep = sweep_index(dts, frames, add=False)
+    dt_rows, gt_rows = frame_rows(dts), frame_rows(gts)
     score = np.asarray(_column(dts, "score"), dtype=np.float32)
     tables = torch.zeros(TABLE_SHAPE, dtype=torch.int64, device=dev)
     errors = torch.zeros(4, dtype=torch.int32, device=dev)

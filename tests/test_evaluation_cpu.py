@@ -55,14 +55,14 @@ def test_the_cases_cover_what_the_declaration_singles_out():
 
 
 def test_sort_key_orders_like_a_stable_descending_argsort():
-    from range_view_3d_detection_amd.evaluation.detection import _sort_key
+    from range_view_3d_detection_amd.evaluation.rows import sort_key
 
     g = np.random.default_rng(5)
     scores = np.round(g.random(4000), 2).astype(np.float32)  # many ties
     scores[:40] = [0.0, -0.0, 1e-40, -1e-40] * 10  # signed zeros tie, denormals do not
     scores[40:60] = -scores[60:80]
     seg = g.integers(0, 7, 4000)
-    order = torch.sort(_sort_key(torch.from_numpy(seg), torch.from_numpy(scores)), stable=True)[1].numpy()
+    order = torch.sort(sort_key(torch.from_numpy(seg), torch.from_numpy(scores)), stable=True)[1].numpy()
     want = np.concatenate([np.nonzero(seg == s)[0][np.argsort(-scores[seg == s], kind="stable")] for s in range(7)])
     assert np.array_equal(order, want)
 
@@ -130,11 +130,11 @@ def test_update_on_cpu_tensors_raises():
 
 def test_class_numbering_follows_the_task_table():
     """Annotation rows carry (task_id, offset); the head numbers classes task after task (``RangeDecoder.decode``)."""
-    from range_view_3d_detection_amd.evaluation.detection import _task_bases
+    from range_view_3d_detection_amd.evaluation.rows import task_bases
 
     tasks = {0: ["REGULAR_VEHICLE"], 1: ["BOLLARD", "PEDESTRIAN"], 2: ["BUS"]}
-    names, bases = _task_bases(["REGULAR_VEHICLE", "BOLLARD", "PEDESTRIAN", "BUS"], tasks)
+    names, bases = task_bases(["REGULAR_VEHICLE", "BOLLARD", "PEDESTRIAN", "BUS"], tasks)
     assert bases == {0: 0, 1: 1, 2: 3} and names[bases[1] + 1] == "PEDESTRIAN"
     frame = {"category": list(names), "task_id": [0, 1, 1, 2], "offset": [0, 0, 1, 0]}
-    assert _task_bases(frame, None) == (names, bases)
-    assert _task_bases(["A", "B"], None)[1] == {0: 0}
+    assert task_bases(frame, None) == (names, bases)
+    assert task_bases(["A", "B"], None)[1] == {0: 0}

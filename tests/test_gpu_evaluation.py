@@ -51,14 +51,14 @@ def test_hand_computed_cases(case):
 def _scene(g, n_sweeps, n_cat, max_gt=60, max_dt=1000, big=None):
     """Random sweeps: per (sweep, category) 0 .. max_gt ground truths and 0 .. max_dt detections drawn around them (sigma 0.3 .. 3 m),
     scores on a coarse grid (ties), some rows beyond 150 m, some categories empty on either side, rows in shuffled order.
-    ``big`` = (sweep, category, ground truths): one segment with that many boxes."""
+    ``big`` = (sweep, category, ground truths[, detections = 400]): one segment with that many boxes."""
     dts, scores, dt_s, dt_c, gts, npts, gt_s, gt_c = [], [], [], [], [], [], [], []
     for s in range(n_sweeps):
         for c in range(n_cat):
             m = int(g.integers(0, max_gt + 1)) if g.random() > 0.15 else 0
             n = int(g.integers(0, max_dt + 1) if g.random() < 0.2 else g.integers(0, 150)) if g.random() > 0.15 else 0
             if big and (s, c) == big[:2]:
-                m, n = big[2], 400
+                m, n = big[2], big[3] if len(big) > 3 else 400
             centre = np.concatenate([g.uniform(-160, 160, (m, 2)), g.uniform(-2, 2, (m, 1))], 1)
             gt = np.concatenate([centre, g.uniform(0.5, 6, (m, 3)), g.uniform(-math.pi, math.pi, (m, 1))], 1)
             gts.append(gt), npts.append(g.integers(0, 4, m)), gt_s.append(np.full(m, s)), gt_c.append(np.full(m, c))

@@ -221,6 +221,33 @@ def test_matcher_against_the_restatement_on_segments_longer_than_a_tile():
         assert 50 < out["evaluated"].sum() < (scene["dt_roi"] != 0).sum()
 
 
+def test_matcher_keeps_the_cap_and_the_packed_list_across_a_tile_boundary():
+    """One segment of 600 detections (three tiles of the scan), more of them in range than the cap of 300, so the cap falls inside
+    the second tile; flags set and clear on both sides of every tile boundary: the rank of the first scan and the slot of the second
+    both carry over tiles."""
+    g = np.random.default_rng(np.random.randint(1 << 30))
+    scene = _scene(g, 1, 1, big=(0, 0, 40, 600))
+    n, m = len(scene["dts"]), len(scene["gts"])
+    assert (n, m) == (600, 40)
+    scene["dt_roi"], scene["gt_roi"] = g.integers(0, 2, n).astype(np.uint8), g.integers(0, 2, m).astype(np.uint8)
+    in_range = (scene["dts"][:, :3].astype(np.float64) ** 2).sum(1) <= 150.0 ** 2
+    by_score = np.argsort(-scene["scores"], kind="stable")
+    assert in_range.sum() > 300 and 256 < np.nonzero(np.cumsum(in_range[by_score]) == 300)[0][0] < 512
+    for tile in (by_score[:256], by_score[256:512], by_score[512:]):
+        assert 0 < scene["dt_roi"][tile].sum() < len(tile)
+    cfg = _cfg(1, max_num_dts_per_category=300)
+    out = _match(scene, cfg, True, True)
+    want = ref.match_roi_ref(scene["dts"], scene["scores"], scene["dt_sweep"], scene["dt_cat"], scene["dt_roi"], scene["gts"], scene["gt_valid"],
+                             scene["gt_roi"], scene["gt_sweep"], scene["gt_cat"], 1, 1, cfg)
+    for key in ("evaluated", "tp", "matched_gt", "gt_evaluated"):
+        assert np.array_equal(out[key], want[key]), key
+    assert np.array_equal(np.isnan(out["err"]), np.isnan(want["err"])) and np.allclose(out["err"], want["err"], rtol=0, atol=1e-5, equal_nan=True)
+    assert 100 < out["evaluated"].sum() < 300 and out["evaluated"][by_score[256:]].sum() > 10 and out["matched_gt"].max() >= 0
+    plain = eval_ref.match_ref(scene["dts"], scene["scores"], scene["dt_sweep"], scene["dt_cat"], scene["gts"], scene["gt_valid"], scene["gt_sweep"],
+                               scene["gt_cat"], 1, 1, cfg)
+    assert np.array_equal(_match(scene, cfg, False, False)["evaluated"], plain["evaluated"]) and plain["evaluated"].sum() == 300
+
+
 def _small_scene(g):
     """The existing evaluation test's scene scaled down: 4 sweeps x 5 categories, 200 detections with tied scores, rows by sweep."""
     scene = _scene(g, 4, 5, max_gt=12, max_dt=60)
@@ -265,12 +292,11 @@ def test_an_all_covering_roi_changes_nothing():
 
     # rv_eval_match_roi without flags is rv_eval_match, array for array
     n_cat, n_seg, n, m = 5, 20, len(scene["dts"]), len(scene["gts"])
-    from range_view_3d_detection_amd.evaluation.detection import _segments, _sort_key
+    from range_view_3d_detection_amd.evaluation.rows import order_rows
 
     dts, gts, valid = _dev(scene["dts"]), _dev(scene["gts"]), _dev(scene["gt_valid"])
-    keys, dt_order = torch.sort(_sort_key(_dev(scene["dt_sweep"]) * n_cat + _dev(scene["dt_cat"]), _dev(scene["scores"])), stable=True)
-    gt_sorted, gt_order = torch.sort(_dev(scene["gt_sweep"]) * n_cat + _dev(scene["gt_cat"]), stable=True)
-    dt_off, gt_off = _segments(keys, n_seg, 32), _segments(gt_sorted, n_seg, 0)
+    dt_order, dt_off, gt_order, gt_off = order_rows(_dev(scene["dt_sweep"]) * n_cat + _dev(scene["dt_cat"]), _dev(scene["scores"]),
+                                                    _dev(scene["gt_sweep"]) * n_cat + _dev(scene["gt_cat"]), n_seg)
     thr = (ctypes.c_double * 4)(0.5, 1.0, 2.0, 4.0)
     results = []
     for name in ("rv_eval_match", "rv_eval_match_roi"):
