@@ -1201,6 +1201,11 @@ int rv_waymo_range_image_to_batch(const float* range_image, const double* extrin
                                   const int32_t* host_feat_src, const int32_t* host_feat_op, int32_t pad, int32_t circular,
                                   float* features, float* cart, uint8_t* mask, int64_t* num_pts, rvStream stream);
 
+/* The debug panels of the training loop (rendering/tensorboard.py) and mmcv's IoU ops (csrc/render.hip) are declared, with their full
+ * semantics, in include/rv3d_render.h -- a header of its own beside this one, which it includes: this file's list of prototypes, and
+ * that of the headers it includes, stay the lists that the binding's census counts.  The binding (`_lib.py`) types its entries
+ * exactly as it types this file's. */
+
 #ifdef __cplusplus
 }
 #endif

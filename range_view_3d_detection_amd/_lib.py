@@ -1,8 +1,8 @@
 """ctypes binding of ``librv3d_hip.so`` (the C ABI declared in ``include/rv3d.h``).
 
 ``include/rv3d.h`` is the single source of the binding's types: ``prototypes()`` parses the declarations in its own text once per
-process, ``included_prototypes()`` those of the headers it includes (``rv3d_wnms.h``), and ``load()`` sets ``restype`` / ``argtypes`` of
-every symbol of both tables.  Call sites pass plain Python values (``int``,
+process, ``included_prototypes()`` those of the headers it includes (``rv3d_wnms.h``), ``companion_prototypes()`` those of the headers
+beside it that include it (``rv3d_render.h``), and ``load()`` sets ``restype`` / ``argtypes`` of every symbol of the three tables.  Call sites pass plain Python values (``int``,
 ``float``, ``None``, ``ptr(t)``, a ctypes Structure or array); a wrong argument count or a wrong struct raises in Python.
 
 There is deliberately no CPU fallback: if the library is missing or a call fails the host
@@ -25,6 +25,8 @@ LIB_PATH = os.environ.get("RV3D_LIB") or os.path.join(_HERE, "librv3d_hip.so")  
 # the same sources built with fp16 operands (csrc/common.h, RV_OPERAND_F16): inference under torch.autocast(dtype=float16)
 LIB_PATH_F16 = os.environ.get("RV3D_LIB_F16") or os.path.join(_HERE, "librv3d_hip_f16.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rv3d.h")
+# headers beside rv3d.h that include IT and declare further entries of the same library (rv3d_render.h: the debug panels, csrc/render.hip)
+COMPANION_HEADERS = ("rv3d_render.h",)
 
 # flags (mirror include/rv3d.h)
 IN_AFFINE, IN_RELU, OUT_F32, OUT_BIAS, OUT_STATS, OUT_ACCUM, OUT_RELU = 1, 2, 4, 8, 16, 32, 64
@@ -236,6 +238,19 @@ def included_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], .
     return table
 
 
+@functools.lru_cache(maxsize=None)
+def companion_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    """The same table for ``COMPANION_HEADERS``: headers in include/ that include rv3d.h and declare further entries (``rv3d_render.h``).
+    ``load()`` types them like the header's own; one that is missing is an error."""
+    table = {}
+    for name in COMPANION_HEADERS:
+        path = os.path.join(os.path.dirname(HEADER_PATH), name)
+        if not os.path.exists(path):
+            raise RvError(f"the companion header {path} is missing")
+        table.update(_parse_header(path))
+    return table
+
+
 def declared_symbols() -> List[str]:
     """Every function name declared in include/rv3d.h (used by the export test)."""
     return sorted(prototypes())
@@ -268,11 +283,11 @@ def _dlopen(path: str) -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     # restype / argtypes of every declared symbol; the parameter names make ctypes refuse extra arguments too (a bare cdecl
     # function pointer ignores them) and accept them as keywords
-    for name, (restype, params) in {**prototypes(), **included_prototypes()}.items():
+    for name, (restype, params) in {**prototypes(), **included_prototypes(), **companion_prototypes()}.items():
         try:
             fn = ctypes.CFUNCTYPE(restype, *[t for t, _ in params])((name, lib), tuple((1, p) for _, p in params))
         except AttributeError:
-            raise RvError(f"{path} does not export {name}, which include/rv3d.h (or a header it includes) declares") from None
+            raise RvError(f"{path} does not export {name}, which include/rv3d.h (or a header it includes, or a companion header) declares") from None
         setattr(lib, name, fn)
     return lib
 

@@ -78,28 +78,6 @@ __global__ __launch_bounds__(THREADS) void waymo_offsets_kernel(const Segments s
     }
 }
 
-__device__ float2 waymo_iou_pair(const float* a, const float* b) {
-    float2 out = make_float2(0.0f, 0.0f);
-    // circumscribed circles of the footprints apart (with a margin far above the rounding of the clip): the intersection is empty
-    const float dx = a[0] - b[0], dy = a[1] - b[1];
-    const float reach = 0.5f * (sqrtf(a[3] * a[3] + a[4] * a[4]) + sqrtf(b[3] * b[3] + b[4] * b[4]));
-    if (dx * dx + dy * dy > reach * reach * 1.001f + 1e-6f) return out;
-    float ra[5], rb[5], sa, ca, sb, cb, area;  // boxes are [x, y, z, l, w, h, yaw]; the rectangles rv_rotated_iou takes
-    rect_of_box(a[0], a[1], a[3], a[4], a[6], ra), rect_of_box(b[0], b[1], b[3], b[4], b[6], rb);
-    yaw_sincos(a[6], sa, ca), yaw_sincos(b[6], sb, cb);
-    out.x = rotated_iou_inter(ra, sa, ca, rb, sb, cb, area);
-    const float hha = 0.5f * a[5], hhb = 0.5f * b[5];
-    const float top_a = a[2] + hha, top_b = b[2] + hhb, bot_a = a[2] - hha, bot_b = b[2] - hhb;
-    const float top = top_a < top_b ? top_a : top_b, bot = bot_a > bot_b ? bot_a : bot_b;
-    const float dz = top - bot > 0.0f ? top - bot : 0.0f;
-    const float vol_a = (a[3] * a[4]) * a[5], vol_b = (b[3] * b[4]) * b[5];
-    if (!(vol_a > 0.0f) || !(vol_b > 0.0f)) return out;
-    const float inter = area * dz;
-    const float uni = vol_a + vol_b - inter;
-    if (uni > 0.0f) out.y = inter / uni;
-    return out;
-}
-
 __global__ __launch_bounds__(THREADS) void waymo_iou_kernel(const Segments s, const float* dts, const float* gts, int n_seg,
                                                             const int64_t* pair_off, int64_t capacity, float2* iou) {
     int64_t total = pair_off[n_seg];

@@ -1,6 +1,6 @@
 // Rotated-BEV-IoU of two boxes [x1, y1, x2, y2, ry], the rectangle of a box and the sin / cos the IoU takes.  Users: nms_core.h (the
-// pair masks of nms.hip and nms2.hip), nms.hip (sin / cos pass, rv_rotated_iou), nms2.hip (gather), softassign.hip (BEV affinity) and
-// evaluate_waymo.hip (BEV / 3-D IoU); all include it where fused multiply-add contraction is off, so that the result matches
+// pair masks of nms.hip and nms2.hip), nms.hip (sin / cos pass, rv_rotated_iou), nms2.hip (gather), softassign.hip (BEV affinity),
+// evaluate_waymo.hip and render.hip (BEV / 3-D IoU); all include it where fused multiply-add contraction is off, so that the result matches
 // oracle/c/oracle.c bit for bit.
 #pragma once
 #include "common.h"
@@ -90,6 +90,30 @@ __device__ __forceinline__ float rotated_iou_inter(const float* a, float sa, flo
 __device__ float rotated_iou(const float* a, float sa, float ca, const float* b, float sb, float cb) {
     float inter;
     return rotated_iou_inter(a, sa, ca, b, sb, cb, inter);
+}
+
+// (BEV, 3-D) IoU of two boxes [x, y, z, l, w, h, yaw], z the CENTRE (include/rv3d.h, "IoU of a pair"): ONE function for
+// waymo_iou_kernel (evaluate_waymo.hip) and boxes_iou3d_kernel (render.hip), so that the two agree bit for bit
+__device__ float2 waymo_iou_pair(const float* a, const float* b) {
+    float2 out = make_float2(0.0f, 0.0f);
+    // circumscribed circles of the footprints apart (with a margin far above the rounding of the clip): the intersection is empty
+    const float dx = a[0] - b[0], dy = a[1] - b[1];
+    const float reach = 0.5f * (sqrtf(a[3] * a[3] + a[4] * a[4]) + sqrtf(b[3] * b[3] + b[4] * b[4]));
+    if (dx * dx + dy * dy > reach * reach * 1.001f + 1e-6f) return out;
+    float ra[5], rb[5], sa, ca, sb, cb, area;  // boxes are [x, y, z, l, w, h, yaw]; the rectangles rv_rotated_iou takes
+    rect_of_box(a[0], a[1], a[3], a[4], a[6], ra), rect_of_box(b[0], b[1], b[3], b[4], b[6], rb);
+    yaw_sincos(a[6], sa, ca), yaw_sincos(b[6], sb, cb);
+    out.x = rotated_iou_inter(ra, sa, ca, rb, sb, cb, area);
+    const float hha = 0.5f * a[5], hhb = 0.5f * b[5];
+    const float top_a = a[2] + hha, top_b = b[2] + hhb, bot_a = a[2] - hha, bot_b = b[2] - hhb;
+    const float top = top_a < top_b ? top_a : top_b, bot = bot_a > bot_b ? bot_a : bot_b;
+    const float dz = top - bot > 0.0f ? top - bot : 0.0f;
+    const float vol_a = (a[3] * a[4]) * a[5], vol_b = (b[3] * b[4]) * b[5];
+    if (!(vol_a > 0.0f) || !(vol_b > 0.0f)) return out;
+    const float inter = area * dz;
+    const float uni = vol_a + vol_b - inter;
+    if (uni > 0.0f) out.y = inter / uni;
+    return out;
 }
 
 }  // namespace
