@@ -1204,7 +1204,8 @@ int rv_waymo_range_image_to_batch(const float* range_image, const double* extrin
 /* The debug panels of the training loop (rendering/tensorboard.py) and mmcv's IoU ops (csrc/render.hip) are declared, with their full
  * semantics, in include/rv3d_render.h -- a header of its own beside this one, which it includes: this file's list of prototypes, and
  * that of the headers it includes, stay the lists that the binding's census counts.  The binding (`_lib.py`) types its entries
- * exactly as it types this file's. */
+ * exactly as it types this file's.  include/rv3d_optim.h is a second header of that kind: rv_adamw_step for several parameter groups,
+ * per-parameter step counts, amsgrad and maximize (rv_adamw_step_groups). */
 
 #ifdef __cplusplus
 }

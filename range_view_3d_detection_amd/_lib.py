@@ -2,7 +2,8 @@
 
 ``include/rv3d.h`` is the single source of the binding's types: ``prototypes()`` parses the declarations in its own text once per
 process, ``included_prototypes()`` those of the headers it includes (``rv3d_wnms.h``), ``companion_prototypes()`` those of the headers
-beside it that include it (``rv3d_render.h``), and ``load()`` sets ``restype`` / ``argtypes`` of every symbol of the three tables.  Call sites pass plain Python values (``int``,
+beside it that include it (``rv3d_render.h``), ``optim_prototypes()`` those of ``rv3d_optim.h`` (another such header: the grouped optimiser
+step), and ``load()`` sets ``restype`` / ``argtypes`` of every symbol of the four tables.  Call sites pass plain Python values (``int``,
 ``float``, ``None``, ``ptr(t)``, a ctypes Structure or array); a wrong argument count or a wrong struct raises in Python.
 
 There is deliberately no CPU fallback: if the library is missing or a call fails the host
@@ -27,6 +28,8 @@ LIB_PATH_F16 = os.environ.get("RV3D_LIB_F16") or os.path.join(_HERE, "librv3d_hi
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rv3d.h")
 # headers beside rv3d.h that include IT and declare further entries of the same library (rv3d_render.h: the debug panels, csrc/render.hip)
 COMPANION_HEADERS = ("rv3d_render.h",)
+# another header of that kind, with a table of its own (`optim_prototypes()`): the grouped optimiser step of csrc/optim.hip
+OPTIM_HEADERS = ("rv3d_optim.h",)
 
 # flags (mirror include/rv3d.h)
 IN_AFFINE, IN_RELU, OUT_F32, OUT_BIAS, OUT_STATS, OUT_ACCUM, OUT_RELU = 1, 2, 4, 8, 16, 32, 64
@@ -38,6 +41,7 @@ SEL_SMALL_GRIDS, SEL_SMALL_GRIDS6, SEL_NO_GEN6, SEL_NO_GEN5, SEL_NO_POINTWISE, S
 SELECT = 0
 EW_RELU_A, EW_RELU_B, EW_RELU_OUT = 1, 2, 4
 BNB_RELU_Z, BNB_RES_ACCUM, BNB_Y_FROM_INPUT = 1, 2, 4
+ADAM_AMSGRAD, ADAM_MAXIMIZE = 1, 2  # RV_ADAM_* (rvAdamRow.flags, include/rv3d_optim.h)
 WNMS_MERGE_SUPPRESSED, WNMS_SCORE_KEEPER, WNMS_NMS_GE, WNMS_MERGE_GE = 1, 2, 4, 8  # RV_WNMS_* (rv_wnms_opt / rv_nms_sweeps_opt: per call)
 # rv_ew_pass_info: passes and kernel forms (RV_EW_PASS_* / RV_EW_FORM_*)
 EW_PASS_COMBINE, EW_PASS_MASK_GRAD, EW_PASS_BN_FINALIZE, EW_PASS_BWD_REDUCE, EW_PASS_BWD_REDUCE_PAIR, EW_PASS_BWD_FINALIZE, EW_PASS_BWD_APPLY, EW_PASS_BWD_APPLY_PAIR = range(8)
@@ -120,6 +124,12 @@ class RoiLayer(ctypes.Structure):
                 ("ty", ctypes.c_double)]
 
 
+class AdamRow(ctypes.Structure):
+    """``rvAdamRow`` of include/rv3d_optim.h: the hyper-parameters of one (parameter group, step count) of ``rv_adamw_step_groups``."""
+
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay")] + [("step", ctypes.c_int64), ("flags", ctypes.c_int32)]
+
+
 ML_MAX_LEVELS, ML_MAX_ENTRIES = 8, 16  # RV_ML_MAX_LEVELS / RV_ML_MAX_ENTRIES
 AFFINITY_GAUSSIAN, AFFINITY_BEV = 0, 1  # RV_AFFINITY_* (rv_soft_assign)
 CLS_VARIFOCAL, CLS_FOCAL, CLS_PENALTY_REDUCED = 0, 1, 2  # RV_CLS_* (rvLossKinds.cls_kind)
@@ -176,7 +186,7 @@ _SCALARS = {"int": ctypes.c_int32, "int32_t": ctypes.c_int32, "int64_t": ctypes.
 _POINTEES = ("void", "float", "double", "uint8_t", "int32_t", "int64_t", "uint64_t")  # T*, const T*, T* const*: all c_void_p
 _STRUCTS = {"rvTapGeom": ctypes.POINTER(TapGeom), "rvTapShape": ctypes.POINTER(TapShape), "rvBnbEpilogue": ctypes.POINTER(BnbEpilogue),
             "rvTargetLevel": ctypes.POINTER(TargetLevel), "rvTargetOut": ctypes.POINTER(TargetOut), "rvLossEntry": ctypes.POINTER(LossEntry),
-            "rvLossParams": ctypes.POINTER(LossParams), "rvLossKinds": ctypes.POINTER(LossKinds),
+            "rvLossParams": ctypes.POINTER(LossParams), "rvLossKinds": ctypes.POINTER(LossKinds), "rvAdamRow": ctypes.POINTER(AdamRow),
             # fed raw memory: converters/av2/roi.py builds the table as a numpy record array and keeps it in a device tensor
             "rvRoiLayer": ctypes.c_void_p}
 
@@ -242,8 +252,18 @@ def included_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], .
 def companion_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
     """The same table for ``COMPANION_HEADERS``: headers in include/ that include rv3d.h and declare further entries (``rv3d_render.h``).
     ``load()`` types them like the header's own; one that is missing is an error."""
+    return _companion_table(COMPANION_HEADERS)
+
+
+@functools.lru_cache(maxsize=None)
+def optim_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    """The same table for ``OPTIM_HEADERS`` (``rv3d_optim.h``: ``rv_adamw_step_groups``, ``rv_adam_max_rows``)."""
+    return _companion_table(OPTIM_HEADERS)
+
+
+def _companion_table(names) -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
     table = {}
-    for name in COMPANION_HEADERS:
+    for name in names:
         path = os.path.join(os.path.dirname(HEADER_PATH), name)
         if not os.path.exists(path):
             raise RvError(f"the companion header {path} is missing")
@@ -283,7 +303,7 @@ def _dlopen(path: str) -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     # restype / argtypes of every declared symbol; the parameter names make ctypes refuse extra arguments too (a bare cdecl
     # function pointer ignores them) and accept them as keywords
-    for name, (restype, params) in {**prototypes(), **included_prototypes(), **companion_prototypes()}.items():
+    for name, (restype, params) in {**prototypes(), **included_prototypes(), **companion_prototypes(), **optim_prototypes()}.items():
         try:
             fn = ctypes.CFUNCTYPE(restype, *[t for t, _ in params])((name, lib), tuple((1, p) for _, p in params))
         except AttributeError:

@@ -8,7 +8,11 @@
 //   p *= 1 - lr*wd;  m = m + (g - m)(1 - b1);  v = v*b2 + g*g*(1 - b2);
 //   p -= (lr / (1 - b1^t)) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
 // with g = grad * min(1, max_norm / (||grad||_2 + 1e-6)) (torch.nn.utils.clip_grad_norm_).
+//
+// rv_adamw_step_groups (include/rv3d_optim.h) is the same pair of launches for several parameter groups, per-parameter step
+// counts, amsgrad and maximize: the hyper-parameters become rows passed by value, each tensor names its row.
 #include "common.h"
+#include "../../include/rv3d_optim.h"
 
 namespace {
 
@@ -110,6 +114,114 @@ __global__ __launch_bounds__(256) void optim_adamw_kernel(const OptTensor* tenso
     for (int64_t i = done + threadIdx.x; i < n; i += 256) adam_elem(p[i], g[i], m[i], v[i], h, clip);
 }
 
+// ---- the same step for several parameter groups / step counts / amsgrad / maximize (rv_adamw_step_groups, rv3d_optim.h) ----
+constexpr int kMaxRows = 64;  // rows of hyper-parameters by value in the kernel arguments: 64 x 32 B = 2 KB of the 4 KB there are
+
+struct OptRow {  // OptHyper of one (group, step count), without max_norm (one for all rows) and with the row's RV_ADAM_* flags
+    float decay, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps;
+    int32_t flags;
+};
+struct OptRows {
+    OptRow r[kMaxRows];
+};
+
+// adam_elem with amsgrad: vmax = max(vmax, v) (_foreach_maximum_), and the denominator takes sqrt(vmax)
+__device__ __forceinline__ void adam_elem_amsgrad(float& p, const float g, float& m, float& v, float& vmax, const OptHyper& h, const float clip) {
+    const float gc = g * clip;
+    p *= h.decay;
+    m = m + (gc - m) * h.one_minus_beta1;
+    v = v * h.beta2 + gc * gc * h.one_minus_beta2;
+    vmax = (vmax != vmax || vmax > v) ? vmax : v;  // at::maximum: a NaN on either side is kept
+    const float denom = sqrtf(vmax) / h.bc2_sqrt + h.eps;
+    p -= h.step_size * (m / denom);
+}
+
+__global__ __launch_bounds__(256) void optim_adamw_groups_kernel(const OptTensor* tensors, const int32_t* tensor_row, float* const* vmax,
+                                                                 const OptChunk* chunks, const float* partial, int n_partial,
+                                                                 const float max_norm, const int n_rows, float* total_norm_out,
+                                                                 const OptRows rows) {
+    // the total and the clip coefficient as optim_adamw_kernel forms them (same order, same operations)
+    __shared__ double red[4];
+    __shared__ float clip_s;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n_partial; i += 256) s += (double)partial[i];
+    s = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const float norm = (float)sqrt((red[0] + red[1]) + (red[2] + red[3]));
+        float clip = 1.f;
+        if (max_norm > 0.f) {
+            clip = max_norm / (norm + 1e-6f);
+            clip = clip < 1.f ? clip : 1.f;
+        }
+        clip_s = clip;
+        if (blockIdx.x == 0 && total_norm_out) total_norm_out[0] = norm;
+    }
+    __syncthreads();
+    const OptChunk c = chunks[blockIdx.x];
+    const OptTensor t = tensors[c.tensor];
+    const int32_t ri = tensor_row[c.tensor];
+    if (ri < 0 || ri >= n_rows) return;  // (uniform; the host checks the column: never index the by-value array outside it)
+    const OptRow r = rows.r[ri];
+    OptHyper h;
+    h.decay = r.decay;
+    h.one_minus_beta1 = r.one_minus_beta1;
+    h.beta2 = r.beta2;
+    h.one_minus_beta2 = r.one_minus_beta2;
+    h.step_size = r.step_size;
+    h.bc2_sqrt = r.bc2_sqrt;
+    h.eps = r.eps;
+    h.max_norm = max_norm;
+    // maximize: g = -g before anything else; (-g) * clip == g * (-clip) exactly, so the sign rides on the coefficient
+    const float clip = (r.flags & RV_ADAM_MAXIMIZE) ? -clip_s : clip_s;
+    const int64_t lo = (int64_t)c.chunk * kChunk, hi = lo + kChunk < t.n ? lo + kChunk : t.n;
+    const int64_t n = hi - lo;
+    float* p = t.p + lo;
+    const float* g = t.g + lo;
+    float* m = t.m + lo;
+    float* v = t.v + lo;
+    int64_t done = 0;
+    if (r.flags & RV_ADAM_AMSGRAD) {
+        float* x = vmax ? vmax[c.tensor] : nullptr;
+        if (x == nullptr) return;  // (uniform; the entry point refuses amsgrad rows without the table)
+        x += lo;
+        if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)x)) & 15) == 0) {
+            const int64_t n4 = n >> 2;
+            for (int64_t i = threadIdx.x; i < n4; i += 256) {
+                const f32x4 p4 = ((f32x4*)p)[i], m4 = ((f32x4*)m)[i], v4 = ((f32x4*)v)[i], x4 = ((f32x4*)x)[i], g4 = ((const f32x4*)g)[i];
+                float pp[4] = {p4[0], p4[1], p4[2], p4[3]}, mm[4] = {m4[0], m4[1], m4[2], m4[3]}, vv[4] = {v4[0], v4[1], v4[2], v4[3]};
+                float xx[4] = {x4[0], x4[1], x4[2], x4[3]};
+                const float gg[4] = {g4[0], g4[1], g4[2], g4[3]};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) adam_elem_amsgrad(pp[j], gg[j], mm[j], vv[j], xx[j], h, clip);
+                ((f32x4*)p)[i] = f32x4{pp[0], pp[1], pp[2], pp[3]};
+                ((f32x4*)m)[i] = f32x4{mm[0], mm[1], mm[2], mm[3]};
+                ((f32x4*)v)[i] = f32x4{vv[0], vv[1], vv[2], vv[3]};
+                ((f32x4*)x)[i] = f32x4{xx[0], xx[1], xx[2], xx[3]};
+            }
+            done = n4 << 2;
+        }
+        for (int64_t i = done + threadIdx.x; i < n; i += 256) adam_elem_amsgrad(p[i], g[i], m[i], v[i], x[i], h, clip);
+        return;
+    }
+    if (((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) == 0) {
+        const int64_t n4 = n >> 2;
+        for (int64_t i = threadIdx.x; i < n4; i += 256) {
+            const f32x4 p4 = ((f32x4*)p)[i], m4 = ((f32x4*)m)[i], v4 = ((f32x4*)v)[i], g4 = ((const f32x4*)g)[i];
+            float pp[4] = {p4[0], p4[1], p4[2], p4[3]}, mm[4] = {m4[0], m4[1], m4[2], m4[3]}, vv[4] = {v4[0], v4[1], v4[2], v4[3]};
+            const float gg[4] = {g4[0], g4[1], g4[2], g4[3]};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) adam_elem(pp[j], gg[j], mm[j], vv[j], h, clip);
+            ((f32x4*)p)[i] = f32x4{pp[0], pp[1], pp[2], pp[3]};
+            ((f32x4*)m)[i] = f32x4{mm[0], mm[1], mm[2], mm[3]};
+            ((f32x4*)v)[i] = f32x4{vv[0], vv[1], vv[2], vv[3]};
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + threadIdx.x; i < n; i += 256) adam_elem(p[i], g[i], m[i], v[i], h, clip);
+}
+
 }  // namespace
 
 extern "C" int32_t rv_optim_chunk_elems(void) { return kChunk; }
@@ -134,5 +246,40 @@ extern "C" int rv_adamw_step(const void* tensors, const void* chunks, int32_t n_
     hipLaunchKernelGGL(optim_adamw_kernel, dim3(n_chunks), dim3(256), 0, st, (const OptTensor*)tensors, (const OptChunk*)chunks, partial,
                        n_chunks, h, total_norm);
     RV_CHECK_LAUNCH("optim_adamw_kernel");
+    return 0;
+}
+
+extern "C" int32_t rv_adam_max_rows(void) { return kMaxRows; }
+
+extern "C" int rv_adamw_step_groups(const void* tensors, const int32_t* tensor_row, const void* vmax, const void* chunks, int32_t n_chunks,
+                                    float* partial, const rvAdamRow* rows, int32_t n_rows, double max_norm, float* total_norm,
+                                    rvStream stream) {
+    RV_REQUIRE(tensors && tensor_row && chunks && partial && rows && n_chunks > 0, "rv_adamw_step_groups: null argument");
+    RV_REQUIRE(n_rows >= 1 && n_rows <= kMaxRows, "rv_adamw_step_groups: n_rows = %d, outside 1 .. rv_adam_max_rows() = %d", (int)n_rows, kMaxRows);
+    static_assert(sizeof(OptRows) + 64 <= 3072, "the kernel arguments must stay well under 4 KB");
+    OptRows k;
+    memset(&k, 0, sizeof k);
+    for (int i = 0; i < n_rows; ++i) {
+        const rvAdamRow& a = rows[i];
+        RV_REQUIRE(a.step >= 1 && a.beta1 >= 0.0 && a.beta1 < 1.0 && a.beta2 >= 0.0 && a.beta2 < 1.0,
+                   "rv_adamw_step_groups: bad hyper-parameters in row %d", i);
+        RV_REQUIRE((a.flags & ~(RV_ADAM_AMSGRAD | RV_ADAM_MAXIMIZE)) == 0, "rv_adamw_step_groups: unknown flags %d in row %d", (int)a.flags, i);
+        RV_REQUIRE(!(a.flags & RV_ADAM_AMSGRAD) || vmax, "rv_adamw_step_groups: row %d has RV_ADAM_AMSGRAD and vmax is null", i);
+        const double bc1 = 1.0 - pow(a.beta1, (double)a.step), bc2 = 1.0 - pow(a.beta2, (double)a.step);
+        OptRow& r = k.r[i];
+        r.decay = (float)(1.0 - a.lr * a.weight_decay);
+        r.one_minus_beta1 = (float)(1.0 - a.beta1);
+        r.beta2 = (float)a.beta2;
+        r.one_minus_beta2 = (float)(1.0 - a.beta2);
+        r.step_size = (float)(a.lr / bc1);
+        r.bc2_sqrt = (float)sqrt(bc2);
+        r.eps = (float)a.eps;
+        r.flags = a.flags;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(optim_sqnorm_kernel, dim3(n_chunks), dim3(256), 0, st, (const OptTensor*)tensors, (const OptChunk*)chunks, partial);
+    hipLaunchKernelGGL(optim_adamw_groups_kernel, dim3(n_chunks), dim3(256), 0, st, (const OptTensor*)tensors, tensor_row,
+                       (float* const*)vmax, (const OptChunk*)chunks, partial, n_chunks, (float)max_norm, n_rows, total_norm, k);
+    RV_CHECK_LAUNCH("optim_adamw_groups_kernel");
     return 0;
 }
