@@ -407,6 +407,8 @@ def test_rotated_iou_matches_oracle():
     out = torch.empty((200, 200), dtype=torch.float32, device=DEV)
     L.call("rv_rotated_iou", L.ptr(rd), 200, L.ptr(rd), 200, L.ptr(out), L.stream_ptr())
     assert np.array_equal(out.cpu().numpy(), ref)
+    # (boxes within 12 m of the origin: these two bounds do not hold at range.  How accurate the shared arithmetic is, at 0 .. 200 m and
+    # on degenerate pairs, is tests/test_gpu_iou_geometry.py against the float64 reference of tests/iou_ref.py)
     assert abs(float(out.diagonal().min()) - 1.0) < 1e-5 and float(out.max()) <= 1.0 + 1e-6
 
 
