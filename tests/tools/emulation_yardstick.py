@@ -5,6 +5,7 @@ script and recorded in tests/test_gpu_fullsize_train.py (``EMULATION``).  CPU on
 
     python tests/tools/emulation_yardstick.py [rv-av2|rv-waymo|base-av2|base-waymo|first-step]
     python tests/tools/emulation_yardstick.py envelope [case key ...]   # rewrites tests/golden/emulation_envelope.json (given keys: only those cases)
+    python tests/tools/emulation_yardstick.py two-rank [case key ...]   # rewrites tests/golden/two_rank_yardstick.json (see ``two_rank``)
 
 ``envelope`` (round-5 review, item 9): the crop cases of tests/test_gpu_realwidth.py under EIGHT summation orders of the CPU bf16
 emulation (``Numerics.bf16(sum_order=k)``: every conv visits its input channels in a permuted order -- the same network, another
@@ -115,7 +116,33 @@ def envelope_case(widths, n_feat, n_cls, W, shift):
             "q05_min": min(r["q05"] for r in rows), "q05_max": max(r["q05"] for r in rows)}
 
 
+def two_rank(wanted):
+    """tests/golden/two_rank_yardstick.json: the CPU side of tests/test_gpu_two_rank.py (cases, functional and arithmetic in
+    tests/two_rank.py) -- per case the fp32 oracle's functional value, the bf16 emulation's per-parameter gradient cosine and
+    |log norm ratio| against fp32 under four summation orders, its running statistics' distance from fp32, and the local-BatchNorm
+    control (the oracle per rank slice, gradients summed): what a rank-local SyncBN would score."""
+    import two_rank as tr
+
+    out = {}
+    if wanted and os.path.exists(tr.YARDSTICK):
+        out = tr.load_yardstick()["cases"]
+    for name, spec in tr.CASES.items():
+        for shift in spec[6]:
+            key = tr.case_key(name, shift)
+            if wanted and key not in wanted:
+                continue
+            print(key, flush=True)
+            out[key] = tr.record_case(name, shift)
+    with open(tr.YARDSTICK, "w") as f:
+        json.dump({"threads": torch.get_num_threads(), "torch": torch.__version__, "sum_orders": list(tr.SUM_ORDERS), "cases": out}, f, indent=1)
+        f.write("\n")
+    print("wrote", tr.YARDSTICK)
+
+
 if __name__ == "__main__":
+    if sys.argv[1:2] == ["two-rank"]:
+        two_rank(sys.argv[2:])
+        sys.exit(0)
     if sys.argv[1:2] == ["envelope"]:
         path = os.path.join(ROOT, "tests", "golden", "emulation_envelope.json")
         wanted = sys.argv[2:]  # case keys to (re-)record; the other cases keep their recorded values
