@@ -783,13 +783,19 @@ class TapLayer:
         return self._bias_pad[1]
 
     def invalidate(self) -> None:
-        """Drop the packed bf16 images.  They are re-packed automatically when ``weight._version`` or its storage changes
+        """Drop every cached image of this layer (packed weights of both operand types, folded forms, eval-mode BatchNorm folds,
+        padded bias).  They are re-made automatically when ``weight._version`` or its storage changes
         (optimizer steps, ``load_state_dict``, ``copy_``); writes that bypass the version counter (``p.data.add_(...)``,
         weight-averaging swaps through ``.data``) do not show there -- call this (or ``engine.invalidate_packed_weights``)
         after such surgery."""
         self._packed.clear()
         self._version = None
         self._fold_version = None
+        # every other image made from the parameters: the fp16 folded image, the eval-mode BatchNorm folds (weight image + bias)
+        # and the padded bias are keyed on the same version counters, which such writes do not move either
+        self.__dict__.pop("_fold_f16", None)
+        self.__dict__.pop("_eval_fold", None)
+        self._bias_pad = None
 
     def packed(self, form: str) -> Tensor:
         """bf16 weight image for ``form``; re-packed when the parameter changed (optimizer step / load_state_dict)."""
@@ -844,6 +850,7 @@ class Tape:
         self.chained_wgrad = None  # (RV3D_OVERLAP=chain) event behind the last big weight gradient on the side stream
         self.held_wgrads: List = []  # weight-gradient launches held back for a SyncBN all-reduce (engine_bwd._release_held_wgrads)
         self.bn_counters: List[Tensor] = []
+        self.bn_written: List[Tensor] = []  # running statistics a kernel updated in place (Tensor._version has not moved yet)
 
     # ---- gradient buffers (views follow their parents) ----
     def grad_buffer(self, a: Act) -> Tuple[Act, bool]:
@@ -1094,6 +1101,8 @@ class BnOp(Op):
             if bn.running_mean.shape[0] != cp:  # padded copies: write the logical channels back
                 bn.running_mean.copy_(rm[:c])
                 bn.running_var.copy_(rv[:c])
+            else:  # the kernel wrote the module's own tensors through raw pointers: autograd is told at the end of the forward pass
+                t.bn_written += (bn.running_mean, bn.running_var)
             t.bn_counters.append(bn.num_batches_tracked)  # incremented together at the end of the forward pass
             conv.partial = None
             self.state = BnState(bn, scale, shift, mean, invstd, conv.count)
@@ -1170,6 +1179,8 @@ class SmallKOp(Op):
             if bn.running_mean.shape[0] != cp:
                 bn.running_mean.copy_(rm[:c])
                 bn.running_var.copy_(rv[:c])
+            else:
+                t.bn_written += (bn.running_mean, bn.running_var)
             t.bn_counters.append(bn.num_batches_tracked)
         else:
             L.call("rv_bn_fold_eval", cp, L.ptr(self.gamma_p), L.ptr(self.beta_p), L.ptr(rm), L.ptr(rv), bn.eps,

@@ -301,6 +301,11 @@ class _ProgramFn(torch.autograd.Function):
         if tape.bn_counters:
             torch._foreach_add_(tape.bn_counters, 1)  # num_batches_tracked of every BatchNorm on the tape, one launch
             tape.bn_counters = []
+        if tape.bn_written:
+            # rv_bn_finalize / rv_smallk_forward updated these running statistics through raw pointers: tell autograd, and with it
+            # everything keyed on Tensor._version (the eval-mode fold of engine.TapLayer.packed_eval).  Host bookkeeping, no launch.
+            torch.autograd.graph.increment_version(tape.bn_written)
+            tape.bn_written = []
         # an output nobody differentiates (the backbone's stride-2/4/16 maps when the head reads stride 1 only) gets NO gradient
         # instead of a materialised zero tensor, which would be converted, copied and then accumulated into by every real writer
         ctx.set_materialize_grads(_MATERIALIZE_GRADS)

@@ -682,3 +682,39 @@ def test_pointwise_kernel_counts_its_wait_over_the_order_it_was_written_in(tmp_p
     mem = [ln.split()[0] for ln in body[:waits[0]] if ln.startswith(VMEM)]
     assert mem[-16:] == ["global_load_lds_dwordx4"] * 8 + ["global_store_dwordx4"] * 8, mem[-20:]
     _assert_no_spills(co, "pointwise_kernelILi256E")
+
+
+def test_raw_pointer_writes_move_no_version_and_increment_version_does():
+    """The premise of the running-statistics bookkeeping (program._ProgramFn.forward): a kernel that writes a tensor through its raw pointer
+    leaves ``Tensor._version`` where it was -- so a cache keyed on it (``TapLayer.packed_eval``) would serve the old fold -- and
+    ``torch.autograd.graph.increment_version``, the signal the program sends for the running statistics a tape wrote in place, moves it
+    without touching the data; ``_foreach_add_`` (the ``num_batches_tracked`` update next to it) moves the versions of its own operands only."""
+    rm, rv, count = torch.zeros(32), torch.ones(32), torch.tensor(0)
+    before = (rm._version, rv._version, count._version)
+    src = (ctypes.c_float * 32)(*range(32))
+    ctypes.memmove(rm.data_ptr(), src, ctypes.sizeof(src))
+    assert rm[5] == 5.0 and (rm._version, rv._version, count._version) == before
+    torch._foreach_add_([count], 1)
+    assert count._version == before[2] + 1 and (rm._version, rv._version) == before[:2]
+    torch.autograd.graph.increment_version([rm, rv])
+    assert (rm._version, rv._version) == (before[0] + 1, before[1] + 1)
+    assert rm[5] == 5.0 and torch.equal(rv, torch.ones(32))
+
+
+def test_tap_layer_invalidate_drops_every_cached_image():
+    """``TapLayer.invalidate`` (after writes through ``.data``, which move no version): no image made from the old tensors stays behind."""
+    from range_view_3d_detection_amd import engine as E
+
+    conv = torch.nn.Conv2d(32, 32, 3, stride=(1, 2), bias=True)
+    l = E.tap_layer(conv)
+    ver = (conv.weight._version, conv.weight.data_ptr())
+    l._packed.update({"gather": torch.zeros(1), "gather:f16": torch.zeros(1)})
+    l._version = l._fold_version = ver
+    l.__dict__["_fold_f16"] = (ver, torch.zeros(1))
+    l.__dict__["_eval_fold"] = {("gather", "bf16"): (None, torch.zeros(1), torch.zeros(1))}
+    assert torch.equal(l.padded_bias()[:32], conv.bias.detach()) and l._bias_pad is not None
+    l.invalidate()
+    assert not l._packed and l._version is None and l._fold_version is None and l._bias_pad is None
+    assert "_fold_f16" not in l.__dict__ and "_eval_fold" not in l.__dict__
+    conv.bias.data.add_(1.0)
+    assert torch.equal(l.padded_bias()[:32], conv.bias.detach())
