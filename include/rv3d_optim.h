@@ -50,6 +50,38 @@ int32_t rv_adam_max_rows(void);
 int rv_adamw_step_groups(const void* tensors, const int32_t* tensor_row, const void* vmax, const void* chunks, int32_t n_chunks,
                          float* partial, const rvAdamRow* rows, int32_t n_rows, double max_norm, float* total_norm, rvStream stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Weight averaging -- torch.optim.swa_utils.AveragedModel: the exponential moving average (get_ema_multi_avg_fn) or the equal average
+ * (get_swa_multi_avg_fn) of the weights, both one torch._foreach_lerp_(averaged, current, weight) per update -- inside the optimiser's
+ * second launch, where every updated parameter is in registers, and as one launch for the tensors the optimiser did not step.
+ *
+ * rv_adamw_step_groups_avg is rv_adamw_step_groups plus two arguments.  avg: n_tensors DEVICE pointers on the device, the averaged
+ * twin of each tensor (fp32, as many elements as the parameter), NULL for a tensor that is not averaged (the idea of `vmax`); the
+ * argument itself is required.  avg_weight: ONE weight for all tensors, in [0, 1], rounded to fp32 once on the host (w).
+ * Launch 1 is unchanged.  Launch 2 does, after the Adam update of an element and with the new p still in registers,
+ *   a = w < 0.5 ? a + w (p - a) : p - (p - a)(1 - w)           (at::lerp's expression, in fp32; w == 1 stores p exactly)
+ * The parameters and moments come out bit for bit as from rv_adamw_step_groups on the same inputs (the same element functions); the
+ * amsgrad / maximize / clipping / row semantics are its own.  The 16-byte path of a chunk needs `a` aligned like p, g, m and v; a chunk
+ * with a misaligned `a` takes the scalar path.  Added traffic: 8 B per averaged element (a read and written once), nothing else.
+ * Returns non-zero before anything is launched for what rv_adamw_step_groups refuses, a NULL avg, or avg_weight outside [0, 1] (NaN
+ * included).
+ * Replaces AveragedModel.update_parameters' foreach lerp over the stepped parameters (12 B per element: a, p in, a out) behind the step.
+ *
+ * rv_average_tensors is the same expression as ONE multi-tensor launch over fp32 tensors the step did not cover: parameters without a
+ * gradient, BatchNorm's running_mean / running_var under use_buffers=True, and -- avg_weight = 1 -- the plain copy of the buffers under
+ * use_buffers=False.  table: n_tensors rows (avg, src, n) on the DEVICE: two device pointers and an int64 element count (24 B).
+ * chunks: n_chunks int32 pairs (tensor, chunk) on the device, chunk = a run of rv_optim_chunk_elems() elements, as rv_adamw_step's;
+ * one workgroup per chunk.  avg and src of a row may be the same address or disjoint, nothing in between.
+ * Returns non-zero before anything is launched for a NULL table or chunks, n_chunks <= 0, or avg_weight outside [0, 1].  The rows are
+ * on the device, so the host cannot read them: a row with a NULL pointer, or a chunk that starts at or beyond the row's n, is left
+ * untouched by the kernel; the caller checks the table when it builds it.
+ * Replaces one foreach lerp (or one copy_ per buffer: ~234 launches on the 78 BatchNorm layers of the rv-av2 model) per update.
+ * ------------------------------------------------------------------------------------- */
+int rv_adamw_step_groups_avg(const void* tensors, const int32_t* tensor_row, const void* vmax, const void* avg, double avg_weight,
+                             const void* chunks, int32_t n_chunks, float* partial, const rvAdamRow* rows, int32_t n_rows, double max_norm,
+                             float* total_norm, rvStream stream);
+int rv_average_tensors(const void* table, const void* chunks, int32_t n_chunks, double avg_weight, rvStream stream);
+
 #ifdef __cplusplus
 }
 #endif

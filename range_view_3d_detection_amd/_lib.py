@@ -3,7 +3,8 @@
 ``include/rv3d.h`` is the single source of the binding's types: ``prototypes()`` parses the declarations in its own text once per
 process, ``included_prototypes()`` those of the headers it includes (``rv3d_wnms.h``), ``companion_prototypes()`` those of the headers
 beside it that include it (``rv3d_render.h``), ``optim_prototypes()`` those of ``rv3d_optim.h`` (another such header: the grouped optimiser
-step), and ``load()`` sets ``restype`` / ``argtypes`` of every symbol of the four tables.  Call sites pass plain Python values (``int``,
+step) and ``average_prototypes()`` the weight-averaging entries of that header, and ``load()`` sets ``restype`` / ``argtypes`` of every
+symbol of the five tables.  Call sites pass plain Python values (``int``,
 ``float``, ``None``, ``ptr(t)``, a ctypes Structure or array); a wrong argument count or a wrong struct raises in Python.
 
 There is deliberately no CPU fallback: if the library is missing or a call fails the host
@@ -30,6 +31,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "rv3d.h")
 COMPANION_HEADERS = ("rv3d_render.h",)
 # another header of that kind, with a table of its own (`optim_prototypes()`): the grouped optimiser step of csrc/optim.hip
 OPTIM_HEADERS = ("rv3d_optim.h",)
+# the weight-averaging entries of that header, a table of their own (`average_prototypes()`): `optim_prototypes()` stays the grouped step
+AVERAGE_ENTRIES = ("rv_adamw_step_groups_avg", "rv_average_tensors")
 
 # flags (mirror include/rv3d.h)
 IN_AFFINE, IN_RELU, OUT_F32, OUT_BIAS, OUT_STATS, OUT_ACCUM, OUT_RELU = 1, 2, 4, 8, 16, 32, 64
@@ -258,7 +261,18 @@ def companion_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], 
 @functools.lru_cache(maxsize=None)
 def optim_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
     """The same table for ``OPTIM_HEADERS`` (``rv3d_optim.h``: ``rv_adamw_step_groups``, ``rv_adam_max_rows``)."""
-    return _companion_table(OPTIM_HEADERS)
+    return {k: v for k, v in _companion_table(OPTIM_HEADERS).items() if k not in AVERAGE_ENTRIES}
+
+
+@functools.lru_cache(maxsize=None)
+def average_prototypes() -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
+    """The same table for ``AVERAGE_ENTRIES``, declared in ``rv3d_optim.h`` too: the optimiser step that also averages the weights and the
+    multi-tensor average (``optim.AveragedModel``).  An entry the header does not declare is an error."""
+    table = _companion_table(OPTIM_HEADERS)
+    missing = [k for k in AVERAGE_ENTRIES if k not in table]
+    if missing:
+        raise RvError(f"include/rv3d_optim.h does not declare {missing}")
+    return {k: table[k] for k in AVERAGE_ENTRIES}
 
 
 def _companion_table(names) -> Dict[str, Tuple[object, Tuple[Tuple[object, str], ...]]]:
@@ -303,7 +317,7 @@ def _dlopen(path: str) -> ctypes.CDLL:
     lib = ctypes.CDLL(path)
     # restype / argtypes of every declared symbol; the parameter names make ctypes refuse extra arguments too (a bare cdecl
     # function pointer ignores them) and accept them as keywords
-    for name, (restype, params) in {**prototypes(), **included_prototypes(), **companion_prototypes(), **optim_prototypes()}.items():
+    for name, (restype, params) in {**prototypes(), **included_prototypes(), **companion_prototypes(), **optim_prototypes(), **average_prototypes()}.items():
         try:
             fn = ctypes.CFUNCTYPE(restype, *[t for t, _ in params])((name, lib), tuple((1, p) for _, p in params))
         except AttributeError:

@@ -851,6 +851,7 @@ class Tape:
         self.held_wgrads: List = []  # weight-gradient launches held back for a SyncBN all-reduce (engine_bwd._release_held_wgrads)
         self.bn_counters: List[Tensor] = []
         self.bn_written: List[Tensor] = []  # running statistics a kernel updated in place (Tensor._version has not moved yet)
+        self.cma_counts: Optional[Dict[int, int]] = None  # num_batches_tracked of the BatchNorms without a momentum (bn_momentum)
 
     # ---- gradient buffers (views follow their parents) ----
     def grad_buffer(self, a: Act) -> Tuple[Act, bool]:
@@ -1096,7 +1097,7 @@ class BnOp(Op):
                 conv.partial = reduced if reduced is not None else allreduce_partial_rows(conv.partial, conv.rows, conv.count)
                 conv.rows, count_arg = 1, -1
             L.call("rv_bn_finalize", L.ptr(conv.partial), conv.rows, cp, count_arg, L.ptr(gamma),
-                   L.ptr(beta), bn.eps, bn.momentum if bn.momentum is not None else 0.1, L.ptr(rm),
+                   L.ptr(beta), bn.eps, bn_momentum(t, bn), L.ptr(rm),
                    L.ptr(rv), L.ptr(scale), L.ptr(shift), L.ptr(mean), L.ptr(invstd), L.stream_ptr())
             if bn.running_mean.shape[0] != cp:  # padded copies: write the logical channels back
                 bn.running_mean.copy_(rm[:c])
@@ -1119,6 +1120,26 @@ class BnOp(Op):
         from . import engine_bwd
 
         engine_bwd.bn_backward(self, t)
+
+
+RUN_MODULE: Optional[nn.Module] = None  # the module whose program is being built (set by program.run around the build)
+
+
+def bn_momentum(t: Tape, bn: nn.BatchNorm2d) -> float:
+    """The factor of the running-statistics update of this train-mode forward, as ``torch.nn.BatchNorm2d.forward`` chooses it:
+    ``bn.momentum``, or -- ``momentum=None``, the cumulative average ``torch.optim.swa_utils.update_bn`` asks for --
+    ``1 / (num_batches_tracked + 1)``.  The kernels take the factor by value, so the second form needs the counters on the host: ONE
+    read per program build for all BatchNorms of the module being built that have no momentum (kept on the tape), none otherwise."""
+    if bn.momentum is not None:
+        return bn.momentum
+    if t.cma_counts is None:
+        own = [m for m in (RUN_MODULE.modules() if RUN_MODULE is not None else ())
+               if isinstance(m, nn.modules.batchnorm._BatchNorm) and m.momentum is None and m.num_batches_tracked is not None]
+        counts = torch.stack([m.num_batches_tracked for m in own]).tolist() if own else []
+        t.cma_counts = {id(m): int(c) for m, c in zip(own, counts)}
+    if id(bn) not in t.cma_counts:  # (a BatchNorm outside the module being built: its own read)
+        t.cma_counts[id(bn)] = int(bn.num_batches_tracked)
+    return 1.0 / (t.cma_counts[id(bn)] + 1)
 
 
 def _padded(p: Tensor, cp: int, fill: float = 0.0) -> Tensor:
@@ -1174,7 +1195,7 @@ class SmallKOp(Op):
                 self.count = -1
             L.call("rv_smallk_forward", x.ptr(), x.ld, x.pixels, cin, L.ptr(wp), pad32(cin), cp,
                    L.ptr(moments), self.count, L.ptr(self.gamma_p), L.ptr(self.beta_p), bn.eps,
-                   bn.momentum if bn.momentum is not None else 0.1, L.ptr(rm), L.ptr(rv), L.ptr(scale), L.ptr(shift),
+                   bn_momentum(t, bn), L.ptr(rm), L.ptr(rv), L.ptr(scale), L.ptr(shift),
                    L.ptr(self.mean), L.ptr(self.invstd), 1, self.out.ptr() if apply else None, self.out.ld, L.stream_ptr())
             if bn.running_mean.shape[0] != cp:
                 bn.running_mean.copy_(rm[:c])

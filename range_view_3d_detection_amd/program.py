@@ -348,7 +348,11 @@ class _ProgramFn(torch.autograd.Function):
 
 def run(build: Callable, module: nn.Module, inputs: Sequence[Tensor]) -> Tuple[Tensor, ...]:
     params = [p for p in module.parameters()]
-    return _ProgramFn.apply(build, module.training, len(inputs), *inputs, *params)
+    outer, E.RUN_MODULE = E.RUN_MODULE, module  # (read only by engine.bn_momentum, for BatchNorms with momentum=None)
+    try:
+        return _ProgramFn.apply(build, module.training, len(inputs), *inputs, *params)
+    finally:
+        E.RUN_MODULE = outer
 
 
 def standalone(m: nn.Module, *inputs: Tensor):
