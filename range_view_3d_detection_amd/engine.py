@@ -21,6 +21,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
+from .images import Image, ImageCache
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -603,11 +604,17 @@ def _materialize_operand(x, layer, src, wu: int, wv: int, out, out_f32: bool, ev
 # conv layers: geometry + packed weights
 # ---------------------------------------------------------------------------------------------
 _LAYERS: "weakref.WeakSet[TapLayer]" = weakref.WeakSet()
-_PACK_TABLES: Dict[tuple, Tensor] = {}
+_PACK_TABLES: Dict[tuple, Tensor] = {}  # the one live device table of rv_pack_batch, keyed by the layers and buffers it names
 BATCH_PACK = True
 # Strided layers (stride-2 convs, the ConvTranspose2d up-samplers): run their strided gather and their weight gradient on the
 # stride-1 FOLDED view (fine tensor read as (N, H, W/s, s*C)) so that the LDS-DMA kernels take them.
 FOLD_STRIDED = True
+FORMS = ("gather", "scatter")
+
+
+def image_slot(form: Optional[str], kind: Optional[str] = None) -> tuple:
+    """Cache slot (kind, form, operand tag) of an image in the current operand type; kind: weight / folded / eval_fold / bias."""
+    return (kind or ("folded" if form == "folded" else "weight"), form, L.operand_tag())
 
 
 def prepack_stale() -> None:
@@ -615,47 +622,35 @@ def prepack_stale() -> None:
     launch (``rv_pack_batch``) instead of one ``rv_pack_weight`` launch per layer when the layer is next used (~160 launches
     per training step on the rv-* models).  Called at the start of a training-mode program; layers seen for the first time,
     layers with a permuted weight (``in_perm``) and non-fp32 parameters stay on the lazy per-layer path.  Both images of a
-    layer are written (a layer whose input needs no gradient never reads its scatter image: a few small ones)."""
-    if not BATCH_PACK:  # (no grad-mode test here: inside an autograd.Function's forward grad mode is off)
-        return
-    stale = []
-    for l in _LAYERS:
+    layer are written (a layer whose input needs no gradient never reads its scatter image: a few small ones), and the folded one
+    if it has been used, as persistent cache entries: the same buffers every step, so the table is built once per set of layers."""
+    def is_stale(l: "TapLayer") -> bool:  # packed before, and not since the parameter changed
+        held = [e.current for e in l.images.entries() if e.slot[0] == "weight"]
         w = l.weight
-        if (l._version is None or l.in_perm is not None or not w.requires_grad or not w.is_cuda or w.dtype != torch.float32
-                or not w.is_contiguous() or not l._packed):
-            continue
-        if (w._version, w.data_ptr()) != l._version:
-            stale.append(l)
+        return bool(held) and not any(held) and l.in_perm is None and w.requires_grad and w.is_cuda and w.dtype == torch.float32 and w.is_contiguous()
+
+    stale = sorted(filter(is_stale, _LAYERS), key=id) if BATCH_PACK else []  # (no grad-mode test: inside an autograd.Function's forward it is off)
     if len(stale) < 2:
         return
-    stale.sort(key=id)
-    dev = stale[0].weight.device
-    for l in stale:
-        if not l._images:
-            n = L.load().rv_packed_weight_bytes(l.geom) // 2
-            l._images = {f: torch.empty(n, dtype=torch.bfloat16, device=dev) for f in ("gather", "scatter")}
-    folded = [l for l in stale if l._fold_image is not None]  # (layers whose folded image has been used at least once)
-    key = tuple((id(l), l.weight.data_ptr(), l._images["gather"].data_ptr(), l._images["scatter"].data_ptr(),
-                 l._fold_image.data_ptr() if l._fold_image is not None else 0) for l in stale)
-    n_entries = 2 * len(stale) + len(folded)
-    table = _PACK_TABLES.get(key)
-    if table is None:
-        eb = L.load().rv_pack_batch_entry_bytes()
-        host = (ctypes.c_uint8 * (eb * n_entries))()
-        for i, l in enumerate(stale):
-            L.call("rv_pack_batch_fill", l.geom, L.ptr(l.weight), L.ptr(l._images["gather"]), L.ptr(l._images["scatter"]),
-                   ctypes.byref(host, 2 * eb * i))
-        for i, l in enumerate(folded):
-            L.call("rv_pack_batch_fill_folded", l.geom, L.ptr(l.weight), L.ptr(l._fold_image), ctypes.byref(host, eb * (2 * len(stale) + i)))
-        _PACK_TABLES.clear()  # one live table (a second model in the process rebuilds it: cheap)
-        table = torch.frombuffer(host, dtype=torch.uint8).clone().to(dev)
-        _PACK_TABLES[key] = table
-    L.call("rv_pack_batch", L.ptr(table), n_entries, L.stream_ptr())
-    for l in stale:
-        l._packed = dict(l._images)
-        l._version = (l.weight._version, l.weight.data_ptr())
-    for l in folded:
-        l._fold_version = l._version
+    with L.operand("bf16"):
+        imgs = {l: {f: l.image_buffer(f) for f in (*FORMS, "folded") if f != "folded" or l.images.held(image_slot(f))} for l in stale}
+        folded = [l for l in stale if "folded" in imgs[l]]
+        key = tuple((id(l), l.weight.data_ptr(), *(img.data_ptr() for img in imgs[l].values())) for l in stale)
+        n_entries = 2 * len(stale) + len(folded)
+        table = _PACK_TABLES.get(key)
+        if table is None:
+            eb = L.load().rv_pack_batch_entry_bytes()
+            host = (ctypes.c_uint8 * (eb * n_entries))()
+            for i, l in enumerate(stale):
+                L.call("rv_pack_batch_fill", l.geom, L.ptr(l.weight), L.ptr(imgs[l]["gather"]), L.ptr(imgs[l]["scatter"]), ctypes.byref(host, 2 * eb * i))
+            for i, l in enumerate(folded):
+                L.call("rv_pack_batch_fill_folded", l.geom, L.ptr(l.weight), L.ptr(imgs[l]["folded"]), ctypes.byref(host, eb * (2 * len(stale) + i)))
+            _PACK_TABLES.clear()  # one live table (a second model in the process rebuilds it: cheap)
+            table = _PACK_TABLES[key] = torch.frombuffer(host, dtype=torch.uint8).clone().to(stale[0].weight.device)
+        L.call("rv_pack_batch", L.ptr(table), n_entries, L.stream_ptr())
+        for l in stale:
+            for f, img in imgs[l].items():
+                l.images.adopt(image_slot(f), (l.weight,), img, persistent=True)
 
 
 class TapLayer:
@@ -673,13 +668,8 @@ class TapLayer:
             cv = taps * pad32(c)
         self.geom = L.TapGeom(kh, kw, stride_w, pad[0], pad[1], cu, cv)
         self.cu, self.cv = cu, cv
-        self._packed: Dict[str, Tensor] = {}
-        self._version = None
-        self._images: Dict[str, Tensor] = {}  # persistent buffers of the batched re-pack (prepack_stale)
+        self.images = ImageCache()  # every device image made from the parameters; nothing else on the layer holds one
         self._fold_geom = None
-        self._fold_image: Optional[Tensor] = None
-        self._fold_version = None
-        self._bias_pad: Optional[Tuple[tuple, Tensor]] = None
         _LAYERS.add(self)
 
     # forward direction of the torch module: conv = gather, conv-transpose = scatter
@@ -727,100 +717,62 @@ class TapLayer:
             self._fold_geom = gf
         return self._fold_geom
 
+    # ---- images made from the parameters: all in self.images, all kept valid by images.source_key ---------------------
+    def image_buffer(self, form: str, kind: Optional[str] = None) -> Tensor:
+        """Where the next image of ``form`` goes: the buffer of the held entry if that is persistent (rewritten in place), else a new one."""
+        old = self.images.held(image_slot(form, kind))
+        if old is not None and old.persistent:
+            return old.data
+        n = L.load().rv_packed_weight_bytes(self.fold_geom() if form == "folded" else self.geom) // 2
+        return torch.empty(n, dtype=L.act_dtype(), device=self.weight.device)
+
+    def _pack(self, w: Tensor, imgs: Dict[str, Tensor]) -> None:
+        dst = (imgs["folded"],) if "folded" in imgs else (imgs.get("gather"), imgs.get("scatter"))
+        L.call("rv_pack_weight_folded" if "folded" in imgs else "rv_pack_weight", self.geom, L.ptr(w), *map(L.ptr, dst), L.stream_ptr())
+
+    def packed(self, form: str) -> Tensor:
+        """Weight image for ``form`` (gather / scatter / folded) in the current operand type; re-packed when the parameter changed
+        (optimizer step / load_state_dict).  The bf16 folded image is one persistent buffer from its first use on."""
+        def make(old: Optional[Image]) -> Tensor:
+            # a training step needs both images (forward in one form, backward-data in the other): one launch writes both
+            both = (form in FORMS and L.operand_tag() == "bf16" and torch.is_grad_enabled() and self.weight.requires_grad
+                    and not any(self.images.current(image_slot(f)) for f in FORMS))
+            imgs = {f: self.image_buffer(f) for f in (FORMS if both else (form,))}
+            self._pack(self._torch_weight(), imgs)
+            for f in imgs.keys() - {form}:
+                self.images.adopt(image_slot(f), (self.weight,), imgs[f])
+            return imgs[form]
+
+        return self.images.get(image_slot(form), (self.weight,), make, persistent=form == "folded" and L.operand_tag() == "bf16").data
+
     def packed_folded(self) -> Tensor:
-        """bf16 gather image of the folded form; re-packed with the other images when the parameter changed."""
-        if L.operand_tag() != "bf16":  # (eval under autocast(float16): its own image, re-made when the parameter changed)
-            ver = (self.weight._version, self.weight.data_ptr())
-            hit = self.__dict__.get("_fold_f16")
-            if hit is None or hit[0] != ver:
-                n = L.load().rv_packed_weight_bytes(self.fold_geom()) // 2
-                img = torch.empty(n, dtype=L.act_dtype(), device=self.weight.device)
-                L.call("rv_pack_weight_folded", self.geom, L.ptr(self.weight.detach().contiguous().float()), L.ptr(img), L.stream_ptr())
-                self.__dict__["_fold_f16"] = hit = (ver, img)
-            return hit[1]
-        ver = (self.weight._version, self.weight.data_ptr())
-        if ver != self._fold_version or self._fold_image is None:
-            gf = self.fold_geom()
-            n = L.load().rv_packed_weight_bytes(gf) // 2
-            if self._fold_image is None:
-                self._fold_image = torch.empty(n, dtype=torch.bfloat16, device=self.weight.device)
-            L.call("rv_pack_weight_folded", self.geom, L.ptr(self.weight.detach().contiguous().float()), L.ptr(self._fold_image), L.stream_ptr())
-            self._fold_version = ver
-        return self._fold_image
+        return self.packed("folded")
 
     def packed_eval(self, form: str, bn: nn.Module) -> Tuple[Tensor, Tensor]:
         """Inference image of conv -> eval-mode BatchNorm: (weight image with gamma / sqrt(var + eps) folded into every output
-        channel, padded bias beta - mean * scale), cached until the conv weight or any BatchNorm tensor changes.  The fold is
+        channel, padded bias beta - mean * scale), cached until the conv weight, any BatchNorm tensor or eps changes.  The fold is
         a handful of small fp32 torch ops once per checkpoint, not per forward."""
-        key = (self.weight._version, self.weight.data_ptr(), bn.weight._version, bn.bias._version,
-               bn.running_mean._version, bn.running_var._version, bn.running_mean.data_ptr())
-        cache = self.__dict__.setdefault("_eval_fold", {})
-        hit = cache.get((form, L.operand_tag()))
-        if hit is None or hit[0] != key:
-            c, cp = self.c_out, pad32(self.c_out)
+        def make(old: Optional[Image]) -> Tuple[Tensor, Tensor]:
             scale = bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
             shift = bn.bias.detach().double() - bn.running_mean.detach().double() * scale
-            w = self._torch_weight(out_scale=scale.float())
-            geom = self.fold_geom() if form == "folded" else self.geom
-            nbytes = L.load().rv_packed_weight_bytes(geom)
-            img = torch.empty(nbytes // 2, dtype=L.act_dtype(), device=self.weight.device)
-            if form == "folded":
-                L.call("rv_pack_weight_folded", self.geom, L.ptr(w.contiguous()), L.ptr(img), L.stream_ptr())
-            else:
-                L.call("rv_pack_weight", self.geom, L.ptr(w), L.ptr(img if form == "gather" else None),
-                       L.ptr(img if form == "scatter" else None), L.stream_ptr())
-            bias = torch.zeros(cp, dtype=torch.float32, device=self.weight.device)
-            bias[:c] = shift.float()
-            cache[(form, L.operand_tag())] = hit = (key, img, bias)
-        return hit[1], hit[2]
+            img = self.image_buffer(form, "eval_fold")
+            self._pack(self._torch_weight(out_scale=scale.float()), {form: img})
+            return img, torch.nn.functional.pad(shift.float(), (0, pad32(self.c_out) - self.c_out))
+
+        e = self.images.get(image_slot(form, "eval_fold"), (self.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make, extra=(bn.eps,))
+        return e.data, e.aux
 
     def padded_bias(self) -> Tensor:
         """fp32 bias padded to the 32-channel slab, cached until the parameter changes (two launches per step and biased layer otherwise)."""
-        b = self.bias
-        key = (b._version, b.data_ptr())
-        if self._bias_pad is None or self._bias_pad[0] != key:
-            self._bias_pad = (key, torch.nn.functional.pad(b.detach().float(), (0, pad32(self.c_out) - self.c_out)))
-        return self._bias_pad[1]
+        make = lambda old: torch.nn.functional.pad(self.bias.detach().float(), (0, pad32(self.c_out) - self.c_out))
+        return self.images.get(("bias", None, "f32"), (self.bias,), make).data
 
     def invalidate(self) -> None:
-        """Drop every cached image of this layer (packed weights of both operand types, folded forms, eval-mode BatchNorm folds,
-        padded bias).  They are re-made automatically when ``weight._version`` or its storage changes
-        (optimizer steps, ``load_state_dict``, ``copy_``); writes that bypass the version counter (``p.data.add_(...)``,
-        weight-averaging swaps through ``.data``) do not show there -- call this (or ``engine.invalidate_packed_weights``)
-        after such surgery."""
-        self._packed.clear()
-        self._version = None
-        self._fold_version = None
-        # every other image made from the parameters: the fp16 folded image, the eval-mode BatchNorm folds (weight image + bias)
-        # and the padded bias are keyed on the same version counters, which such writes do not move either
-        self.__dict__.pop("_fold_f16", None)
-        self.__dict__.pop("_eval_fold", None)
-        self._bias_pad = None
-
-    def packed(self, form: str) -> Tensor:
-        """bf16 weight image for ``form``; re-packed when the parameter changed (optimizer step / load_state_dict)."""
-        ver = (self.weight._version, self.weight.data_ptr())
-        if ver != self._version:
-            self._packed.clear()
-            self._version = ver
-        if L.operand_tag() != "bf16":  # fp16 images (inference under autocast(float16)): their own cache entries, packed by that build
-            key = form + ":" + L.operand_tag()
-            if key not in self._packed:
-                nbytes = L.load().rv_packed_weight_bytes(self.geom)
-                buf = torch.empty(nbytes // 2, dtype=L.act_dtype(), device=self.weight.device)
-                L.call("rv_pack_weight", self.geom, L.ptr(self._torch_weight()), L.ptr(buf if form == "gather" else None),
-                       L.ptr(buf if form == "scatter" else None), L.stream_ptr())
-                self._packed[key] = buf
-            return self._packed[key]
-        if form not in self._packed:
-            nbytes = L.load().rv_packed_weight_bytes(self.geom)
-            w = self._torch_weight()
-            # a training step needs both images (forward in one form, backward-data in the other): one launch writes both
-            forms = ("gather", "scatter") if (torch.is_grad_enabled() and self.weight.requires_grad and "gather" not in self._packed and "scatter" not in self._packed) else (form,)
-            bufs = {f: torch.empty(nbytes // 2, dtype=torch.bfloat16, device=self.weight.device) for f in forms}
-            L.call("rv_pack_weight", self.geom, L.ptr(w), L.ptr(bufs.get("gather")), L.ptr(bufs.get("scatter")), L.stream_ptr())
-            self._packed.update(bufs)
-        return self._packed[form]
+        """Drop every image of this layer.  ``images.source_key`` re-makes an image when the version counter or the storage pointer of a
+        tensor it was made from moves (optimizer steps, ``load_state_dict``, ``copy_``, a tensor swapped in through ``.data``).  Writes that
+        move neither (``p.data.add_(...)``, a kernel writing through the raw pointer) do not show there -- call this (or
+        ``engine.invalidate_packed_weights``) after such surgery."""
+        self.images.clear()
 
 
 # ---------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ from torch import Tensor, nn
 from . import _lib as L
 from . import engine as E
 from .engine import Act, Lazy, Operand, Tape
+from .images import source_key
 
 
 # ---------------------------------------------------------------------------------------------
@@ -173,7 +174,7 @@ def range_partition_program(t: Tape, m: nn.Module, features: Tensor, cart: Tenso
             raise L.RvError("RangePartition: a non-boolean mask must hold only 0 and 1 (the reference MULTIPLIES by it; the kernel gates)")
         mask8 = mask.to(torch.uint8).contiguous()
     bounds = m.__dict__.get("_rv_bounds")
-    ver = (m.lower_bounds._version, m.upper_bounds._version, m.lower_bounds.data_ptr())
+    ver = source_key(m.lower_bounds, m.upper_bounds)
     if bounds is None or bounds[0] != ver:  # (host copies of the twelve frozen numbers: read back once, not per step)
         lo = (ctypes.c_float * bands)(*[float(v) for v in m.lower_bounds.detach().flatten().tolist()])
         hi = (ctypes.c_float * bands)(*[float(v) for v in m.upper_bounds.detach().flatten().tolist()])

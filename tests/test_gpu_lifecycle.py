@@ -1,16 +1,16 @@
 """Life cycle of the cached device images: one model run in one mode, changed, and run again.
 
-``engine.TapLayer`` keeps packed weight images (``_packed``, with ``:f16`` variants), the persistent buffers of the batched re-pack
-(``_images`` / ``_PACK_TABLES``), the folded stride-1 images (``_fold_image`` / ``_fold_f16``), the eval-mode BatchNorm folds (``_eval_fold``:
-weight image + padded bias per (form, operand)) and the padded bias (``_bias_pad``); ``program.py`` keeps ``_rv_bounds``.  All of them are kept
-valid by ``Tensor._version`` / ``data_ptr()`` keys.  A wrong image makes no kernel test fail; it shows as validation outputs that are silently
-wrong.  Two checking layers, used by every scenario:
+``engine.TapLayer`` keeps every image made from parameters in one cache, ``layer.images`` (``images.ImageCache``): packed weight images of
+both operand types, the persistent buffers the batched re-pack writes, the folded stride-1 images, the eval-mode BatchNorm folds (weight
+image + padded bias per (form, operand)) and the padded bias; ``program.py`` keeps host copies of the ``RangePartition`` bounds.  All of them
+are kept valid by one rule, ``images.source_key``: the version counter and the pointer of every tensor the image was made from.  A wrong image
+makes no kernel test fail; it shows as validation outputs that are silently wrong.  Two checking layers, used by every scenario:
 
-* ``audit(model)`` (white box): every image a layer of the model would SERVE now is re-made from the current parameters through a fresh
-  ``TapLayer`` with empty caches and must be equal bit for bit (the pack kernels are tested against torch elsewhere: here the fresh pack is
-  the reference for staleness only).  A weight image whose key no longer matches the parameter (all of them right after an optimiser step)
-  is not served -- it is re-packed at its next use -- and is counted under ``stale_skipped``.  The audit never re-packs ``_packed`` /
-  ``_fold_image`` itself, so it can run between training steps without taking work away from ``prepack_stale``.
+* ``audit(model)``: every entry of ``layer.images.entries()`` that the layer would SERVE now is re-made from the entry's recorded source
+  tensors through a fresh ``TapLayer`` with an empty cache and must be equal bit for bit (the pack kernels are tested against torch
+  elsewhere: here the fresh pack is the reference for staleness only).  A weight image whose key no longer matches the parameter (all of them right after an optimiser step)
+  is not served -- it is re-packed at its next use -- and is counted under ``stale_skipped``.  The audit never re-packs the weight images or
+  the folded images itself, so it can run between training steps without taking work away from ``prepack_stale``.
 * ``cold(model)``: a new model that has never run, loaded with a deep copy of the warm model's state dict.  The warm model's eval outputs
   must EQUAL the cold model's (``torch.equal``); two cold rebuilds are shown to be bit-equal first, so a mismatch means staleness.
 * the state dict read back from the device goes through the CPU oracle in eval mode (fp32): ``rel_err(warm, oracle)`` within
@@ -24,7 +24,7 @@ from __future__ import annotations
 import contextlib
 import copy
 import gc
-import weakref
+import types
 
 import pytest
 import torch
@@ -35,7 +35,6 @@ pytestmark = pytest.mark.gpu
 
 N_CLS = 3
 KINDS = ("packed", "packed_f16", "fold", "fold_f16", "eval_fold", "eval_fold_folded", "bias_pad")  # (eval_fold_folded: those of eval_fold in the folded strided form)
-_BN_OF: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()  # TapLayer -> the BatchNorm module packed_eval folded into it
 
 
 # ---------------------------------------------------------------------------------------------
@@ -92,30 +91,12 @@ def _grids(small):
     return L.select(L.SEL_SMALL_GRIDS) if small else contextlib.nullcontext()
 
 
-@contextlib.contextmanager
-def _recording_folds():
-    """Remember which BatchNorm module every ``packed_eval`` call folded (the audit re-makes the fold with the same module)."""
-    from range_view_3d_detection_amd import engine as E
-
-    real = E.TapLayer.packed_eval
-
-    def packed_eval(self, form, bn):
-        _BN_OF[self] = bn
-        return real(self, form, bn)
-
-    E.TapLayer.packed_eval = packed_eval
-    try:
-        yield
-    finally:
-        E.TapLayer.packed_eval = real
-
-
 def evaluate(model, batch, tag="bf16", small=False):
     """Eval-mode forward: (logits, regressands) as fp32 CPU tensors.  ``tag`` "f16": under ``torch.autocast("cuda", dtype=torch.float16)``."""
     model.eval()
     data = dict(batch)
     cast = torch.autocast("cuda", dtype=torch.float16) if tag == "f16" else contextlib.nullcontext()
-    with torch.no_grad(), cast, _grids(small), _recording_folds():
+    with torch.no_grad(), cast, _grids(small):
         out, _ = model.head(model.backbone(data), data, return_loss=False)
     lg, rg = out[1][0]["logits"].float().cpu(), out[1][0]["regressands"].float().cpu()
     assert torch.isfinite(lg).all() and torch.isfinite(rg).all()
@@ -153,6 +134,11 @@ def _same_bits(a, b):
     return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.int16), b.view(torch.int16))
 
 
+def layers_of(model):
+    """(module name, TapLayer) of every conv of ``model`` that has run."""
+    return [(name, m.__dict__["_rv_layer"]) for name, m in model.named_modules() if "_rv_layer" in m.__dict__]
+
+
 def audit(model):
     """Every cached image the conv layers of ``model`` would serve now against a fresh pack of the current parameters; returns the number
     of images compared per kind (and ``stale_skipped``: weight images whose key says "re-pack at next use")."""
@@ -160,49 +146,39 @@ def audit(model):
     from range_view_3d_detection_amd import engine as E
 
     n = dict.fromkeys(KINDS + ("stale_skipped",), 0)
+    f16 = {"bf16": "", "f16": "_f16"}
+    modules = dict(model.named_modules())
     with torch.no_grad():
-        for name, m in model.named_modules():
-            l = m.__dict__.get("_rv_layer")
-            if l is None:
-                continue
-            assert l.weight is m.weight, name
+        for name, l in layers_of(model):
+            assert l.weight is modules[name].weight, name
             g = l.geom
-            fresh = E.TapLayer(l.weight, g.stride_w, (g.pad_h, g.pad_w), l.transposed, bias=l.bias, in_perm=l.in_perm)
-            ver = (l.weight._version, l.weight.data_ptr())
-            for key, img in list(l._packed.items()):
-                if l._version != ver:
-                    n["stale_skipped"] += 1
-                    continue
-                form, _, tag = key.partition(":")
-                with L.operand(tag or "bf16"):
-                    assert _same_bits(img, fresh.packed(form)), (name, key)
-                n["packed_f16" if tag else "packed"] += 1
-            if l._fold_image is not None:
-                if l._fold_version != ver:
-                    n["stale_skipped"] += 1
+            for e in l.images.entries():
+                kind, form, tag = e.slot
+                what = (name, e.slot)
+                # the fresh layer is built from the tensors the entry says it was made from: they must be the layer's own
+                assert e.sources[0] is (l.bias if kind == "bias" else l.weight), what
+                fresh = E.TapLayer(l.weight if kind == "bias" else e.sources[0], g.stride_w, (g.pad_h, g.pad_w), l.transposed,
+                                   bias=e.sources[0] if kind == "bias" else l.bias, in_perm=l.in_perm)
+                if kind in ("weight", "folded"):
+                    if not e.current:
+                        n["stale_skipped"] += 1
+                        continue
+                    with L.operand(tag):
+                        assert _same_bits(e.data, fresh.packed(form)), what
+                    n[("packed" if kind == "weight" else "fold") + f16[tag]] += 1
+                elif kind == "eval_fold":
+                    assert len(e.sources) == 5 and len(e.extra) == 1, what
+                    bn = types.SimpleNamespace(**dict(zip(("weight", "bias", "running_mean", "running_var"), e.sources[1:])), eps=e.extra[0])
+                    with L.operand(tag):
+                        img, bias = l.packed_eval(form, bn)  # what the layer serves for the current state of conv and BatchNorm
+                        ref_img, ref_bias = fresh.packed_eval(form, bn)
+                    assert _same_bits(img, ref_img), what + ("image",)
+                    assert bias.dtype == torch.float32 and torch.equal(bias, ref_bias), what + ("bias",)
+                    n["eval_fold"] += 1
+                    n["eval_fold_folded"] += int(form == "folded")
                 else:
-                    assert _same_bits(l._fold_image, fresh.packed_folded()), (name, "_fold_image")
-                    n["fold"] += 1
-            hit = l.__dict__.get("_fold_f16")
-            if hit is not None:
-                if hit[0] != ver:
-                    n["stale_skipped"] += 1
-                else:
-                    with L.operand("f16"):
-                        assert _same_bits(hit[1], fresh.packed_folded()), (name, "_fold_f16")
-                    n["fold_f16"] += 1
-            for form, tag in list(l.__dict__.get("_eval_fold", {})):
-                bn = _BN_OF[l]
-                with L.operand(tag):
-                    img, bias = l.packed_eval(form, bn)  # what the layer serves for the current state of conv and BatchNorm
-                    ref_img, ref_bias = fresh.packed_eval(form, bn)
-                assert _same_bits(img, ref_img), (name, "_eval_fold image", form, tag)
-                assert bias.dtype == torch.float32 and torch.equal(bias, ref_bias), (name, "_eval_fold bias", form, tag)
-                n["eval_fold"] += 1
-                n["eval_fold_folded"] += int(form == "folded")
-            if l._bias_pad is not None:
-                assert torch.equal(l.padded_bias(), fresh.padded_bias()), (name, "_bias_pad")
-                n["bias_pad"] += 1
+                    assert kind == "bias" and torch.equal(l.padded_bias(), fresh.padded_bias()), what
+                    n["bias_pad"] += 1
     return n
 
 
@@ -349,9 +325,9 @@ def test_frozen_backbone_convs(widths, W, small, whole):
 
 @pytest.mark.parametrize("widths,W,small", CASES)
 def test_ordinary_loop_alternating_operand_types(widths, W, small):
-    """3. eval (bf16) -> two optimiser steps -> eval (f16 autocast) -> two steps -> eval (bf16) -> eval (f16): the ``:f16`` weight images
+    """3. eval (bf16) -> two optimiser steps -> eval (f16 autocast) -> two steps -> eval (bf16) -> eval (f16): the fp16 weight images
     and the fp16 folds neither survive a re-pack nor are lost to ``prepack_stale``; inside every training step (after backward) the images the
-    step ran on -- ``_fold_image`` of the strided layers among them at c128 -- are audited while they are current."""
+    step ran on -- the folded images of the strided layers among them at c128 -- are audited while they are current."""
     model = build(widths)
     batch = batch_of(2, 16, W, 3)
     check_cold_rebuilds_agree(model, widths, batch, ("bf16", "f16"), small)
@@ -369,7 +345,7 @@ def test_ordinary_loop_alternating_operand_types(widths, W, small):
     check_warm(model, widths, batch, "f16", small, label="3 last eval")
     expect(audit(model), "packed", "packed_f16", "eval_fold", "bias_pad", *folded)
     # both operand types' folds are held at once
-    tags = {tag for m in model.modules() if "_rv_layer" in m.__dict__ for _, tag in m.__dict__["_rv_layer"].__dict__.get("_eval_fold", {})}
+    tags = {e.slot[2] for _, l in layers_of(model) for e in l.images.entries() if e.slot[0] == "eval_fold" and e.current}
     assert tags == {"bf16", "f16"}, tags
 
 
@@ -436,16 +412,16 @@ def test_in_place_edits_torch_can_see():
 def test_edits_torch_cannot_see_then_invalidate():
     """6. ``p.data.add_(...)`` on conv weights, a conv bias, BatchNorm weights and running statistics, then
     ``engine.invalidate_packed_weights(model)``: after the call the audit and the cold equality hold, under both operand types -- the
-    promise of ``TapLayer.invalidate``'s docstring, for ``_eval_fold``, ``_fold_f16`` and ``_bias_pad`` as well as ``_packed``."""
+    promise of ``TapLayer.invalidate``'s docstring, for the eval folds, the fp16 folded images and the padded biases as well as the weight
+    images."""
     from range_view_3d_detection_amd import _lib as L
     from range_view_3d_detection_amd import engine as E
 
     def fold_f16():
         """The fp16 folded image of every strided layer, asked for as an fp16 program that does not fold its BatchNorm asks for it."""
         with torch.no_grad(), L.operand("f16"):
-            for m in model.modules():
-                l = m.__dict__.get("_rv_layer")
-                if l is not None and l.fold_geom() is not None:
+            for _, l in layers_of(model):
+                if l.fold_geom() is not None:
                     l.packed_folded()
 
     widths, W, small = "c128", 128, True  # (the folded strided forms run here)
@@ -500,13 +476,13 @@ def test_deepcopy_of_a_warm_model():
 
 def _batched(model):
     """Layers of ``model`` whose served images are the persistent buffers ``prepack_stale`` writes."""
-    return sum(1 for m in model.modules() if "_rv_layer" in m.__dict__ and m.__dict__["_rv_layer"]._images
-               and m.__dict__["_rv_layer"]._packed.get("gather") is m.__dict__["_rv_layer"]._images["gather"])
+    held = [l.images.held(("weight", "gather", "bf16")) for _, l in layers_of(model)]  # (stale after the optimiser step: held, not current)
+    return sum(1 for e in held if e is not None and e.persistent)
 
 
 def test_prepack_stale_subsets():
     """8. ``prepack_stale``: exactly one stale layer (the ``< 2`` early return), a layer seen for the first time in the same step as stale
-    ones, a second model trained in the same process (``_PACK_TABLES`` rebuilt), the first model deleted and a third of other widths
+    ones, a second model trained in the same process (the device table of ``rv_pack_batch`` rebuilt), the first model deleted and a third of other widths
     trained.  The audit runs in every step, after backward: the images the step ran on are current then."""
     from range_view_3d_detection_amd import engine as E
 
@@ -520,14 +496,17 @@ def test_prepack_stale_subsets():
     bs = [batch_of(2, 16, 64, s) for s in (81, 82, 83)]
     train(a, opt_a, bs[:2], between=audited(a))
     assert _batched(a) > 40  # (the second step ran on the batched re-pack)
+    slot = ("weight", "gather", "bf16")
+    buffers = {l: l.images.held(slot).data for _, l in layers_of(a) if l.images.held(slot).persistent}
     train(a, opt_a, bs[2:], between=audited(a))
+    assert all(l.images.held(slot).data is buf for l, buf in buffers.items())  # (rewritten in place: the device table stays valid)
     # exactly one stale layer: every image is current after this forward/backward; then ONE weight changes
     a.train()
     a(bs[0]).backward()
     conv = _edit_targets(a)[0]
     with torch.no_grad():
         conv.weight.mul_(1.05)
-    stale = [l for l in E._LAYERS if l._version is not None and l._packed and l._version != (l.weight._version, l.weight.data_ptr())]
+    stale = [l for l in E._LAYERS if (held := [e.current for e in l.images.entries() if e.slot[0] == "weight"]) and not any(held)]
     assert len(stale) == 1 and stale[0].weight is conv.weight
     a(bs[1]).backward()
     counts = audit(a)
@@ -548,7 +527,7 @@ def test_prepack_stale_subsets():
     batch = batch_of(2, 16, 64, 3)
     check_warm(b, "c32", batch, label="8 second model")
     # the first model gone, a third one of other widths
-    del a, opt_a, conv, stale, audited
+    del a, opt_a, conv, stale, audited, buffers
     gc.collect()
     c = build("c64", seed=4)
     opt_c = optimiser(c)
@@ -579,7 +558,7 @@ def test_shape_changes_between_calls():
 
 
 def test_range_partition_bounds_cache():
-    """10. ``RangePartition``'s host copies of the band bounds (``_rv_bounds``): ``lower_bounds.copy_`` is picked up -- eval equals a cold
+    """10. ``RangePartition``'s host copies of the band bounds: ``lower_bounds.copy_`` is picked up -- eval equals a cold
     rebuild of the same state at all four strides."""
     from range_view_3d_detection_amd.nn.backbones.dla import RangeNet
 
@@ -590,7 +569,7 @@ def test_range_partition_bounds_cache():
 
     def run(net):
         net.eval()
-        with torch.no_grad(), _recording_folds():
+        with torch.no_grad():
             out = net({k: batch[k] for k in ("features", "cart", "mask")})
         return {s: v.float().cpu() for s, v in out.items()}
 
@@ -612,3 +591,29 @@ def test_range_partition_bounds_cache():
     for s in moved:
         assert torch.isfinite(moved[s]).all() and torch.equal(moved[s], ref[s]), s
     expect(audit(net), "eval_fold")  # (every conv of this backbone has a BatchNorm behind it: in eval mode there is no other image)
+
+
+def test_batchnorm_tensors_swapped_through_data():
+    """11. ``bn.weight.data`` / ``bn.bias.data`` / ``bn.running_var.data`` of every BatchNorm replaced, one attribute at a time, by a scaled
+    clone (x 1.5, far above a bf16 ulp): no version counter moves and ``running_mean`` stays where it is -- only the swapped tensor's pointer
+    tells.  Under both operand types the next eval differs from the one before the swap and equals a cold rebuild of the current state."""
+    model = build("c32")
+    batch = batch_of(2, 16, 64, 3)
+    tags = ("bf16", "f16")
+    check_cold_rebuilds_agree(model, "c32", batch, tags)
+    last = {tag: evaluate(model, batch, tag) for tag in tags}
+    bns = [m for m in model.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+    assert len(bns) > 40
+    for attr in ("weight", "bias", "running_var"):
+        for bn in bns:
+            t = getattr(bn, attr)
+            version, mean_ptr = t._version, bn.running_mean.data_ptr()
+            t.data = 1.5 * t.detach().clone()
+            assert t._version == version and bn.running_mean.data_ptr() == mean_ptr, attr  # (the premise: no version moved)
+        for tag in tags:
+            warm = evaluate(model, batch, tag)
+            ref = evaluate(cold(model, "c32"), batch, tag)
+            assert not torch.equal(warm[0], last[tag][0]) and not torch.equal(warm[1], last[tag][1]), (attr, tag, "the old fold was served")
+            assert torch.equal(warm[0], ref[0]) and torch.equal(warm[1], ref[1]), (attr, tag, rel_err(warm[0], ref[0]), rel_err(warm[1], ref[1]))
+            last[tag] = warm
+        expect(audit(model), "eval_fold", "bias_pad")

@@ -636,15 +636,16 @@ def test_batched_weight_repack_equals_the_per_layer_pack():
     E.prepack_stale()
     covered = 0
     for l in layers:
+        held = {e.slot: e for e in l.images.entries() if e.slot[0] == "weight"}
         if l.in_perm is not None:
-            assert l._version != (l.weight._version, l.weight.data_ptr())  # still stale: the lazy path repacks it
+            assert held and not any(e.current for e in held.values())  # still stale: the lazy path repacks it
             continue
-        assert l._version == (l.weight._version, l.weight.data_ptr()) and set(l._packed) == {"gather", "scatter"}
+        assert set(held) == {("weight", "gather", "bf16"), ("weight", "scatter", "bf16")} and all(e.current and e.persistent for e in held.values())
         n = L.load().rv_packed_weight_bytes(ctypes.byref(l.geom)) // 2
         ref = {f: torch.empty(n, dtype=torch.bfloat16, device=DEV) for f in ("gather", "scatter")}
         L.call("rv_pack_weight", ctypes.byref(l.geom), L.ptr(l.weight.detach().contiguous()), L.ptr(ref["gather"]), L.ptr(ref["scatter"]), L.stream_ptr())
         for f in ref:
-            assert torch.equal(l._packed[f].view(torch.int16), ref[f].view(torch.int16)), (f, l.geom.kh, l.geom.kw, l.geom.stride_w)
+            assert torch.equal(held["weight", f, "bf16"].data.view(torch.int16), ref[f].view(torch.int16)), (f, l.geom.kh, l.geom.kw, l.geom.stride_w)
         covered += 1
     assert covered > 40
     loss = model(batch)  # and the next step runs on the batched images
@@ -655,10 +656,11 @@ def test_batched_weight_repack_equals_the_per_layer_pack():
 
     opt = AdamW(list(model.parameters()), lr=1e-2)
     loss.backward()
-    before = {id(l): l._packed["gather"].clone() for l in layers if l.in_perm is None}
+    gather = lambda l: l.images.current(("weight", "gather", "bf16")).data
+    before = {id(l): gather(l).clone() for l in layers if l.in_perm is None}
     opt.step()
     model(batch)
-    changed = sum(int(not torch.equal(before[id(l)], l._packed["gather"])) for l in layers if l.in_perm is None)
+    changed = sum(int(not torch.equal(before[id(l)], gather(l))) for l in layers if l.in_perm is None)
     assert changed == len(before), (changed, len(before))
 
 

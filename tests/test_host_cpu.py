@@ -707,14 +707,17 @@ def test_tap_layer_invalidate_drops_every_cached_image():
 
     conv = torch.nn.Conv2d(32, 32, 3, stride=(1, 2), bias=True)
     l = E.tap_layer(conv)
-    ver = (conv.weight._version, conv.weight.data_ptr())
-    l._packed.update({"gather": torch.zeros(1), "gather:f16": torch.zeros(1)})
-    l._version = l._fold_version = ver
-    l.__dict__["_fold_f16"] = (ver, torch.zeros(1))
-    l.__dict__["_eval_fold"] = {("gather", "bf16"): (None, torch.zeros(1), torch.zeros(1))}
-    assert torch.equal(l.padded_bias()[:32], conv.bias.detach()) and l._bias_pad is not None
+    bn = torch.nn.BatchNorm2d(32)
+    for slot in (("weight", "gather", "bf16"), ("weight", "gather", "f16"), ("folded", "folded", "f16")):
+        l.images.adopt(slot, (conv.weight,), torch.zeros(1))
+    l.images.adopt(("weight", "scatter", "bf16"), (conv.weight,), torch.zeros(1), persistent=True)  # (as the batched re-pack leaves it)
+    l.images.get(("folded", "folded", "bf16"), (conv.weight,), lambda old: torch.zeros(1), persistent=True)
+    l.images.adopt(("eval_fold", "gather", "bf16"), (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), torch.zeros(1),
+                   aux=torch.zeros(1), extra=(bn.eps,))
+    assert torch.equal(l.padded_bias()[:32], conv.bias.detach())
+    held = l.images.entries()
+    assert {e.slot[0] for e in held} == {"weight", "folded", "eval_fold", "bias"} and len(held) == 7 and all(e.current for e in held)
     l.invalidate()
-    assert not l._packed and l._version is None and l._fold_version is None and l._bias_pad is None
-    assert "_fold_f16" not in l.__dict__ and "_eval_fold" not in l.__dict__
+    assert l.images.entries() == []
     conv.bias.data.add_(1.0)
     assert torch.equal(l.padded_bias()[:32], conv.bias.detach())
