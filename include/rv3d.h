@@ -200,7 +200,9 @@ int rv_tap_data_grad_bnb(const rvTapGeom* g, const rvTapShape* s, int32_t scatte
  * `workspace` holds split-K partial slabs; rv_tap_wgrad_workspace_bytes() sizes it.
  * V may carry the same folded BN+ReLU as in the forward (RV_IN_AFFINE|RV_IN_RELU in
  * s->flags applies to V when v_affine != 0, else to U).
- * Replaces cuDNN conv2d backward-weight / ATen conv_transpose2d backward-weight. */
+ * Replaces cuDNN conv2d backward-weight / ATen conv_transpose2d backward-weight.
+ * All three entry points plan alike and refuse what the launch refuses (a null g or s, kh*kw above 24 taps, Wv != Wu * stride_w, an
+ * empty tensor): rv_tap_wgrad_workspace_bytes then returns -1, rv_tap_wgrad_info nonzero, both with rv_last_error() set. */
 int64_t rv_tap_wgrad_workspace_bytes(const rvTapGeom* g, const rvTapShape* s);
 /* host-side introspection (bench / tests): info[0] = kernel generation that rv_tap_wgrad will launch for (g, s)
  * (1 generic, 2 register-staged 3-tap groups, 3 LDS-DMA ring), info[1] = split-K factor, info[2] = workgroups */

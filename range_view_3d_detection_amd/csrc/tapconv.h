@@ -54,6 +54,7 @@ int rv_build_tap_table(const rvTapGeom* g, bool scatter, TapTable* tt, int* phas
 
 // Everything that is decided about a tap-conv launch before it runs and that no kernel reads: filled ONCE by tap_plan
 // (tapconv.hip), read by the planning entry points (rv_tap_stats_rows, rv_tap_launch_info, rv_tap_bnb_rows) and by the launch.
+// (The weight gradient's planning entry points, rv_tap_wgrad_info and rv_tap_wgrad_workspace_bytes, read wgrad.hip's own WgradPlan.)
 struct TapPlan {
     int gen;             // 1 = generic, 2, 4, 5, 6, 7 = pointwise; 0 = RV_OUT_BNB asked of a layer no kernel forms the sums for
     int bn, ks;          // generations 4 / 5: channels per workgroup (256 / 128); generation 2: 32-channel K steps per chunk

@@ -62,6 +62,25 @@ __device__ __forceinline__ u32x4 transform8(u32x4 v, const float* sc, const floa
     return v;
 }
 
+// Shared by wgrad_kernel and wgrad2_body, the register-staged generations.  (Their folded-BatchNorm prologue, the sc[8] / sh[8] load,
+// stays written out in both: as a helper it swaps the registers the two base pointers land in.)
+// element offset of 16-byte chunk `chunk` of pixel row k in a staged [k][128] tile (granule swizzle, file header)
+__device__ __forceinline__ int stage_off(int k, int chunk) { return k * 128 + (((chunk >> 1) ^ sigma(k)) << 4) + (chunk & 1) * 8; }
+
+// transposed-read addressing: lane = 16*g + 4*q + p supplies rows row0 + 8g + q (+4), columns col0 + 4p .. +3 (before the granule
+// swizzle) of its tile; col0: first channel of the 16-wide fragment inside the 128-wide tile.  (g, q, p come from the caller,
+// computed once in front of its K loop: formed in here, the same arithmetic is scheduled differently.)
+__device__ __forceinline__ bf16x8 frag(const bf16_t* tile, int g, int q, int p, int row0, int col0) {
+    const int r_lo = row0 + 8 * g + q, r_hi = r_lo + 4, gran = col0 >> 4;
+    const bf16_t* p_lo = tile + r_lo * 128 + ((gran ^ sigma(r_lo)) << 4) + 4 * p;
+    const bf16_t* p_hi = tile + r_hi * 128 + ((gran ^ sigma(r_hi)) << 4) + 4 * p;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p_lo);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p_hi);
+    typedef __attribute__((ext_vector_type(8))) short s16x8;
+    const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    return __builtin_bit_cast(bf16x8, both);
+}
+
 __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
     __shared__ __attribute__((aligned(16))) bf16_t lds[2][2][32 * 128];  // [buffer][U/V][k][128]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -143,8 +162,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
     auto store = [&](int buf) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int k = prow + 16 * j;
-            const int off = k * 128 + (((chunk >> 1) ^ sigma(k)) << 4) + (chunk & 1) * 8;
+            const int off = stage_off(prow + 16 * j, chunk);
             pin_here(ru[j]);
             pin_here(rv[j]);
             // zero-filled (out-of-range) slots hold exact zeros; relu(shift) must not leak into them
@@ -161,21 +179,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // transposed-read addressing: lane = 16*g + 4*q + p supplies row (8g + q [+4]), columns 4p..4p+3 of its tile
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    const int row_lo = 8 * g + q, row_hi = row_lo + 4;
-    auto frag = [&](const bf16_t* tile, int col0) -> bf16x8 {
-        // col0: first channel of the 16-wide fragment inside the 128-wide tile
-        const int gran = col0 >> 4;
-        const bf16_t* p_lo = tile + row_lo * 128 + ((gran ^ sigma(row_lo)) << 4) + 4 * p;
-        const bf16_t* p_hi = tile + row_hi * 128 + ((gran ^ sigma(row_hi)) << 4) + 4 * p;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p_lo);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p_hi);
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8, both);
-    };
-
     if (k_begin < k_end) {
         load(k_begin);
         store(0);
@@ -186,10 +190,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_kernel(const WgradArgs a) {
             if (has_next) load(kb + 32);
             bf16x8 fb[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) fb[j] = frag(&lds[buf][1][0], wn * 64 + j * 16);
+            for (int j = 0; j < 4; ++j) fb[j] = frag(&lds[buf][1][0], g, q, p, 0, wn * 64 + j * 16);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                const bf16x8 fa = frag(&lds[buf][0][0], wm * 64 + i * 16);
+                const bf16x8 fa = frag(&lds[buf][0][0], g, q, p, 0, wm * 64 + i * 16);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
                     acc[i][j] = RV_MFMA_16x16x32(fa, fb[j], acc[i][j], 0, 0, 0);
@@ -374,14 +378,14 @@ __device__ __forceinline__ void wgrad2_body(const Wgrad2Args& a, bf16_t (*lds)[2
             const int k = prow + 32 * j;
             pin_here(ru[j]);
             if ((affine || relu) && !a.v_affine && u_ok) ru[j] = transform8(ru[j], sc, sh, affine, relu);
-            *(u32x4*)(&lds[buf][0][k * 128 + (((chunk >> 1) ^ sigma(k)) << 4) + (chunk & 1) * 8]) = ru[j];
+            *(u32x4*)(&lds[buf][0][stage_off(k, chunk)]) = ru[j];
         }
 #pragma unroll
         for (int j = 0; j < 3; ++j) {
             const int k = prow + 32 * j;
             pin_here(rv[j]);
             if ((affine || relu) && a.v_affine && rv_ok[j]) rv[j] = transform8(rv[j], sc, sh, affine, relu);
-            if (k < 66) *(u32x4*)(&lds[buf][1][k * 128 + (((chunk >> 1) ^ sigma(k)) << 4) + (chunk & 1) * 8]) = rv[j];
+            if (k < 66) *(u32x4*)(&lds[buf][1][stage_off(k, chunk)]) = rv[j];
         }
     };
 
@@ -394,18 +398,6 @@ __device__ __forceinline__ void wgrad2_body(const Wgrad2Args& a, bf16_t (*lds)[2
             for (int j = 0; j < 2; ++j) acc[t][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
-    typedef __attribute__((ext_vector_type(8))) short s16x8;
-    auto frag = [&](const bf16_t* tile, int row0, int col0) -> bf16x8 {
-        // rows row0 + 8g + q (+4), columns col0 + 4p .. +3 (before the granule swizzle)
-        const int r_lo = row0 + 8 * g + q, r_hi = r_lo + 4, gran = col0 >> 4;
-        const bf16_t* p_lo = tile + r_lo * 128 + ((gran ^ sigma(r_lo)) << 4) + 4 * p;
-        const bf16_t* p_hi = tile + r_hi * 128 + ((gran ^ sigma(r_hi)) << 4) + 4 * p;
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p_lo);
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p_hi);
-        const s16x8 both = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        return __builtin_bit_cast(bf16x8, both);
-    };
-
     if (c_begin < c_end) {
         load(c_begin);
         store(0);
@@ -418,12 +410,12 @@ __device__ __forceinline__ void wgrad2_body(const Wgrad2Args& a, bf16_t (*lds)[2
             for (int kk = 0; kk < 2; ++kk) {  // two MFMA K-steps of 32 pixels
                 bf16x8 fa[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) fa[i] = frag(&lds[buf][0][0], kk * 32, wm * 64 + i * 16);
+                for (int i = 0; i < 4; ++i) fa[i] = frag(&lds[buf][0][0], g, q, p, kk * 32, wm * 64 + i * 16);
 #pragma unroll
                 for (int t = 0; t < TG; ++t) {
                     bf16x8 fb[2];
 #pragma unroll
-                    for (int j = 0; j < 2; ++j) fb[j] = frag(&lds[buf][1][0], kk * 32 + t, wn * 32 + j * 16);
+                    for (int j = 0; j < 2; ++j) fb[j] = frag(&lds[buf][1][0], g, q, p, kk * 32 + t, wn * 32 + j * 16);
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -777,75 +769,125 @@ __global__ __launch_bounds__(512, 2) void wgrad3_kernel(const Wgrad2Args a) {
     }
 }
 
+// Everything that is decided about a weight-gradient launch before it runs (the role TapPlan has for the tap-convs, tapconv.h): filled
+// ONCE by plan(), read by the three entry points below.  The library keeps no mutable state: a plan lives for one call.
 struct WgradPlan {
-    int taps, tiles_u, tiles_v, ksplit, k_per_split;
-    int64_t elems;
-    bool v2;
-    int groups, chunks, chunks_per_split;
-    int main_blocks, left_m, left_blocks;  // wgrad3's balanced split
+    int gen;        // 1 = wgrad_kernel, 2 = wgrad2_kernel, 3 = wgrad3_kernel
+    int ksplit;     // fp32 slabs the reduction sums
+    int64_t elems;  // of one slab
+    int64_t workspace_bytes;
+    int grid, block;  // 256 / 512 threads
+    size_t lds;       // dynamic LDS bytes: 0 / kW3Lds
+    int reduce_blocks;
+    UnpackTo up;
+    // what the kernel receives (a1: generation 1, a2: generations 2 and 3; the other one stays zero): the shape-derived fields set;
+    // pointers, ld_u, ld_v and v_affine unset until the launch fills them
+    WgradArgs a1;
+    Wgrad2Args a2;
 };
 
-bool wgrad_dma_eligible(const rvTapGeom* g, const rvTapShape* s);
-
 int plan(const rvTapGeom* g, const rvTapShape* s, WgradPlan* p) {
-    p->taps = g->kh * g->kw;
-    const int cu = rv_pad32(g->cu), cv = rv_pad32(g->cv);
-    p->tiles_u = rv_ceil_div(cu, 128);
-    p->tiles_v = rv_ceil_div(cv, 128);
-    const int64_t K = (int64_t)s->N * s->H * s->Wu;
-    const int64_t chunks = (K + 31) / 32;
-    const int base = p->taps * p->tiles_u * p->tiles_v;
-    int64_t ks = (1024 + base - 1) / base;  // ~4 blocks per CU
-    if (ks > chunks) ks = chunks;
-    if (ks < 1) ks = 1;
-    const int64_t per = (chunks + ks - 1) / ks;
-    p->k_per_split = (int)(per * 32);
-    p->ksplit = (int)((chunks + per - 1) / per);
-    p->elems = (int64_t)p->taps * cu * cv;
-    // wgrad2: stride 1, whole 64-pixel chunks per image row
-    p->v2 = (g->stride_w == 1) && (s->Wu >= 64);
-    if (p->v2) {
-        p->groups = g->kh * ((g->kw + 2) / 3);
-        p->chunks = s->N * s->H * ((s->Wu + 63) / 64);
-        const int base2 = p->groups * p->tiles_u * p->tiles_v;
+    RV_REQUIRE(g && s, "rv_tap_wgrad: null geometry or shape");
+    RV_REQUIRE(g->kh >= 1 && g->kw >= 1 && g->kh * g->kw <= kMaxTaps, "rv_tap_wgrad: kernel %dx%d unsupported", g->kh, g->kw);
+    RV_REQUIRE(s->Wv == s->Wu * g->stride_w, "rv_tap_wgrad: Wv (%d) must equal Wu (%d) * stride_w (%d)", s->Wv, s->Wu, g->stride_w);
+    RV_REQUIRE(g->cu >= 1 && g->cv >= 1 && s->N >= 1 && s->H >= 1 && s->Wu >= 1, "rv_tap_wgrad: empty tensor");
+    memset(p, 0, sizeof(*p));
+    const int taps = g->kh * g->kw, cu = rv_pad32(g->cu), cv = rv_pad32(g->cv);
+    const int tiles_u = rv_ceil_div(cu, 128), tiles_v = rv_ceil_div(cv, 128);
+    // The generation.  wgrad2 / wgrad3: stride 1, whole 64-pixel chunks per image row.  wgrad3 (the DMA bypasses the registers, its
+    // epilogue stores whole tiles): plain operands, no folded BatchNorm on the way in, and channel counts of whole 128-wide tiles.
+    const bool chunked = (g->stride_w == 1) && (s->Wu >= 64);
+    const bool dma = !(s->flags & (RV_IN_AFFINE | RV_IN_RELU)) && cu % 128 == 0 && cv % 128 == 0;
+    p->gen = !chunked ? 1 : dma ? 3 : 2;
+    auto shape = [&](auto& a) {  // the fields both argument structs have
+        a.N = s->N;
+        a.H = s->H;
+        a.Wu = s->Wu;
+        a.cu_pad = cu;
+        a.cv_pad = cv;
+        a.taps = taps;
+        a.tiles_u = tiles_u;
+        a.tiles_v = tiles_v;
+        a.flags = s->flags & ~(RV_WGRAD_TORCH_LAYOUT | RV_SEL_MASK);
+        for (int t = 0; t < taps; ++t) {
+            a.dh[t] = (int8_t)(t / g->kw - g->pad_h);
+            a.dw[t] = (int8_t)(t % g->kw - g->pad_w);
+        }
+    };
+    if (p->gen == 1) {
+        WgradArgs& a = p->a1;
+        shape(a);
+        a.Wv = s->Wv;
+        a.stride_w = g->stride_w;
+        const int64_t chunks = ((int64_t)s->N * s->H * s->Wu + 31) / 32;  // K steps of 32 pixels
+        const int base = taps * tiles_u * tiles_v;
+        int64_t ks = (1024 + base - 1) / base;  // ~4 blocks per CU
+        if (ks > chunks) ks = chunks;
+        const int64_t per = (chunks + ks - 1) / ks;
+        a.k_per_split = (int)(per * 32);
+        a.ksplit = p->ksplit = (int)((chunks + per - 1) / per);
+        p->grid = base * p->ksplit;
+        p->block = 256;
+    } else {
+        Wgrad2Args& b = p->a2;
+        shape(b);
+        b.groups = g->kh * ((g->kw + 2) / 3);
+        for (int ky = 0, gi = 0; ky < g->kh; ++ky)
+            for (int kx = 0; kx < g->kw; kx += 3, ++gi) {
+                b.g_first[gi] = (int8_t)(ky * g->kw + kx);
+                b.g_count[gi] = (int8_t)((g->kw - kx) < 3 ? (g->kw - kx) : 3);
+            }
+        b.chunks = s->N * s->H * ((s->Wu + 63) / 64);
+        const int base2 = b.groups * tiles_u * tiles_v;
         // split-K factor: ONE round of workgroups, as close to 256 as the tile count allows (round-4 sweep over the factor,
         // profiles/r04_wgrad_ksplit.txt: 128 <-> 128 3x3 at W = 2656 takes 185 us with 255 workgroups and 220-290 us with 504 / 768
         // / 1008; 256 <-> 256 3x3 504 us with 252 against 528 with 768; the 1x1 256 <-> 256 107 us with 256 against 155 with 1024;
         // 512 <-> 512 the same with 240 and 768 -- every extra round pays the per-workgroup prologue, the 196 KB slab and its
         // share of the reduction again), at least 32 K chunks per block so that the fp32 slab traffic stays small next to the MFMA
         // work; layers with more tiles than CUs take no split at all
-        int64_t ks_max = p->chunks / 32;
+        int64_t ks_max = b.chunks / 32;
         if (ks_max < 1) ks_max = 1;
         const int64_t cus = rv_cu_count();
         int64_t ks2 = cus / base2;
         if (ks2 < 1) ks2 = 1;
         if (ks2 > ks_max) ks2 = ks_max;
-        p->chunks_per_split = (int)((p->chunks + ks2 - 1) / ks2);
-        p->ksplit = (p->chunks + p->chunks_per_split - 1) / p->chunks_per_split;
-        p->main_blocks = base2 * p->ksplit;
-        p->left_m = 0;
-        p->left_blocks = 0;
+        b.chunks_per_split = (int)((b.chunks + ks2 - 1) / ks2);
+        b.ksplit = (b.chunks + b.chunks_per_split - 1) / b.chunks_per_split;
+        b.main_blocks = base2 * b.ksplit;
+        int left_blocks = 0;
         // Balanced split (wgrad3): 48 tiles (512 <-> 512, 3x3) take 5 slices each = 240 workgroups on 256 CUs.  The 16 idle CUs get
         // work: every tile keeps 5 slices of L chunks and leaves a remainder R = C - 5 L that a "remainder" workgroup sums for m = 3
         // tiles in turn (one more slab per tile, three epilogues for that workgroup), with m R + (m - 1) overhead = L so that all 256
         // workgroups finish together.  The regular slices of all tiles still cover the same pixels at the same time (L2 sharing), and
         // so do the remainders.
         const int64_t free_cus = cus - (int64_t)base2 * ks2;
-        if (wgrad_dma_eligible(g, s) && ks2 >= 2 && p->ksplit == ks2 && free_cus >= 8 &&
-            (int64_t)base2 * ks2 * 100 < cus * 96) {
+        if (p->gen == 3 && ks2 >= 2 && b.ksplit == ks2 && free_cus >= 8 && (int64_t)base2 * ks2 * 100 < cus * 96) {
             const int64_t m = (base2 + free_cus - 1) / free_cus;
             const int64_t ovh = 24;  // chunks one more prologue + epilogue is worth
-            const int64_t len = (m * p->chunks + (m - 1) * ovh + m * ks2) / (m * ks2 + 1);  // (rounded up)
-            const int64_t rem = p->chunks - ks2 * len;
+            const int64_t len = (m * b.chunks + (m - 1) * ovh + m * ks2) / (m * ks2 + 1);  // (rounded up)
+            const int64_t rem = b.chunks - ks2 * len;
             if (m <= 4 && rem >= 32 && len >= 32) {
-                p->chunks_per_split = (int)len;
-                p->ksplit = (int)ks2 + 1;
-                p->main_blocks = base2 * (int)ks2;
-                p->left_m = (int)m;
-                p->left_blocks = (int)((base2 + m - 1) / m);
+                b.chunks_per_split = (int)len;
+                b.ksplit = (int)ks2 + 1;
+                b.main_blocks = base2 * (int)ks2;
+                b.left_m = (int)m;
+                left_blocks = (int)((base2 + m - 1) / m);
             }
         }
+#ifdef RV_DIAG_NO_XCD_REMAP  // (diagnostic build only, profiles/tools/diag_wgrad.sh: every K slice spread over all eight L2s -- the slope of time against L2-miss traffic)
+        b.xcd_remap = 0;
+#else
+        b.xcd_remap = 1;
+#endif
+        p->ksplit = b.ksplit;
+        p->grid = b.main_blocks + left_blocks;
+        p->block = 512;
+        p->lds = p->gen == 3 ? kW3Lds : 0;
     }
+    p->elems = (int64_t)taps * cu * cv;
+    p->workspace_bytes = p->elems * p->ksplit * (int64_t)sizeof(float);
+    p->reduce_blocks = (int)((p->elems / 4 + 255) / 256 < 4096 ? (p->elems / 4 + 255) / 256 : 4096);
+    p->up = UnpackTo{(s->flags & RV_WGRAD_TORCH_LAYOUT) ? 1 : 0, g->cu, g->cv, cu, cv, taps};
     return 0;
 }
 
@@ -853,138 +895,59 @@ int plan(const rvTapGeom* g, const rvTapShape* s, WgradPlan* p) {
 
 extern "C" int64_t rv_tap_wgrad_workspace_bytes(const rvTapGeom* g, const rvTapShape* s) {
     WgradPlan p;
-    plan(g, s, &p);
-    return p.elems * p.ksplit * (int64_t)sizeof(float);
+    return plan(g, s, &p) ? -1 : p.workspace_bytes;
 }
-
-namespace {
-bool wgrad_dma_eligible(const rvTapGeom* g, const rvTapShape* s) {
-    return !(s->flags & (RV_IN_AFFINE | RV_IN_RELU)) && rv_pad32(g->cu) % 128 == 0 && rv_pad32(g->cv) % 128 == 0;
-}
-}  // namespace
 
 extern "C" int rv_tap_wgrad_info(const rvTapGeom* g, const rvTapShape* s, int32_t* host_info) {
-    RV_REQUIRE(g && s && host_info, "rv_tap_wgrad_info: null argument");
+    RV_REQUIRE(host_info, "rv_tap_wgrad_info: null argument");
     WgradPlan p;
-    plan(g, s, &p);
-    host_info[0] = p.v2 ? (wgrad_dma_eligible(g, s) ? 3 : 2) : 1;
+    if (plan(g, s, &p)) return 1;
+    host_info[0] = p.gen;
     host_info[1] = p.ksplit;
-    host_info[2] = p.v2 ? p.main_blocks + p.left_blocks : p.tiles_v * p.tiles_u * p.taps * p.ksplit;
+    host_info[2] = p.grid;
     return 0;
 }
 
 extern "C" int rv_tap_wgrad(const rvTapGeom* g, const rvTapShape* s, const void* U, int32_t ld_u, const void* V,
                             int32_t ld_v, const float* in_scale, const float* in_shift, int32_t v_affine,
                             float* dT_packed, void* workspace, rvStream stream) {
-    RV_REQUIRE(g && s && U && V && dT_packed && workspace, "rv_tap_wgrad: null argument");
-    RV_REQUIRE(s->Wv == s->Wu * g->stride_w, "rv_tap_wgrad: Wv (%d) must equal Wu (%d) * stride_w (%d)", s->Wv, s->Wu, g->stride_w);
-    RV_REQUIRE(!(s->flags & RV_IN_AFFINE) || (in_scale && in_shift), "rv_tap_wgrad: RV_IN_AFFINE without scale/shift");
-    RV_REQUIRE(g->kh * g->kw <= kMaxTaps, "rv_tap_wgrad: kernel %dx%d unsupported", g->kh, g->kw);
+    RV_REQUIRE(U && V && dT_packed && workspace, "rv_tap_wgrad: null argument");
     WgradPlan p;
-    plan(g, s, &p);
-    UnpackTo up;
-    up.on = (s->flags & RV_WGRAD_TORCH_LAYOUT) ? 1 : 0;
-    up.cu = g->cu;
-    up.cv = g->cv;
-    up.cu_pad = rv_pad32(g->cu);
-    up.cv_pad = rv_pad32(g->cv);
-    up.taps = g->kh * g->kw;
-    if (p.v2) {
-        Wgrad2Args b;
-        memset(&b, 0, sizeof(b));
-        b.U = (const bf16_t*)U;
-        b.V = (const bf16_t*)V;
-        b.scale = in_scale;
-        b.shift = in_shift;
-        b.slabs = (float*)workspace;
-        b.N = s->N;
-        b.H = s->H;
-        b.Wu = s->Wu;
-        b.cu_pad = rv_pad32(g->cu);
-        b.cv_pad = rv_pad32(g->cv);
-        b.ld_u = ld_u;
-        b.ld_v = ld_v;
-        RV_REQUIRE(ld_u >= b.cu_pad && ld_v >= b.cv_pad && ld_u % 8 == 0 && ld_v % 8 == 0, "rv_tap_wgrad: bad channel strides");
-        b.taps = p.taps;
-        b.groups = p.groups;
-        b.ksplit = p.ksplit;
-        b.chunks_per_split = p.chunks_per_split;
-        b.chunks = p.chunks;
-        b.main_blocks = p.main_blocks;
-        b.left_m = p.left_m;
-        b.tiles_u = p.tiles_u;
-        b.tiles_v = p.tiles_v;
-        b.flags = s->flags & ~(RV_WGRAD_TORCH_LAYOUT | RV_SEL_MASK);
-        b.v_affine = v_affine;
-#ifdef RV_DIAG_NO_XCD_REMAP  // (diagnostic build only, profiles/tools/diag_wgrad.sh: every K slice spread over all eight L2s -- the slope of time against L2-miss traffic)
-        b.xcd_remap = 0;
-#else
-        b.xcd_remap = 1;
-#endif
-        int gi = 0;
-        for (int ky = 0; ky < g->kh; ++ky)
-            for (int kx = 0; kx < g->kw; ++kx) {
-                b.dh[ky * g->kw + kx] = (int8_t)(ky - g->pad_h);
-                b.dw[ky * g->kw + kx] = (int8_t)(kx - g->pad_w);
-                if (kx % 3 == 0) {
-                    b.g_first[gi] = (int8_t)(ky * g->kw + kx);
-                    b.g_count[gi] = (int8_t)((g->kw - kx) < 3 ? (g->kw - kx) : 3);
-                    ++gi;
-                }
-            }
-        hipStream_t st2 = (hipStream_t)stream;
-        const int grid2 = p.main_blocks + p.left_blocks;
-        const bool dma = wgrad_dma_eligible(g, s);
-        if (dma) {
-            RV_LDS_OPT_IN(160 * 1024, wgrad3_kernel);
-            hipLaunchKernelGGL(wgrad3_kernel, dim3(grid2), dim3(512), kW3Lds, st2, b);
-            RV_CHECK_LAUNCH("wgrad3_kernel");
-        } else {
-            hipLaunchKernelGGL(wgrad2_kernel, dim3(grid2), dim3(512), 0, st2, b);
-            RV_CHECK_LAUNCH("wgrad2_kernel");
-        }
-#ifndef RV_DIAG_SKIP_REDUCE  // (diagnostic build only: WRONG gradients -- an upper bound on what ANY way of folding the split-K reduction away can return)
-        const int rb2 = (int)((p.elems / 4 + 255) / 256 < 4096 ? (p.elems / 4 + 255) / 256 : 4096);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rb2), dim3(256), 0, st2, (const float*)workspace, p.ksplit, p.elems, dT_packed, up);
-        RV_CHECK_LAUNCH("wgrad_reduce_kernel");
-#endif
-        return 0;
-    }
-    WgradArgs a;
-    memset(&a, 0, sizeof(a));
-    a.U = (const bf16_t*)U;
-    a.V = (const bf16_t*)V;
-    a.scale = in_scale;
-    a.shift = in_shift;
-    a.slabs = (float*)workspace;
-    a.N = s->N;
-    a.H = s->H;
-    a.Wu = s->Wu;
-    a.Wv = s->Wv;
-    a.cu_pad = rv_pad32(g->cu);
-    a.cv_pad = rv_pad32(g->cv);
-    a.ld_u = ld_u;
-    a.ld_v = ld_v;
-    RV_REQUIRE(ld_u >= a.cu_pad && ld_v >= a.cv_pad && ld_u % 8 == 0 && ld_v % 8 == 0, "rv_tap_wgrad: bad channel strides");
-    a.stride_w = g->stride_w;
-    a.taps = p.taps;
-    a.ksplit = p.ksplit;
-    a.k_per_split = p.k_per_split;
-    a.tiles_u = p.tiles_u;
-    a.tiles_v = p.tiles_v;
-    a.flags = s->flags & ~(RV_WGRAD_TORCH_LAYOUT | RV_SEL_MASK);
-    a.v_affine = v_affine;
-    for (int ky = 0; ky < g->kh; ++ky)
-        for (int kx = 0; kx < g->kw; ++kx) {
-            a.dh[ky * g->kw + kx] = (int8_t)(ky - g->pad_h);
-            a.dw[ky * g->kw + kx] = (int8_t)(kx - g->pad_w);
-        }
+    if (plan(g, s, &p)) return 1;
+    RV_REQUIRE(!(s->flags & RV_IN_AFFINE) || (in_scale && in_shift), "rv_tap_wgrad: RV_IN_AFFINE without scale/shift");
+    RV_REQUIRE(ld_u >= p.up.cu_pad && ld_v >= p.up.cv_pad && ld_u % 8 == 0 && ld_v % 8 == 0, "rv_tap_wgrad: bad channel strides");
+    auto bind = [&](auto& a) {
+        a.U = (const bf16_t*)U;
+        a.V = (const bf16_t*)V;
+        a.scale = in_scale;
+        a.shift = in_shift;
+        a.slabs = (float*)workspace;
+        a.ld_u = ld_u;
+        a.ld_v = ld_v;
+        a.v_affine = v_affine;
+    };
     hipStream_t st = (hipStream_t)stream;
-    const int grid = p.tiles_v * p.tiles_u * p.taps * p.ksplit;
-    hipLaunchKernelGGL(wgrad_kernel, dim3(grid), dim3(256), 0, st, a);
-    RV_CHECK_LAUNCH("wgrad_kernel");
-    const int rb = (int)((p.elems / 4 + 255) / 256 < 4096 ? (p.elems / 4 + 255) / 256 : 4096);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rb), dim3(256), 0, st, (const float*)workspace, p.ksplit, p.elems, dT_packed, up);
+    switch (p.gen) {
+        case 1:
+            bind(p.a1);
+            hipLaunchKernelGGL(wgrad_kernel, dim3(p.grid), dim3(p.block), p.lds, st, p.a1);
+            RV_CHECK_LAUNCH("wgrad_kernel");
+            break;
+        case 2:
+            bind(p.a2);
+            hipLaunchKernelGGL(wgrad2_kernel, dim3(p.grid), dim3(p.block), p.lds, st, p.a2);
+            RV_CHECK_LAUNCH("wgrad2_kernel");
+            break;
+        default:
+            bind(p.a2);
+            RV_LDS_OPT_IN(160 * 1024, wgrad3_kernel);
+            hipLaunchKernelGGL(wgrad3_kernel, dim3(p.grid), dim3(p.block), p.lds, st, p.a2);
+            RV_CHECK_LAUNCH("wgrad3_kernel");
+    }
+#ifdef RV_DIAG_SKIP_REDUCE  // (diagnostic build only: WRONG gradients -- an upper bound on what ANY way of folding the split-K reduction away can return)
+    if (p.gen != 1) return 0;
+#endif
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(p.reduce_blocks), dim3(256), 0, st, (const float*)workspace, p.ksplit, p.elems, dT_packed, p.up);
     RV_CHECK_LAUNCH("wgrad_reduce_kernel");
     return 0;
 }

@@ -117,6 +117,46 @@ def test_weight_gradient_split_plans(lib):
     assert plan(128, 128, 1) == [3, 256, 256]     # 1x1, one tile: 8192 chunks of 64 pixels over 256 workgroups (never fewer than 32 per workgroup)
 
 
+def test_weight_gradient_plans_equal_the_recorded_table(lib):
+    """Every branch of the weight-gradient planner at 256 compute units: ``tests/golden/wgrad_plans.json`` (``make_golden_wgrad_plans.py``:
+    kernels x strides x channel counts x widths x batches x operand flags, recorded from the library before the planner became one
+    ``WgradPlan``) holds what ``rv_tap_wgrad_info`` and ``rv_tap_wgrad_workspace_bytes`` answered; every row is asked for exactly.  The
+    table reaches all three generations and the balanced split.  The planning entry points refuse what the launch refuses."""
+    h = lib.load()
+    import json
+
+    rec = json.load(open(os.path.join(ROOT, "tests", "golden", "wgrad_plans.json")))
+    assert rec["columns"] == ["kh", "kw", "stride_w", "pad_h", "pad_w", "cu", "cv", "N", "H", "Wu", "Wv", "flags", "gen", "ksplit", "workgroups",
+                              "workspace_bytes"]
+    rows = rec["rows"]
+    assert len(rows) == 4 * 3 * 8 * 8 * 2 * 2 and all(len(r) == 16 for r in rows) and {r[12] for r in rows} == {1, 2, 3}
+    info = (ctypes.c_int32 * 4)()
+
+    def ask(kh, kw, st, ph, pw, cu, cv, n, hh, wu, wv, flags):
+        g, s = lib.TapGeom(kh, kw, st, ph, pw, cu, cv), lib.TapShape(n, hh, wu, wv, 0, 0, flags)
+        info[:] = [-1, -1, -1, -1]
+        rc = h.rv_tap_wgrad_info(ctypes.byref(g), ctypes.byref(s), info)
+        return rc, list(info)[:3], h.rv_tap_wgrad_workspace_bytes(ctypes.byref(g), ctypes.byref(s))
+
+    wrong, balanced = [], 0
+    for row in rows:
+        rc, got, nbytes = ask(*row[:12])
+        if rc != 0 or got + [nbytes] != row[12:]:
+            wrong.append((row, rc, got, nbytes))
+        kh, kw, cu, cv = row[0], row[1], row[5], row[6]
+        tiles_groups = -(-cu // 128) * -(-cv // 128) * kh * ((kw + 2) // 3)  # (the channel counts of generation 3 are whole tiles)
+        balanced += row[12] == 3 and row[13] * tiles_groups != row[14]
+    assert not wrong, (len(wrong), wrong[:5])
+    assert balanced >= 1
+    # a 5x5 kernel (25 taps), and a fine width that is not the coarse one times the stride
+    for bad, word in (((5, 5, 1, 2, 2, 128, 128, 4, 64, 512, 512, 0), b"5x5"), ((3, 3, 2, 1, 1, 128, 128, 4, 64, 1000, 2048, 0), b"stride_w")):
+        g, s = lib.TapGeom(*bad[:7]), lib.TapShape(*bad[7:11], 0, 0, bad[11])
+        assert h.rv_ew_combine(ctypes.c_int64(10), 32, None, 32, None, None, None, 0, None, None, None, 32, 0, None) != 0  # (another message)
+        assert h.rv_tap_wgrad_info(ctypes.byref(g), ctypes.byref(s), info) != 0 and word in h.rv_last_error(), h.rv_last_error()
+        assert h.rv_ew_combine(ctypes.c_int64(10), 32, None, 32, None, None, None, 0, None, None, None, 32, 0, None) != 0
+        assert h.rv_tap_wgrad_workspace_bytes(ctypes.byref(g), ctypes.byref(s)) == -1 and word in h.rv_last_error(), h.rv_last_error()
+
+
 def test_null_arguments_fail_with_message(lib):
     h = lib.load()
     assert h.rv_ew_combine(ctypes.c_int64(10), 32, None, 32, None, None, None, 0, None, None, None, 32, 0, None) != 0
