@@ -21,7 +21,7 @@ import torch
 from torch import Tensor, nn
 
 from . import _lib as L
-from .images import Image, ImageCache
+from .images import Image, ImageCache, source_key
 
 BN_EPS = 1e-5
 BN_MOMENTUM = 0.1
@@ -670,6 +670,7 @@ class TapLayer:
         self.cu, self.cv = cu, cv
         self.images = ImageCache()  # every device image made from the parameters; nothing else on the layer holds one
         self._fold_geom = None
+        self._eval_fold_ok: Optional[Tuple[tuple, bool]] = None  # (source key, decision) of eval_fold_ok: a flag, not an image
         _LAYERS.add(self)
 
     # forward direction of the torch module: conv = gather, conv-transpose = scatter
@@ -762,6 +763,34 @@ class TapLayer:
         e = self.images.get(image_slot(form, "eval_fold"), (self.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var), make, extra=(bn.eps,))
         return e.data, e.aux
 
+    def eval_fold_ok(self, bn: nn.Module) -> bool:
+        """Whether the fp16 image of ``w * gamma / sqrt(var + eps)`` still holds this layer's weights as well as the plain fp16 image does.
+        fp16's normal range ends at 2^-14: a small scale pushes a channel's folded weights into subnormals, which keep an ABSOLUTE
+        step of 2^-24 -- measured on an MI355X with scales of 2^-10 .. 2^-12, the folded conv was up to 7.5 times further from fp64
+        BatchNorm than conv -> fp16 -> BatchNorm in fp32, the route the reference evaluates on; the kernels honour subnormal operands,
+        the loss is the image's own.  A weight the image cannot hold at all (beyond 65504) is the same case at the other end.  Rule,
+        per output channel, E = sum of squared rounding errors of the image / sum of squared weights: the layer is NOT folded when a
+        channel has E(folded) > 2^-22 -- an rms relative error above 2^-11, which no image of normal numbers has -- and
+        E(folded) > 4 E(plain), i.e. the plain image is not just as coarse (a channel of tiny weights to begin with).  Such a layer runs
+        conv -> BatchNorm as a folded operand of its consumer, as with ``EVAL_FOLD = False``.  Decided once per checkpoint (one host
+        read per layer), where ``packed_eval`` would build the image; the bf16 build's range ends at 2^-126: always folded."""
+        if L.operand_tag() != "f16":
+            return True
+        key = source_key(self.weight, bn.weight, bn.running_var, extra=(bn.eps,))
+        if self._eval_fold_ok is None or self._eval_fold_ok[0] != key:
+            scale = (bn.weight.detach().double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)).float()
+            dim = 1 if self.transposed else 0
+
+            def rounding(w: Tensor) -> Tensor:
+                rows = w.transpose(0, dim).reshape(w.shape[dim], -1)
+                return (rows.to(torch.float16).float() - rows).double().square().sum(1) / rows.double().square().sum(1).clamp_min(1e-300)
+
+            w = self.weight.detach().float()
+            folded, plain = rounding(w * (scale.view(1, -1, 1, 1) if self.transposed else scale.view(-1, 1, 1, 1))), rounding(w)
+            coarse = ~(folded <= 2.0 ** -22) & ~(folded <= 4 * plain)  # (negated <=: an infinite or NaN error -- overflow -- counts as coarse)
+            self._eval_fold_ok = (key, not bool(coarse.any()))
+        return self._eval_fold_ok[1]
+
     def padded_bias(self) -> Tensor:
         """fp32 bias padded to the 32-channel slab, cached until the parameter changes (two launches per step and biased layer otherwise)."""
         make = lambda old: torch.nn.functional.pad(self.bias.detach().float(), (0, pad32(self.c_out) - self.c_out))
@@ -773,6 +802,7 @@ class TapLayer:
         move neither (``p.data.add_(...)``, a kernel writing through the raw pointer) do not show there -- call this (or
         ``engine.invalidate_packed_weights``) after such surgery."""
         self.images.clear()
+        self._eval_fold_ok = None
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1187,7 +1217,7 @@ def conv_bn(t: Tape, layer: TapLayer, x: Operand, bn: nn.BatchNorm2d, relu: bool
     that fold the BatchNorm themselves (MetaModulateOp; ``fold_eval=False`` likewise keeps the Lazy form in eval mode)."""
     if smallk and _smallk_eligible(layer, x, relu, need_input_grad):
         return SmallKOp(t, layer, x, bn).out
-    if t.inference and EVAL_FOLD and fold_eval and layer.bias is None:
+    if t.inference and EVAL_FOLD and fold_eval and layer.bias is None and layer.eval_fold_ok(bn):
         # inference: BatchNorm folded into the weight image and the bias, ReLU in the epilogue -- the conv writes the activation
         # itself (no folded operand for the consumer to apply, no write-out pass for the LDS-DMA kernels)
         # (``out``: where the activation goes -- honoured on this path only, the caller checks ``result is out``)
@@ -1202,10 +1232,11 @@ EVAL_RES_FUSE = True
 def conv_bn_residual(t: Tape, layer: TapLayer, x: Operand, bn: nn.BatchNorm2d, res: Operand, relu_conv: bool, relu_out: bool,
                      out: Optional[Act] = None) -> Optional[Act]:
     """Inference: ``relu_out?( relu_conv?(bn(conv(x))) + res )`` in the conv's own launch (BatchNorm folded, residual added in the
-    epilogue: rv_tap_residual).  None when the fusion does not apply (training; folded operands) -- the caller then takes
+    epilogue: rv_tap_residual).  None when the fusion does not apply (training; folded operands; a layer whose fp16 image would
+    underflow: ``TapLayer.eval_fold_ok``) -- the caller then takes
     ``conv_bn`` + ``CombineOp``, whose result is the same bit for bit."""
     if (not t.inference or not (EVAL_FOLD and EVAL_RES_FUSE) or layer.bias is not None or not isinstance(x, Act) or not isinstance(res, Act)
-            or res.cp != pad32(layer.c_out)):
+            or res.cp != pad32(layer.c_out) or not layer.eval_fold_ok(bn)):
         return None
     return ConvOp(t, layer, x, eval_bn=bn, relu_out=relu_conv, residual=res, res_relu=relu_out, out=out).out
 
@@ -1218,7 +1249,7 @@ def conv_bn_many(t: Tape, specs: Sequence[Tuple[TapLayer, Operand, nn.BatchNorm2
     then every BatchNorm is finalised -- under SyncBN with ONE all-reduce for the whole group (``allreduce_partial_rows_many``)
     instead of one per layer; the BnOps sit next to each other on the tape, so the backward pass groups their collectives
     too (``Tape.backward``).  spec = (layer, input, bn, relu, need_input_grad).  Results in spec order."""
-    if t.inference and EVAL_FOLD and all(layer.bias is None for layer, *_ in specs):
+    if t.inference and EVAL_FOLD and all(layer.bias is None and layer.eval_fold_ok(bn) for layer, _, bn, *_ in specs):
         return [ConvOp(t, layer, x, need_input_grad=nig, eval_bn=bn, relu_out=relu).out for layer, x, bn, relu, nig in specs]
     convs = [ConvOp(t, layer, x, stats=t.training, need_input_grad=nig) for layer, x, _, _, nig in specs]
     reduced: List[Optional[Tensor]] = [None] * len(specs)
