@@ -174,17 +174,17 @@ def side_stream(device) -> "torch.cuda.Stream":
 #  (rv-waymo), three interleaved rounds on one box -- the write-out beside a power-capped conv costs more than it hides.)
 
 
-def _launch(name: str, flops: float, fn, nbytes: float = 0.0) -> None:
+def _launch(name, flops: float, fn, nbytes: float = 0.0) -> None:
+    # name: the kernel's profile name, or the conv route that knows it (the planner is asked for it only under a profile)
     if PROFILE is not None:
-        PROFILE.launch(name, flops, fn, nbytes)
+        PROFILE.launch(name if isinstance(name, str) else tap_kernel_name(name), flops, fn, nbytes)
     else:
         fn()
 
 
-def tap_kernel_name(geom, shape, scatter: bool) -> str:
-    info = L.tap_launch_info(geom, shape, scatter)
-    if info is None:
-        raise L.RvError(f"rv_tap_launch_info failed: {L.load().rv_last_error().decode()}")
+def tap_kernel_name(route) -> str:
+    # profile name of the kernel behind a forward / backward-data route (conv_route): the generation the planner answered
+    info, geom, shape, scatter = route.info, route.geom, route.shape, route.image == "scatter"
     if info[0] in (2, 3, 4, 5, 6):
         name = f"tapconv{info[0]}_kernel<{info[1]}>"
     elif info[0] == 7:
@@ -553,7 +553,7 @@ class PendingHeadFinal:  # a tower's final conv fused into the BatchNorm backwar
 # The LDS-DMA tap-conv (tapconv4) streams its operands global -> LDS without passing through registers, so it cannot
 # apply a folded BatchNorm(+ReLU) on the way in.  On the layers it is eligible for it is enough faster than the
 # register-staged kernels (3x3 512 -> 512: 1330 vs 980 TFLOP/s, one box) to pay for writing the operand out once
-# (one HBM-bound pass); forward conv, and the weight gradient in backward, then both read the plain tensor.
+# (one HBM-bound pass); forward conv, and the weight gradient in backward, then both read the plain tensor (conv_route.forward_route).
 MATERIALIZE_FOR_DMA = True  # (module attribute: tests and A/B tools flip it in-process; no environment switch)
 # (Measured and dropped in round 4: the split-K sums of all weight gradients in ONE batched launch at the end of a program's backward --
 #  bit-identical, 76 launches fewer, 1.0-1.6 ms per step SLOWER: the immediate reduction reads slabs that are still in the Infinity Cache.)
@@ -563,41 +563,11 @@ BNB_FUSE = True
 #  masked epilogue -- three 16-byte prefetches per pass, time-neutral to slightly slower; profiles/r04_ab_notes.md.)
 
 
-def _dma_generation(geom, n: int, h: int, wu: int, wv: int, ld_src: int, ld_dst: int, scatter: bool) -> int:
-    """Kernel generation the library would pick for this launch on a PLAIN bf16 operand (rv_tap_launch_info)."""
-    info = L.tap_launch_info(geom, L.TapShape(n, h, wu, wv, ld_src, ld_dst, 0), scatter)
-    return info[0] if info is not None else 0
-
-
-def _dma_eligible(geom, n: int, h: int, wu: int, wv: int, ld_src: int, ld_dst: int, scatter: bool) -> bool:
-    return _dma_generation(geom, n, h, wu, wv, ld_src, ld_dst, scatter) in (4, 5, 6)
-
-
 # 1x1 C -> C layers fed by a folded BatchNorm+ReLU (the stem's second fusion conv): written out once as well when the plain launch runs on the
 # pointwise streaming GEMM (generation 7, round 6) -- write-out + streaming GEMM + wgrad3 on the plain operand against the register-staged
 # tapconv2 + wgrad2 (profiles/r06_ab_notes.md).  Other 1x1 shapes keep the folded operand (the tiled kernel saves what the pass costs).
 MATERIALIZE_FOR_POINTWISE = True
 MATERIALIZE_POINTWISE_C = (256,)  # input widths that take it (128: time-neutral on rv-waymo, +0.27 ms on rv-av2 -- profiles/r06_ab_notes.md section 4; profiles/tools/diag_waymo_stem.py adds it back)
-
-
-def _materialize_operand(x, layer, src, wu: int, wv: int, out, out_f32: bool, eval_bn) -> bool:
-    """Whether ``ConvOp`` writes a folded BatchNorm(+ReLU) operand out once so that its conv runs on a kernel that takes plain operands only."""
-    if not (isinstance(x, Lazy) and MATERIALIZE_FOR_DMA and not out_f32):
-        return False
-    g, form = layer.geom, layer.fwd_form
-    # multi-tap layers on the LDS-DMA kernels (not 1x1 layers in general: there the extra pass costs what the faster kernel saves)
-    if g.kh * g.kw > 1 and _dma_eligible(g, src.N, src.H, wu, wv, src.ld, pad32(layer.c_out), form == "scatter"):
-        return True
-    # 1x1 layers on the pointwise streaming GEMM.  (256 input channels only -- rv-av2's stem.  For 128 input channels (rv-waymo's stem conv, the
-    # 1/2 .. 1/8-resolution layers of both models) the write-out is time-neutral on rv-waymo and +0.27 ms per rv-av2 step: off on that measurement,
-    # profiles/r06_ab_notes.md section 4 -- the fault first met on this route was wgrad3's, fixed there.  Asked with the strides the launch will really have.)
-    if (MATERIALIZE_FOR_POINTWISE and g.kh * g.kw == 1 and layer.bias is None and eval_bn is None and pad32(layer.c_in) in MATERIALIZE_POINTWISE_C
-            and _dma_generation(g, src.N, src.H, wu, wv, pad32(layer.c_in), out.ld if out is not None else pad32(layer.c_out), form == "scatter") == 7):
-        return True
-    # strided multi-tap conv: the FOLDED stride-1 form (forward and weight gradient) then runs on the LDS-DMA kernels instead of the
-    # generic strided ones
-    return (form == "gather" and g.stride_w > 1 and g.kh * g.kw > 1 and layer.fold_geom() is not None and src.ld == src.cp
-            and src.W == g.stride_w * wu and _dma_eligible(layer.fold_geom(), src.N, src.H, wu, wu, g.stride_w * src.ld, pad32(layer.c_out), False))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -977,69 +947,40 @@ class ConvOp(Op):
         self.eval_bn = eval_bn
         assert residual is None or (eval_bn is not None and not out_f32 and not stats)
         self.pos_first: Optional["SmallKOp"] = None
-        src, sc, sh, flags = _operand_parts(x)
-        form = layer.fwd_form
-        g = layer.geom
-        wu, wv = (src.W // g.stride_w, src.W) if form == "gather" else (src.W, src.W * g.stride_w)
-        w_out = wu if form == "gather" else wv
+        from . import conv_route  # (local import: conv_route reads this module's switches)
+
+        src, _, _, in_flags = _operand_parts(x)
         assert src.cp == pad32(layer.c_in), (src.cp, layer.c_in)
-        self.x_plain = None
-        if _materialize_operand(x, layer, src, wu, wv, out, out_f32, eval_bn):
-            self.x_plain = src = x.materialized()
-            sc = sh = None
-            flags = 0
+        assert eval_bn is None or (layer.bias is None and not stats and not t.training)
+        out_flags = ((L.OUT_F32 if out_f32 else 0) | (L.OUT_STATS if stats else 0) | (L.OUT_RELU if eval_bn is not None and relu_out else 0)
+                     | (L.OUT_BIAS if eval_bn is not None or layer.bias is not None else 0) | (L.OUT_RES_RELU if residual is not None and res_relu else 0))
+        r = conv_route.forward_route(layer, src.N, src.H, src.W, src.ld, src.cp, in_flags, out.ld if out else pad32(layer.c_out), out_flags)
+        self.x_plain = x.materialized() if r.write_out else None
+        src, sc, sh, _ = _operand_parts(self.x_plain or x)
+        self.shape, self.rows = r.own, r.rows
+        w_out = r.own.Wv if layer.transposed else r.own.Wu
         self.out_f32 = out_f32
         if out_f32:
-            self.out_t = torch.empty((src.N, src.H, w_out, pad32(layer.c_out)), dtype=torch.float32, device=t.device)
-            dst_ptr, ld_dst = L.ptr(self.out_t), self.out_t.stride(2)
-            flags |= L.OUT_F32
-            self.out = None
+            self.out_t, self.out = torch.empty((src.N, src.H, w_out, pad32(layer.c_out)), dtype=torch.float32, device=t.device), None
         else:
             self.out = out if out is not None else Act.empty(src.N, src.H, w_out, layer.c_out, t.device)
-            dst_ptr, ld_dst = self.out.ptr(), self.out.ld
-        bias = layer.bias
+        dst_ptr = L.ptr(self.out_t) if out_f32 else self.out.ptr()
+        self.partial = partial_rows(self.rows, pad32(layer.c_out), t.device) if stats else None
         if eval_bn is not None:
-            assert bias is None and not stats and not t.training
-            flags |= L.OUT_BIAS | (L.OUT_RELU if relu_out else 0) | (L.OUT_RES_RELU if residual is not None and res_relu else 0)
-            bias_p = None  # (filled below, with the folded weight image)
-        elif bias is not None:
-            flags |= L.OUT_BIAS
-            bias_p = layer.padded_bias()
+            wp, bias_p = layer.packed_eval(r.image, eval_bn)
         else:
-            bias_p = None
-        self.shape = L.TapShape(src.N, src.H, wu, wv, src.ld, ld_dst, flags | (L.OUT_STATS if stats else 0))
-        # a strided gather (stride-2 conv forward) runs on the stride-1 FOLDED view when the LDS-DMA kernels take that
-        lg, lshape, wp = g, self.shape, None
-        gf = layer.fold_geom() if (form == "gather" and g.stride_w > 1 and sc is None and flags & (L.IN_AFFINE | L.IN_RELU) == 0) else None
-        # (the folded view reads row pitch wu * s * ld: only when the fine width is exactly s * wu -- an odd width keeps the generic kernel)
-        if gf is not None and src.ld == src.cp and src.W == g.stride_w * wu and _dma_eligible(gf, src.N, src.H, wu, wu, g.stride_w * src.ld, ld_dst, False):
-            lg = gf
-            lshape = L.TapShape(src.N, src.H, wu, wu, g.stride_w * src.ld, ld_dst, self.shape.flags)
-            wp = layer.packed_folded() if eval_bn is None else "folded"
-        self.partial = None
-        self.rows = 0
-        if stats:
-            self.rows = L.load().rv_tap_stats_rows(lg, lshape, 1 if form == "scatter" else 0)
-            if self.rows < 0:
-                raise L.RvError("rv_tap_stats_rows: " + L.load().rv_last_error().decode())
-            self.partial = partial_rows(self.rows, pad32(layer.c_out), t.device)
-        if eval_bn is not None:
-            wp, bias_p = layer.packed_eval("folded" if isinstance(wp, str) else form, eval_bn)
-        elif wp is None:
-            wp = layer.packed(form)
-        call = lambda: L.call("rv_tap_" + form, lg, lshape, src.ptr(), L.ptr(sc), L.ptr(sh),
+            wp, bias_p = layer.packed(r.image), (layer.padded_bias() if layer.bias is not None else None)
+        call = lambda: L.call("rv_tap_" + layer.fwd_form, r.geom, r.shape, src.ptr(), L.ptr(sc), L.ptr(sh),
                               L.ptr(wp), L.ptr(bias_p), dst_ptr, L.ptr(self.partial), L.stream_ptr())
         if residual is not None:
-            assert sc is None and flags & (L.IN_AFFINE | L.IN_RELU) == 0 and residual.cp == self.out.cp and residual.pixels == self.out.pixels
-            call = lambda: L.call("rv_tap_residual", lg, lshape, 1 if form == "scatter" else 0, src.ptr(),
+            assert sc is None and r.own.flags & (L.IN_AFFINE | L.IN_RELU) == 0 and residual.cp == self.out.cp and residual.pixels == self.out.pixels
+            call = lambda: L.call("rv_tap_residual", r.geom, r.shape, 1 if layer.transposed else 0, src.ptr(),
                                   L.ptr(wp), L.ptr(bias_p), residual.ptr(), residual.ld, dst_ptr, L.stream_ptr())
         if precomputed is not None:
-            assert out is not None and not out_f32 and bias is None
+            assert out is not None and not out_f32 and layer.bias is None
             self.partial, self.rows = precomputed
-        elif PROFILE is not None:
-            _launch(tap_kernel_name(lg, lshape, form == "scatter"), tap_flops(g, self.shape), call, tap_bytes(g, self.shape))
         else:
-            call()
+            _launch(r, tap_flops(layer.geom, self.shape), call, tap_bytes(layer.geom, self.shape))
         self.count = src.N * src.H * w_out
         t.ops.append(self)
 

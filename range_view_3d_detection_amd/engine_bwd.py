@@ -12,7 +12,6 @@ Gradient flow on the tape, in reverse op order:
 
 from __future__ import annotations
 
-import ctypes
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence, Tuple
@@ -21,6 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _lib as L
+from . import conv_route
 from . import engine as E
 from .engine import Act, Lazy, Tape, pad32
 
@@ -65,18 +65,12 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
     if dout is None:
         return
     _release_held_wgrads(t)  # (weight gradients of earlier layers that met no all-reduce since)
-    layer, g = op.layer, op.layer.geom
-    src, sc, sh, in_flags = E._operand_parts(op.x)
-    if op.x_plain is not None:
-        # the forward pass wrote relu(bn(.)) out for the DMA kernel: the weight gradient reads it too
-        src, sc, sh, in_flags = op.x_plain, None, None, 0
-    fwd = layer.fwd_form
-    bwd = "scatter" if fwd == "gather" else "gather"
-    sp = op.shape
+    layer, g, sp = op.layer, op.layer.geom, op.shape
+    # (where the forward pass wrote relu(bn(.)) out for the DMA kernel, the weight gradient reads the plain tensor too)
+    src, sc, sh, in_flags = E._operand_parts(op.x_plain or op.x)
     # ---- input gradient: the opposite tap form -------------------------------------------------
-    fused_first = POS_BWD_FUSE and op.pos_first is not None and op.need_input_grad and t.training
     early_ready = None
-    if fused_first:
+    if POS_BWD_FUSE and op.pos_first is not None and op.need_input_grad and t.training:
         # second positional layer of the MetaKernel stem: dh1 = dy2 W2 is consumed in registers by the first layer's BatchNorm
         # backward + weight gradient (rv_pos_backward_sums) -- no input-gradient tensor, no second pass over it
         _wait_chained_wgrad(t)
@@ -87,98 +81,60 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
         _head_final_sums(op, t, dout)
         return  # (the final conv's weight gradient came out of the same pass)
     elif op.need_input_grad:
-        if isinstance(op.x, Lazy):
-            dst, accumulate = t.lazy_grad_target(op.x)
-        else:
-            dst, accumulate = t.grad_buffer(op.x)
-        shape = L.TapShape(sp.N, sp.H, sp.Wu, sp.Wv, dout.ld, dst.ld, L.OUT_ACCUM if accumulate else 0)
-        bg, bshape = g, shape
-        gf = layer.fold_geom() if (bwd == "gather" and g.stride_w > 1) else None
-        if (gf is not None and dout.ld == dout.cp and dout.W == g.stride_w * sp.Wu
-                and E._dma_eligible(gf, sp.N, sp.H, sp.Wu, sp.Wu, g.stride_w * dout.ld, dst.ld, False)):
-            # backward-data of a ConvTranspose2d = a strided gather over dOut: stride-1 on the folded view (engine.FOLD_STRIDED)
-            bg = gf
-            bshape = L.TapShape(sp.N, sp.H, sp.Wu, sp.Wu, g.stride_w * dout.ld, dst.ld, shape.flags)
-            wp = layer.packed_folded()
-        elif (E.FOLD_STRIDED and bwd == "scatter" and g.stride_w == 2 and g.kh == 1 and g.kw == 1 and g.pad_w == 0 and dst.ld == dst.cp
-              and dst.W == 2 * sp.Wu):
-            # backward-data of a 1x1 stride-2 conv: only the even columns receive anything -- a STRIDE-1 1x1 launch into the
-            # even-column view of the gradient (pixel pitch 2 ld; the one-tap scatter image is the same bytes), odd columns zeroed
-            # unless the buffer already holds another consumer's contribution
-            if not accumulate:
-                dst.data.zero_()
-            bg = L.TapGeom(1, 1, 1, 0, 0, g.cu, g.cv)
-            bshape = L.TapShape(sp.N, sp.H, sp.Wu, sp.Wu, dout.ld, 2 * dst.ld, shape.flags)
-            wp = layer.packed(bwd)
-        else:
-            wp = layer.packed(bwd)
-        call = lambda: L.call("rv_tap_" + bwd, bg, bshape, dout.ptr(), None, None, L.ptr(wp), None,
-                              dst.ptr(), None, L.stream_ptr())
-        if E.BNB_FUSE and bg is g and isinstance(op.x, Lazy) and not accumulate and op.x.bn.mean is not None:
-            # first (often only) consumer of relu(bn(y)): this launch can form that BatchNorm's backward sums on the way out
-            rows = L.load().rv_tap_bnb_rows(g, shape, 1 if bwd == "scatter" else 0)
-            if rows > 0:
-                lz, st = op.x, op.x.bn
-                partial = E.partial_rows(rows, dst.cp, t.device)
-                epi = L.BnbEpilogue(lz.raw.ptr(), lz.raw.ld, L.BNB_RELU_Z if lz.relu else 0, L.ptr(st.scale), L.ptr(st.shift),
-                                    L.ptr(st.mean), L.ptr(st.invstd), L.ptr(partial))
-                call = lambda: L.call("rv_tap_data_grad_bnb", g, shape, 1 if bwd == "scatter" else 0, dout.ptr(),
-                                      L.ptr(wp), dst.ptr(), epi, L.stream_ptr())
-                t.pending[id(lz)].sums = E.BnbSums(partial, rows, dst)
-        if E.OVERLAP_WGRAD and E.EARLY_WGRAD_FILL > 0:
-            # a persistent backward-data launch whose LAST round of tiles fills only part of the chip (1328 tiles on 256 CUs: five full
-            # rounds and 48 tiles): the weight gradient of the same layer -- it reads dOut and the layer input, both complete -- is
-            # released on an event recorded BEFORE this launch instead of after it, so both are eligible at once.  Nothing orders the
-            # two on the hardware queues: the intent is that the weight gradient's workgroups take CUs as the last round leaves them idle;
-            # when they take some earlier, this launch's rounds stretch by the same amount.  Kept on the measurement alone: rv-waymo
-            # -1.0 ms chained / -0.15 ms free-running, rv-av2 (no ragged launch) unchanged (profiles/r04_ab_notes.md, r05_ab_notes.md)
-            info = L.tap_launch_info(bg, bshape, bwd == "scatter")
-            if info is not None and info[0] == 6:
-                wg_tiles, cus = info[2] * info[3], E.cu_count(t.device)
-                if wg_tiles / (cus * ((wg_tiles + cus - 1) // cus)) < E.EARLY_WGRAD_FILL:
-                    early_ready = torch.cuda.Event()
-                    early_ready.record()
-                    t.chained_wgrad = None  # ... and this launch does not wait for the weight gradient before it either: its own tail is where that one ends
+        lazy = op.x if isinstance(op.x, Lazy) else None
+        dst, accumulate = t.lazy_grad_target(lazy) if lazy is not None else t.grad_buffer(op.x)
+        dr = conv_route.dgrad_route(layer, sp, dout.W, dout.ld, dout.cp, dst.W, dst.ld, dst.cp, accumulate,
+                                    lazy is not None and lazy.bn.mean is not None, lambda: E.cu_count(t.device))
+        if dr.zero_first:
+            dst.data.zero_()
+        wp = layer.packed(dr.image)
+        call = lambda: L.call("rv_tap_scatter" if dr.image == "scatter" else "rv_tap_gather", dr.geom, dr.shape, dout.ptr(), None, None,
+                              L.ptr(wp), None, dst.ptr(), None, L.stream_ptr())
+        if dr.bnb_rows:
+            st = lazy.bn
+            partial = E.partial_rows(dr.bnb_rows, dst.cp, t.device)
+            epi = L.BnbEpilogue(lazy.raw.ptr(), lazy.raw.ld, L.BNB_RELU_Z if lazy.relu else 0, L.ptr(st.scale), L.ptr(st.shift),
+                                L.ptr(st.mean), L.ptr(st.invstd), L.ptr(partial))
+            call = lambda: L.call("rv_tap_data_grad_bnb", dr.geom, dr.shape, 1 if dr.image == "scatter" else 0, dout.ptr(),
+                                  L.ptr(wp), dst.ptr(), epi, L.stream_ptr())
+            t.pending[id(lazy)].sums = E.BnbSums(partial, dr.bnb_rows, dst)
+        if dr.early:
+            early_ready = torch.cuda.Event()
+            early_ready.record()
+            t.chained_wgrad = None  # ... and this launch does not wait for the weight gradient before it either: its own tail is where that one ends
         _wait_chained_wgrad(t)
-        if E.PROFILE is not None:
-            E._launch(E.tap_kernel_name(bg, bshape, bwd == "scatter"), E.tap_flops(g, shape), call, E.tap_bytes(g, shape))
-        else:
-            call()
-        if not isinstance(op.x, Lazy):
+        E._launch(dr, E.tap_flops(g, sp), call, E.tap_bytes(g, sp))
+        if lazy is None:
             t.mark_written(op.x)
     # ---- weight gradient ---------------------------------------------------------------------------
-    u, v, v_affine = (dout, src, 1) if fwd == "gather" else (src, dout, 0)
-    wshape = L.TapShape(sp.N, sp.H, sp.Wu, sp.Wv, 0, 0, in_flags | L.WGRAD_TORCH_LAYOUT)
-    # strided layers: the weight gradient on the stride-1 FOLDED view of the fine tensor (wgrad3 instead of the generic kernel),
-    # then rv_unfold_weight_grad picks the kernel's own entries out of the folded gradient
-    wg, wsh, ld_v = g, wshape, v.ld
-    gfw = layer.fold_geom() if (g.stride_w > 1 and sc is None and in_flags == 0 and v.ld == v.cp and v.W == g.stride_w * sp.Wu) else None
-    if gfw is not None:
-        wg, wsh, ld_v = gfw, L.TapShape(sp.N, sp.H, sp.Wu, sp.Wu, 0, 0, L.WGRAD_TORCH_LAYOUT), g.stride_w * v.ld
+    u, v, v_affine = (src, dout, 0) if layer.transposed else (dout, src, 1)
+    wr = conv_route.wgrad_route(layer, sp, in_flags, v.W, v.ld, v.cp)
 
     def run_wgrad() -> None:
-        ws_bytes = L.load().rv_tap_wgrad_workspace_bytes(wg, wsh)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=t.device)
+        wg = wr.geom
+        ws = torch.empty(L.load().rv_tap_wgrad_workspace_bytes(wg, wr.shape), dtype=torch.uint8, device=t.device)
         grad = torch.empty((wg.cu, wg.cv, wg.kh, wg.kw), dtype=torch.float32, device=t.device)
-        wname = "wgrad_kernel(+reduce)"
-        if E.PROFILE is not None:
-            winfo = (ctypes.c_int32 * 4)()
-            L.call("rv_tap_wgrad_info", wg, wsh, winfo)
-            wname = ("wgrad_kernel", "wgrad_kernel", "wgrad2_kernel", "wgrad3_kernel")[winfo[0]] + "(+reduce)"
+        generation = wr.generation if E.PROFILE is not None else 0  # (asked of the planner only under a profile: the name is not read otherwise)
+        wname = ("wgrad_kernel", "wgrad_kernel", "wgrad2_kernel", "wgrad3_kernel")[generation] + "(+reduce)"
         if os.environ.get("RV3D_PROFILE_SHAPES"):
-            wname += f" k{g.kh}x{g.kw}s{g.stride_w} {g.cu}<->{g.cv} {wshape.N}x{wshape.H}x{wshape.Wu}"
+            wname += f" k{g.kh}x{g.kw}s{g.stride_w} {g.cu}<->{g.cv} {sp.N}x{sp.H}x{sp.Wu}"
         # the split-K reduction (one small launch behind the kernel) writes the torch layout dT[cu][cv][kh][kw] itself
         # (RV_WGRAD_TORCH_LAYOUT): no unpack pass
-        E._launch(wname, E.tap_flops(g, wshape),
-                  lambda: L.call("rv_tap_wgrad", wg, wsh, u.ptr(), u.ld, v.ptr(), ld_v,
+        E._launch(wname, E.tap_flops(g, sp),
+                  lambda: L.call("rv_tap_wgrad", wg, wr.shape, u.ptr(), u.ld, v.ptr(), wr.v_pitch * v.ld,
                                  L.ptr(sc), L.ptr(sh), v_affine, L.ptr(grad), L.ptr(ws), L.stream_ptr()),
-                  E.tap_bytes(g, wshape, wgrad=True))
-        if wg is not g:
+                  E.tap_bytes(g, sp, wgrad=True))
+        if wr.unfold:
             folded, grad = grad, torch.empty((g.cu, g.cv, g.kh, g.kw), dtype=torch.float32, device=t.device)
             L.call("rv_unfold_weight_grad", g, L.ptr(folded), L.ptr(grad), 0, L.stream_ptr())
         t.add_param_grad(layer.weight, layer.unpermute_grad(grad))
 
-    small = E.OVERLAP_MAX_TFLOP is None or E.tap_flops(g, wshape) < 1e12 * E.OVERLAP_MAX_TFLOP
+    _schedule_wgrad(t, run_wgrad, E.tap_flops(g, sp), early_ready)
+
+
+def _schedule_wgrad(t: Tape, run_wgrad, flops: float, early_ready) -> None:
+    """Where a weight gradient runs: held for SyncBN, side stream behind an event (``early_ready``: an earlier one), chained, inline."""
+    small = E.OVERLAP_MAX_TFLOP is None or flops < 1e12 * E.OVERLAP_MAX_TFLOP
     if E.OVERLAP_WGRAD and E.HOLD_WGRAD_FOR_SYNC_BN and E.sync_bn_active():
         # Synchronised BatchNorm statistics over real ranks: the all-reduce of the NEXT BatchNorm backward is an RCCL kernel that needs a
         # CU slot, and it becomes ready at the same moment as this weight gradient (both wait for the backward-data launch above).  A
@@ -188,18 +144,8 @@ def conv_backward(op: "E.ConvOp", t: Tape) -> None:
         # exactly as in the local case.
         t.held_wgrads.append(run_wgrad)
     elif E.OVERLAP_WGRAD and (small or E.OVERLAP_CHAIN):
-        side = E.side_stream(t.device)
-        ready = early_ready
-        if ready is None:
-            ready = torch.cuda.Event()
-            ready.record()  # dout (and everything before it on the main stream) is complete at this point of the main stream
-        side.wait_event(ready)
-        with torch.cuda.stream(side):
-            run_wgrad()
-            if E.OVERLAP_CHAIN and not small:  # chained: the main stream's next MFMA-bound launch waits for this one (_wait_chained_wgrad)
-                t.chained_wgrad = torch.cuda.Event()
-                t.chained_wgrad.record()
-        t.used_side_stream = True
+        # chained: the main stream's next MFMA-bound launch waits for this one (_wait_chained_wgrad)
+        _on_side_stream(t, [run_wgrad], early_ready, chain=E.OVERLAP_CHAIN and not small)
     else:
         run_wgrad()
 
@@ -240,16 +186,24 @@ def _head_final_sums(op: "E.ConvOp", t: Tape, dY: Act) -> None:
 def _release_held_wgrads(t: Tape) -> None:
     """Launch the weight gradients held back for a SyncBN all-reduce (see conv_backward) on the side stream, behind everything the
     main stream has been given so far."""
-    if not t.held_wgrads:
-        return
+    if t.held_wgrads:
+        _on_side_stream(t, t.held_wgrads)
+        t.held_wgrads = []
+
+
+def _on_side_stream(t: Tape, runs, ready=None, chain: bool = False) -> None:
+    """``runs`` on the side stream behind ``ready`` (None: an event recorded now); ``chain``: leave an event for the main stream to wait on."""
     side = E.side_stream(t.device)
-    ready = torch.cuda.Event()
-    ready.record()
+    if ready is None:
+        ready = torch.cuda.Event()
+        ready.record()  # dout (and everything before it on the main stream) is complete at this point of the main stream
     side.wait_event(ready)
     with torch.cuda.stream(side):
-        for run in t.held_wgrads:
+        for run in runs:
             run()
-    t.held_wgrads = []
+        if chain:
+            t.chained_wgrad = torch.cuda.Event()
+            t.chained_wgrad.record()
     t.used_side_stream = True
 
 
